@@ -17,7 +17,21 @@ every rank draws exactly its own members on its own GPU), state and parameters r
 trajectory rows written every step.  Timesteps cycle through the 750-step scenario (t = k mod 750); the
 default K + W = 750 is exactly one scenario pass.
 
-Rank 0 prints ONE JSON line.  `value` = (members on all GPUs) x K / the K-step block time, MAX over ranks: the block is
+A PLAIN run (no --full) does only what `value` needs: set-up, W warm-up steps, EXACTLY K timed steps — ONE K-step block,
+HIP event to HIP event on the launch stream(s) (barrier and device sync before it, then the last min(W, 5) warm-up steps
+enqueued right in front of it, so that it starts on a busy queue as a block inside a long run does; MAX over ranks) — then, with
+--dump-outputs DIR, what those steps computed (below), and the line: `metric`, `value`, `unit`, `ms_per_step` (= the block / K),
+`higher_is_better`, `dtype`, `config`, `timing`.  Everything else this file measures — the repeated blocks, the host enqueue
+time, the CPU baseline, `roofline` and the legs beside it, the end-of-run summary exchange — runs with --full only, as described
+below.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed, as DIR/<name>.npy in the run's dtype: the rows that
+step stored, `C` [gases, members] and `T` [members] (when the trajectory is stored), and the state it left, `R` [pools, members]
+and `S` [2, members].  At most 64 MB in all: a larger ensemble is written as a fixed, seeded sample of member columns, the
+same members in every array (DUMP_SEED).  The inputs are fixed by the arguments (seeded design, frozen emissions), so two
+builds can be compared output for output.  With N > 1 ranks each writes its own shard as rank<r>_<name>.npy, 64 MB over all.
+
+WITH --full, rank 0 prints ONE JSON line.  `value` = (members on all GPUs) x K / the K-step block time, MAX over ranks: the block is
 clocked once on the wall clock (barrier, device sync, clock, K steps, drain, clock: `timing.first_block_ms_per_step`) and then
 repeated back to back for --timed-s (6.5) seconds of device time, HIP event to HIP event; the MEDIAN block is reported.
 `timing.host_enqueue_us_per_step` / `host_share` say how long the rank's host thread needs to enqueue a step with all ranks
@@ -72,6 +86,46 @@ WORKLOADS = {
     "config4": ("multigas", 3, 1_250_000, "BASELINE configs[3]: 10M-member multi-gas ensemble over 8 GPUs (1.25M/GPU)"),
     "config5": ("multigas", 3, 12_500_000, "BASELINE configs[4]: 100M-member multi-gas ensemble over 8 GPUs (12.5M/GPU)"),
 }
+DUMP_BUDGET_BYTES = 64_000_000      # --dump-outputs: all arrays together, .npy headers included
+DUMP_SEED = 20261015                # the member sample of an ensemble whose outputs exceed the budget
+
+
+def dump_members(n_members, bytes_per_member, budget=DUMP_BUDGET_BYTES):
+    """The member columns --dump-outputs writes: None = all of them when they fit `budget`, else the largest fixed, seeded
+    sample that does (sorted indices; the same for every run with the same ensemble size and budget)."""
+    if n_members * bytes_per_member <= budget:
+        return None
+    keep = max(1, budget // bytes_per_member)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_members, keep, replace=False))
+
+
+def dump_outputs(eng, t_last, out_dir, prefix="", budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the run's last step (scenario index `t_last`) computed, as <out_dir>/<prefix><name>.npy in the
+    engine's dtype — the rows that step stored (C [G, N], T [N]; when the trajectory is stored) and the state it left
+    (R [pools, N], S [2, N]); a member sample (dump_members) when they exceed `budget`.  Returns what the line reports."""
+    import torch
+    torch.cuda.synchronize(eng.device)
+    arrays = {}
+    if eng.T is not None:
+        row = int(np.searchsorted(eng.out_steps, t_last))
+        if row < eng.n_rows and eng.out_steps[row] == t_last:
+            if eng.C is not None:
+                arrays["C"] = eng.C[row]
+            arrays["T"] = eng.T[row]
+    arrays["R"], arrays["S"] = eng.R, eng.S
+    n = eng.n_members
+    per_member = sum(x.numel() // n for x in arrays.values()) * eng.R.element_size()
+    idx = dump_members(n, per_member, budget - 256 * len(arrays))
+    sel = None if idx is None else torch.from_numpy(idx).to(eng.device)
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, x in arrays.items():
+        host = (x if sel is None else x.index_select(x.dim() - 1, sel)).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), host)
+        shapes[name] = list(host.shape)
+    return {"dir": out_dir, "step": int(t_last), "arrays": shapes, "dtype": str(eng.R.dtype).replace("torch.", ""),
+            "members": n if idx is None else int(idx.size),
+            "member_sample": None if idx is None else f"np.random.default_rng({DUMP_SEED}).choice({n}, {idx.size}, replace=False), sorted"}
 
 
 def parse():
@@ -115,6 +169,13 @@ def parse():
     ap.add_argument("--numpy-baseline", action="store_true",
                     help="add SURVEY 8d's NumPy legs to cpu_baseline: N = 1e5 on one core and on one process per usable "
                          "core, CO2-only and multi-gas (baseline only; adds ~1-2 min)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (repeated blocks for --timed-s, host enqueue time, CPU baseline, "
+                         "roofline and its legs, live traffic, end-of-run summary exchange); the options above that tune those "
+                         "legs act only with --full.  Default: set-up, warm-up, exactly --steps timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (C, T rows and the R, S state) as "
+                         "DIR/<name>.npy, at most 64 MB in all (a fixed, seeded member sample of a larger ensemble)")
     return ap.parse_args()
 
 
@@ -133,16 +194,16 @@ def main():
     n_total = per_gpu * world
 
     # ---- CPU baseline FIRST (rank 0 of a one-GPU run only): the GPU has not been touched yet, so everything after this leg
-    # is one contiguous window of GPU work for whoever samples the card from outside ------------------------------------
+    # is one contiguous window of GPU work for whoever samples the card from outside (--full only) ----------------------
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(kind, G, a.cpu_sample_members, N_SCEN, numpy_legs=a.numpy_baseline)
 
     # ---- roofline.traffic MEASURED IN THIS RUN (rank 0 of a one-GPU per-step run): two child `rocprofv3 --pmc` passes, FETCH_SIZE and
     # WRITE_SIZE separately, of the same kernel at the same size (tools/pmc_workload.py), each calibrated on a known copy in the
-    # same pass — as child processes BEFORE this process touches the GPU ---------------------------------------------------
+    # same pass — as child processes BEFORE this process touches the GPU (--full only) --------------------------------------
     traffic_live = None
-    if (rank == 0 and world == 1 and not a.no_live_traffic and not a.no_trajectory and (a.mode or "per_step") in ("per_step", "graph")
+    if (a.full and rank == 0 and world == 1 and not a.no_live_traffic and not a.no_trajectory and (a.mode or "per_step") in ("per_step", "graph")
             and "rocprof" not in os.environ.get("LD_PRELOAD", "")):      # (not from inside a profiled process)
         from benchlib.traffic import live_traffic          # (no torch in there: the GPU stays untouched by this process)
         traffic_live = live_traffic(kind, a.dtype, per_gpu)
@@ -206,12 +267,15 @@ def main():
     # ---- warm-up, then EXACTLY K timed steps ------------------------------------------------------
     # The clocked region holds this rank's K steps and nothing else: barrier (all ranks start together), device
     # synchronise, clock, K steps, device synchronise, clock.  No collective sits inside it — at 20 steps the region is
-    # under a millisecond and a barrier would be a tenth of it.  The per-rank times are MAX-reduced afterwards.  The block
-    # is then REPEATED back to back (same K, the scenario index keeps cycling) until --timed-s of device time has been
-    # clocked, and the MEDIAN block is what `value` and `ms_per_step` report: a 20-step call is not one sub-millisecond
-    # sample, and the card is visibly busy for seconds to anything that samples it from outside.  `timed_repeats` says how
-    # many blocks were clocked and `first_block_ms_per_step` keeps the single-sample figure.
-    t_idx = legs.run_steps(eng, 0, a.warmup, a.mode or "per_step", k_steps)
+    # under a millisecond and a barrier would be a tenth of it.  The per-rank times are MAX-reduced afterwards.  A plain run
+    # clocks ONE such block, HIP event to HIP event (`clock_blocks(1)`): `--steps` is the number of timed steps.  With --full
+    # the block is clocked on the wall clock first and then REPEATED back to back (same K, the scenario index keeps cycling)
+    # until --timed-s of device time has been clocked, and the MEDIAN block is what `value` and `ms_per_step` report: a 20-step
+    # call is not one sub-millisecond sample, and the card is visibly busy for seconds to anything that samples it from
+    # outside.  `timed_repeats` says how many blocks were clocked and `first_block_ms_per_step` keeps the single-sample figure.
+    # Every run takes W + K steps: a plain run enqueues the last min(W, 5) warm-up steps right before its block (`lead`).
+    lead = 0 if a.full else min(a.warmup, 5)                     # plain run: the last warm-up steps lead into the block
+    t_idx = legs.run_steps(eng, 0, a.warmup - lead, a.mode or "per_step", k_steps)
 
     fail_rank = os.environ.get("FIVEEQ_BENCH_FAIL_RANK")        # test hook: this rank dies before the timed region
     if fail_rank is not None and int(fail_rank) == rank:
@@ -219,15 +283,16 @@ def main():
 
     # Which launch form the timed region uses.  An explicit --mode is taken as given.  The default is the per-step form at
     # every N (the scaling curve must compare one launch form with itself).  For N > 1 the per-step enqueue share
-    # (legs.host_enqueue: all ranks enqueuing at once) is measured first and reported (`timing.host_fallback`: a host-bound node
-    # must not pass for a slow GPU); with --host-fallback a share at or above --host-share-limit switches the timed region to the
-    # hipGraph replay of the same launches (same kernels, same layout, bit-identical results; 1/4 of the host time).
+    # (legs.host_enqueue: all ranks enqueuing at once) is measured first (--full, or --host-fallback, which acts on it) and
+    # reported (`timing.host_fallback`: a host-bound node must not pass for a slow GPU); with --host-fallback a share at or above
+    # --host-share-limit switches the timed region to the hipGraph replay of the same launches (same kernels, same layout,
+    # bit-identical results; 1/4 of the host time).
     k_burst = max(1, min(a.steps, 40))
     mode_requested = a.mode
     fallback = None
     if a.mode is None:
         a.mode = "per_step"
-        if world > 1 or os.environ.get("FIVEEQ_BENCH_FORCE_HOST_CHECK") == "1":
+        if (a.full or a.host_fallback) and (world > 1 or os.environ.get("FIVEEQ_BENCH_FORCE_HOST_CHECK") == "1"):
             e_med, _, d_med, t_idx, _ = legs.host_enqueue(eng, ctl, "per_step", t_idx, k_burst, k_steps)
             fallback = {"per_step_host_enqueue_us_per_step": e_med * 1e6, "per_step_burst_us_per_step": d_med * 1e6,
                         "per_step_host_share": e_med / d_med, "limit": a.host_share_limit,
@@ -253,83 +318,140 @@ def main():
         torch.cuda.synchronize(dev)
         return t1 - t0, t_next
 
-    first, t_idx = timed_block(t_idx)
-    first_max = ctl.max_over_ranks([first])[0]
-    repeats, blocks, wall_all = 1, [first], None
-    if a.timed_s > 0 and first_max < a.timed_s:
-        # The repeats run BACK TO BACK: one barrier + device sync before the first, then R x K steps enqueued with a HIP
-        # event on the launch stream at every block boundary, one drain at the end.  Block i = event i -> event i+1 on the
-        # device's own clock, so a block holds its K steps and nothing else — no idle-stream launch latency, no host
-        # wake-up — exactly what K steps cost inside a long run.  The wall clock around all R blocks is kept beside it as
-        # the cross-check.  (The host runs ahead of the device until the HIP queue is full and is then paced by it.)
-        # The per-step mode may run each timestep as several kernels on their own streams (engine.per_step_streams): a mark
-        # is then one event PER STREAM, the blocks are not joined in between (a join is two cross-stream hops, ~20 us, that a
-        # continuous run does not have), and a block lasts as long as its slowest stream takes from mark to mark.
-        lanes = eng.per_step_stream_list() if a.mode == "per_step" else [torch.cuda.current_stream(dev)]
+    # Event-timed blocks run BACK TO BACK: one barrier + device sync before the first, then R x K steps enqueued with a HIP
+    # event on the launch stream at every block boundary, one drain at the end.  Block i = event i -> event i+1 on the
+    # device's own clock, so a block holds its K steps and nothing else — no host wake-up — exactly what K steps cost inside a
+    # long run.  The wall clock around all R blocks is kept beside it as the cross-check.  (The host runs ahead of the device
+    # until the HIP queue is full and is then paced by it.)
+    # The per-step mode may run each timestep as several kernels on their own streams (engine.per_step_streams): a mark
+    # is then one event PER STREAM, the blocks are not joined in between (a join is two cross-stream hops, ~20 us, that a
+    # continuous run does not have), and a block lasts as long as its slowest stream takes from mark to mark.
+    lanes = eng.per_step_stream_list() if a.mode == "per_step" else [torch.cuda.current_stream(dev)]
 
-        def mark():
-            evs = [torch.cuda.Event(enable_timing=True) for _ in lanes]
-            for ev, lane in zip(evs, lanes):
-                ev.record(lane)
-            return evs
+    def mark():
+        evs = [torch.cuda.Event(enable_timing=True) for _ in lanes]
+        for ev, lane in zip(evs, lanes):
+            ev.record(lane)
+        return evs
 
-        def clock_blocks(n_blocks, t_from):
-            if a.mode == "graph":
-                legs.prepare_graphs(eng, t_from % N_SCEN, a.steps * min(n_blocks, -(-N_SCEN // a.steps) + 1))
-            torch.cuda.synchronize(dev)
-            ctl.barrier()
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            marks = [mark()]
-            for _ in range(n_blocks):
-                t_from = legs.run_steps(eng, t_from, a.steps, a.mode, k_steps, join=False)
-                marks.append(mark())
-            eng.join()
-            done = torch.cuda.Event()
-            done.record()
-            while not done.query():
-                pass
-            wall = time.perf_counter() - t0
-            torch.cuda.synchronize(dev)
-            out = [max(e0.elapsed_time(e1) for e0, e1 in zip(marks[i], marks[i + 1])) * 1e-3 for i in range(n_blocks)]
-            return out, wall, t_from
+    def clock_blocks(n_blocks, t_from, lead=0):
+        """n_blocks K-step blocks back to back, each HIP event to HIP event; `lead` steps (the tail of the warm-up) are enqueued
+        right before the first mark, so that the first block, too, starts on a busy queue rather than behind its launch latency."""
+        if a.mode == "graph":
+            legs.prepare_graphs(eng, t_from % N_SCEN, lead)
+            legs.prepare_graphs(eng, (t_from + lead) % N_SCEN, a.steps * min(n_blocks, -(-N_SCEN // a.steps) + 1))
+        torch.cuda.synchronize(dev)
+        ctl.barrier()
+        torch.cuda.synchronize(dev)
+        t_from = legs.run_steps(eng, t_from, lead, a.mode, k_steps, join=False)
+        t0 = time.perf_counter()
+        marks = [mark()]
+        for _ in range(n_blocks):
+            t_from = legs.run_steps(eng, t_from, a.steps, a.mode, k_steps, join=False)
+            marks.append(mark())
+        eng.join()
+        done = torch.cuda.Event()
+        done.record()
+        while not done.query():
+            pass
+        wall = time.perf_counter() - t0
+        torch.cuda.synchronize(dev)
+        out = [max(e0.elapsed_time(e1) for e0, e1 in zip(marks[i], marks[i + 1])) * 1e-3 for i in range(n_blocks)]
+        return out, wall, t_from
 
-        # how long IS a block inside a run?  The wall-clocked first block carries the idle-stream launch latency (10 % at 20
-        # steps); a short event-timed burst sizes the main loop so that it clocks --timed-s of device time, not 10 % less
-        # (always: on a box's first process the wall-clocked block has been seen 60x too long — 43 ms for 60 steps of 36 us — and a
-        # main loop sized from it clocked 2 ms where 50 were asked for)
-        probe, _, t_idx = clock_blocks(int(min(11, max(1, a.timed_s // max(first_max, 1e-6)))), t_idx)
-        est = float(np.median(ctl.max_over_ranks(probe)))
-        repeats = int(min(max(a.max_repeats, 1), -(-a.timed_s // max(est, 1e-6)))) | 1     # odd
-        blocks, wall_all, t_idx = clock_blocks(repeats, t_idx)
+    if not a.full:
+        # the plain run: exactly K timed steps, one event-timed block behind the last `lead` warm-up steps
+        blocks, wall_all, t_idx = clock_blocks(1, t_idx, lead)
+        repeats, first_max = 1, None
+    else:
+        first, t_idx = timed_block(t_idx)
+        first_max = ctl.max_over_ranks([first])[0]
+        repeats, blocks, wall_all = 1, [first], None
+        if a.timed_s > 0 and first_max < a.timed_s:
+            # how long IS a block inside a run?  The wall-clocked first block carries the idle-stream launch latency (10 % at 20
+            # steps); a short event-timed burst sizes the main loop so that it clocks --timed-s of device time, not 10 % less
+            # (always: on a box's first process the wall-clocked block has been seen 60x too long — 43 ms for 60 steps of 36 us — and a
+            # main loop sized from it clocked 2 ms where 50 were asked for)
+            probe, _, t_idx = clock_blocks(int(min(11, max(1, a.timed_s // max(first_max, 1e-6)))), t_idx)
+            est = float(np.median(ctl.max_over_ranks(probe)))
+            repeats = int(min(max(a.max_repeats, 1), -(-a.timed_s // max(est, 1e-6)))) | 1     # odd
+            blocks, wall_all, t_idx = clock_blocks(repeats, t_idx)
     per_rank_ms_per_step = ctl.gather_over_ranks(float(np.median(blocks)) / a.steps * 1e3)      # each rank's own median block
     blocks = ctl.max_over_ranks(blocks)                          # per block: the slowest rank
     elapsed = float(np.median(blocks))
     value = n_total * a.steps / elapsed
 
-    enq_med, enq_min, _, t_idx, enq_mine = legs.host_enqueue(eng, ctl, a.mode, t_idx, k_burst, k_steps)
-    timing = {"timed_repeats": repeats,
-              "per_rank_ms_per_step": per_rank_ms_per_step, "per_rank_host_enqueue_us": ctl.gather_over_ranks(enq_mine * 1e6),
-              "per_rank_is": "rank r's own median block / K, and its own median enqueue time per step (list index = rank); "
-                             "`ms_per_step` is the median over blocks of the per-block MAX over ranks",
-              "block_ms_min_median_max": [min(blocks) * 1e3, elapsed * 1e3, max(blocks) * 1e3],
-              "device_s_clocked": float(np.sum(blocks)),
-              "first_block_ms_per_step": first_max / a.steps * 1e3,
-              "first_block_is": "ONE K-step block on the wall clock (barrier, device sync, clock, K steps, drained stream, "
-                                "clock; MAX over ranks): the contract's literal sample",
-              "wall_ms_per_step_over_all_repeats": None if wall_all is None else
-              ctl.max_over_ranks([wall_all])[0] / (a.steps * repeats) * 1e3,
-              "host_enqueue_us_per_step": enq_med * 1e6, "host_enqueue_us_per_step_min": enq_min * 1e6,
-              "host_share": enq_med / (elapsed / a.steps),
-              "host_fallback": fallback,
-              "host_enqueue_is": (f"median (and min) over 15 bursts of {k_burst} steps of the wall time this rank's thread spends "
-                                  "inside engine.run -> fiveeq_run_* (enqueue only, drained device, queue never full), every "
-                                  f"burst behind a barrier so that all {world} rank(s) enqueue at once; MAX over ranks; "
-                                  "host_share = that / ms_per_step"),
-              "clocked": ("one K-step block on the wall clock (it is longer than --timed-s)" if repeats == 1 else
-                          f"{repeats} K-step blocks enqueued back to back after one barrier + device sync; block = HIP event "
-                          "to HIP event on the launch stream (the slowest of the launch streams when a timestep is several "
-                          "concurrent launches); MAX over ranks per block, then the median block")}
+    # ---- --dump-outputs: what the LAST timed step computed, before anything below runs the engine again ------------------
+    dumped = None
+    if a.dump_outputs:
+        dumped = dump_outputs(eng, (t_idx - 1) % N_SCEN, a.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "",
+                              budget=DUMP_BUDGET_BYTES // world)
+
+    if not a.full:
+        timing = {"timed_repeats": 1, "per_rank_ms_per_step": per_rank_ms_per_step,
+                  "per_rank_is": "rank r's own block / K (list index = rank); `ms_per_step` is the block's MAX over ranks / K",
+                  "wall_ms_per_step": ctl.max_over_ranks([wall_all])[0] / a.steps * 1e3,
+                  "host_fallback": fallback,
+                  "clocked": ("ONE K-step block after one barrier + device sync: HIP event to HIP event on the launch stream (the "
+                              "slowest of the launch streams when a timestep is several concurrent launches); MAX over ranks.  "
+                              "--full adds the repeated blocks, the host enqueue time and the legs beside the headline")}
+    else:
+        enq_med, enq_min, _, t_idx, enq_mine = legs.host_enqueue(eng, ctl, a.mode, t_idx, k_burst, k_steps)
+        timing = {"timed_repeats": repeats,
+                  "per_rank_ms_per_step": per_rank_ms_per_step, "per_rank_host_enqueue_us": ctl.gather_over_ranks(enq_mine * 1e6),
+                  "per_rank_is": "rank r's own median block / K, and its own median enqueue time per step (list index = rank); "
+                                 "`ms_per_step` is the median over blocks of the per-block MAX over ranks",
+                  "block_ms_min_median_max": [min(blocks) * 1e3, elapsed * 1e3, max(blocks) * 1e3],
+                  "device_s_clocked": float(np.sum(blocks)),
+                  "first_block_ms_per_step": first_max / a.steps * 1e3,
+                  "first_block_is": "ONE K-step block on the wall clock (barrier, device sync, clock, K steps, drained stream, "
+                                    "clock; MAX over ranks): the contract's literal sample",
+                  "wall_ms_per_step_over_all_repeats": None if wall_all is None else
+                  ctl.max_over_ranks([wall_all])[0] / (a.steps * repeats) * 1e3,
+                  "host_enqueue_us_per_step": enq_med * 1e6, "host_enqueue_us_per_step_min": enq_min * 1e6,
+                  "host_share": enq_med / (elapsed / a.steps),
+                  "host_fallback": fallback,
+                  "host_enqueue_is": (f"median (and min) over 15 bursts of {k_burst} steps of the wall time this rank's thread spends "
+                                      "inside engine.run -> fiveeq_run_* (enqueue only, drained device, queue never full), every "
+                                      f"burst behind a barrier so that all {world} rank(s) enqueue at once; MAX over ranks; "
+                                      "host_share = that / ms_per_step"),
+                  "clocked": ("one K-step block on the wall clock (it is longer than --timed-s)" if repeats == 1 else
+                              f"{repeats} K-step blocks enqueued back to back after one barrier + device sync; block = HIP event "
+                              "to HIP event on the launch stream (the slowest of the launch streams when a timestep is several "
+                              "concurrent launches); MAX over ranks per block, then the median block")}
+    mode_run = eng.resolve_mode(a.mode, k_steps)[0]              # what --mode auto resolves to on this ensemble
+    out = {
+        "metric": "ensemble_member_timesteps_per_sec", "value": value, "unit": "member-timesteps/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
+        "timed_repeats": repeats, "timing": timing,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
+        "data": "synthetic",
+        "config": {"workload": f"{a.workload}: {desc}", "members_per_gpu": per_gpu, "members_total": n_total,
+                   "gases": G, "pools": eng.pools, "scenario_steps": N_SCEN, "mode": a.mode, "mode_resolved": mode_run,
+                   "mode_requested": mode_requested or "default",
+                   "steps_per_launch": None,                    # (--full: from the roofline of the timed kernel, below)
+                   "trajectory_stored": eng.C is not None, "compensated_fp32": bool(a.compensated), "parallelism": f"member-shard x{world}",
+                   "chunk_members": eng.chunk_members,
+                   "collective_backend": "rccl" if backend == "nccl" else backend,
+                   "control_plane": None if dist is None else "gloo over 127.0.0.1 (barriers, MAX of the clocked times)",
+                   "emissions_sha256": emissions.emissions_sha256(E)[:16], "lhs_seed": params.LHS_SEED,
+                   "lhs_design": "shard-computable (keyed Feistel bijection), drawn on the device",
+                   "setup_s_rank0": setup_s,
+                   "devices": devices},
+    }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    if not a.full:
+        # ---- the plain run ends here: the line, and the control plane taken down -----------------------------------------
+        del out["config"]["steps_per_launch"]
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ==== --full from here on ===========================================================================================
     # ---- the rows the end-of-run exchange will summarise: taken NOW, from ONE uninterrupted run (the repeated blocks
     # cycled through the scenario and overwrote stored rows with later passes; the roofline batches below overwrite more) ---
     # The WHOLE 750-step scenario, whatever K: the exchange then summarises the years 2014 / 2264 / 2514 of the run, not a
@@ -343,7 +465,6 @@ def main():
         rows = eng.T[years]                                     # advanced indexing: a copy
 
     # ---- roofline of the timed mode's kernel and the legs beside it (benchlib/legs.py; none of it inside a clocked region) ----
-    mode_run = eng.resolve_mode(a.mode, k_steps)[0]              # what --mode auto resolves to on this ensemble
     fusedlike = mode_run in ("fused", "ksteps", "small")
     _, _, _, members_per_wave, _, packed = legs.kernel_tags(eng, a, n_local)
     if not fusedlike:
@@ -361,26 +482,8 @@ def main():
     if not fusedlike and world == 1 and not a.no_hbm_resident and a.hbm_resident_members > 0:
         legs.hbm_resident(eng, a, p, G, dtype, dev, n_local, best_copy_gbs, roofline)
 
-    out = {
-        "metric": "ensemble_member_timesteps_per_sec", "value": value, "unit": "member-timesteps/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
-        "timed_repeats": repeats, "timing": timing,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
-        "data": "synthetic",
-        "config": {"workload": f"{a.workload}: {desc}", "members_per_gpu": per_gpu, "members_total": n_total,
-                   "gases": G, "pools": eng.pools, "scenario_steps": N_SCEN, "mode": a.mode, "mode_resolved": mode_run,
-                   "mode_requested": mode_requested or "default",
-                   "steps_per_launch": (roofline.get("steps_per_launch", 1)),
-                   "trajectory_stored": eng.C is not None, "compensated_fp32": bool(a.compensated), "parallelism": f"member-shard x{world}",
-                   "chunk_members": eng.chunk_members,
-                   "collective_backend": "rccl" if backend == "nccl" else backend,
-                   "control_plane": None if dist is None else "gloo over 127.0.0.1 (barriers, MAX of the clocked times)",
-                   "emissions_sha256": emissions.emissions_sha256(E)[:16], "lhs_seed": params.LHS_SEED,
-                   "lhs_design": "shard-computable (keyed Feistel bijection), drawn on the device",
-                   "setup_s_rank0": setup_s,
-                   "devices": devices},
-        "roofline": legs.ordered(roofline),
-    }
+    out["config"]["steps_per_launch"] = roofline.get("steps_per_launch", 1)
+    out["roofline"] = legs.ordered(roofline)
     if cpu is not None:
         out["cpu_baseline"] = cpu
 

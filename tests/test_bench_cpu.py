@@ -53,3 +53,38 @@ def test_roofline_regime_labels_and_key_order():
                       "peak": 8000.0, "achieved": 7200.0, "bound": "hbm", "single_launch_frac": 0.85, "zzz": 0})
     assert list(r)[:9] == ["bound", "achieved", "peak", "unit", "frac", "regime", "traffic", "hbm_resident_frac", "single_launch_frac"]
     assert list(r)[-2:] == ["note", "zzz"] and len(r) == 12
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget():
+    """--dump-outputs writes every member while the arrays fit the budget, else the largest fixed, seeded sample of member
+    columns that does: the same indices in every run, so two builds are compared on the same members."""
+    sys.path.insert(0, ROOT)
+    import importlib
+
+    import numpy as np
+    bench = importlib.import_module("bench")
+    assert bench.DUMP_BUDGET_BYTES <= 64_000_000
+    assert bench.dump_members(10_000, 96) is None and bench.dump_members(666_000, 96) is None
+    idx = bench.dump_members(1_000_000, 96)
+    assert idx.size == bench.DUMP_BUDGET_BYTES // 96 and idx.size * 96 <= bench.DUMP_BUDGET_BYTES
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 1_000_000
+    assert np.array_equal(idx, bench.dump_members(1_000_000, 96))
+    small = bench.dump_members(100_000_000, 48, budget=1_000_000)
+    assert small.size == 1_000_000 // 48 and np.all(np.diff(small) > 0) and small[-1] < 100_000_000
+
+
+def test_plain_and_full_options():
+    """The plain call runs without --full and without --dump-outputs; both are options of their own."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"]
+        a = bench.parse()
+        assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out_dir"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "out_dir"
+    finally:
+        sys.argv = argv

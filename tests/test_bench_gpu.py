@@ -11,12 +11,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*args, timed_s="0.05", live_traffic=False):
-    """One plain `python bench.py ...` call.  --timed-s: these tests check the line, not the figure, so they clock 50 ms of
-    device time instead of the default 6.5 s (the driver-call test below keeps the default); the two rocprofv3 --pmc child passes
-    that measure roofline.traffic (25 s) run in the contract test only."""
+    """One plain `python bench.py --full ...` call (the legs beside the headline run with --full only).  --timed-s: these tests
+    check the line, not the figure, so they clock 50 ms of device time instead of the default 6.5 s (the driver-call test below
+    keeps the default); the two rocprofv3 --pmc child passes that measure roofline.traffic (25 s) run in the contract test only."""
     extra = [] if timed_s is None or "--timed-s" in args else ["--timed-s", timed_s]
     extra += [] if live_traffic or "--no-live-traffic" in args else ["--no-live-traffic"]
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, *extra], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *args, *extra], capture_output=True, text=True,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -114,7 +114,7 @@ def _torchrun(n, *args, env=None, timeout=900):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), *args]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full", *args]
     full_env = dict(os.environ, **_RANK_ENV)
     full_env.update(env or {})
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=full_env)
@@ -126,7 +126,7 @@ def _plain(n, *args, env=None, timeout=900):
     full_env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     full_env.update(_RANK_ENV)
     full_env.update(env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *args], capture_output=True,
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full", *args], capture_output=True,
                           text=True, timeout=timeout, env=full_env)
 
 
@@ -296,7 +296,7 @@ def test_one_rank_job_runs_every_collective_over_rccl():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         env["MASTER_PORT"] = str(s.getsockname()[1])
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *_SMALL], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *_SMALL], capture_output=True, text=True,
                          timeout=600, env=env)
     d = _one_line(out)
     plain = _bench(*_SMALL)
@@ -318,3 +318,65 @@ def test_a_twenty_step_call_reports_what_a_full_pass_reports():
     assert short["timed_repeats"] > 1000 and short["timing"]["device_s_clocked"] > 6.0 and full["timed_repeats"] == 1
     print(f"20-step median {short['value']:.4g} vs 740-step {full['value']:.4g}: ratio {short['value'] / full['value']:.4f}")
     assert abs(short["value"] / full["value"] - 1.0) < 0.05
+
+
+# ---- the plain run (no --full): set-up, warm-up, EXACTLY --steps timed steps, the line; --dump-outputs ----
+def _lean(*args, timeout=600):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=timeout)
+    return _one_line(out)
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain call clocks ONE block of exactly --steps steps and runs none of the legs beside the headline; --dump-outputs
+    writes what the last timed step computed — the rows it stored and the state it left — equal to the CPU oracle over the same
+    W + K steps of the same members, and bit for bit the same in a second run with the same arguments."""
+    import numpy as np
+
+    from fiveeqscm_amd import emissions, params
+    from oracle import fiveeq_oracle as npo
+    n, k, w = 20000, 30, 5
+    runs = []
+    for name in ("a", "b"):
+        d = _lean("--steps", str(k), "--warmup", str(w), "--members", str(n), "--dump-outputs", str(tmp_path / name))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["metric"] == "ensemble_member_timesteps_per_sec" and d["unit"] == "member-timesteps/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == k and d["warmup"] == w
+        assert d["timed_repeats"] == 1 and d["timing"]["timed_repeats"] == 1
+        assert abs(d["value"] - n * k / (d["ms_per_step"] * k * 1e-3)) < 1e-6 * d["value"]
+        assert d["timing"]["wall_ms_per_step"] >= d["ms_per_step"] * 0.9
+        for leg in ("roofline", "cpu_baseline", "summary"):
+            assert leg not in d, leg
+        du = d["dump_outputs"]
+        assert du["step"] == w + k - 1 and du["members"] == n and du["member_sample"] is None and du["dtype"] == "float64"
+        got = {x: np.load(tmp_path / name / f"{x}.npy") for x in ("C", "T", "R", "S")}
+        assert sorted(os.listdir(tmp_path / name)) == ["C.npy", "R.npy", "S.npy", "T.npy"]
+        assert got["C"].shape == (3, n) and got["T"].shape == (n,) and got["R"].shape == (6, n) and got["S"].shape == (2, n)
+        assert all(v.dtype == np.float64 for v in got.values())
+        runs.append(got)
+    for x in ("C", "T", "R", "S"):
+        assert np.array_equal(runs[0][x], runs[1][x]), x
+    p = params.sample_ensemble_shard(params.default_params("multigas"), n, 0, n)
+    want = npo.run(emissions.rcp_like_emissions(750, 3)[:w + k], p, n)
+    ref = {"C": want["C"][-1], "T": want["T"][-1], "R": np.concatenate(want["R"], axis=0), "S": want["S"]}
+    for x, atol in (("C", 1e-13), ("T", 1e-13), ("R", 1e-12), ("S", 1e-13)):
+        err = np.abs(runs[0][x] - ref[x]) / (1e-10 * np.abs(ref[x]) + atol)
+        assert err.max() <= 1.0, (x, float(err.max()))
+
+
+def test_dump_outputs_of_the_default_workload_stay_within_64_mb(tmp_path):
+    """1M members x (3 C + 1 T + 6 R + 2 S) fp64 values do not fit 64 MB: a fixed, seeded sample of member columns, the same
+    members in every array and in every run."""
+    import numpy as np
+    d = _lean("--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path))
+    du = d["dump_outputs"]
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["C.npy", "R.npy", "S.npy", "T.npy"] and du["member_sample"] and du["members"] < 1_000_000
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64_000_000
+    sys.path.insert(0, ROOT)
+    import bench
+    idx = bench.dump_members(1_000_000, 96, bench.DUMP_BUDGET_BYTES - 256 * 4)
+    assert idx is not None and idx.size == du["members"]
+    for f in files:
+        x = np.load(tmp_path / f)
+        assert x.shape[-1] == du["members"] and np.isfinite(x).all()

@@ -13,10 +13,10 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$QUICK" != "rest" ] && [ "$QUICK" != "sweeps" ]; then
 echo "== bench (default workload) =="
-python3 $R/bench.py > $OUT/bench_config3.json 2> $OUT/bench_config3.err || echo "bench failed"
-python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_config3_driver_call_20_steps.json 2>/dev/null || echo "bench (20 steps) failed"
+python3 $R/bench.py --full > $OUT/bench_config3.json 2> $OUT/bench_config3.err || echo "bench failed"
+python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_config3_driver_call_20_steps.json 2>/dev/null || echo "bench (20 steps) failed"
 echo "== bench under rocprofv3 --kernel-trace --stats =="
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --no-cpu-baseline --no-hbm-resident --no-live-traffic \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-hbm-resident --no-live-traffic \
     > $OUT/bench_config3_under_rocprof.json 2> $OUT/trace.err || echo "trace failed"
 echo "== PMC passes: HBM traffic (FETCH_SIZE, WRITE_SIZE separately) =="
 for N in 1000000 8000000; do
@@ -54,7 +54,7 @@ timeout -k 10 400 rocprofv3 --pmc $SQB --kernel-trace --output-format csv -d $OU
 python3 $R/tools/pmc_valu.py $OUT/sq_counters_small_co2_f64_10k.csv $OUT/valu.json 750 $OUT/pmc_sqa_small $OUT/pmc_sqb_small > /dev/null
 timeout -k 10 400 rocprofv3 --pmc $SQA --kernel-trace --output-format csv -d $OUT/pmc_sqa_small3 -- python3 $R/tools/pmc_workload_fused.py 10000 f64 750 multigas small > $OUT/pmc_sqa_small3.log 2>&1
 python3 $R/tools/pmc_valu.py $OUT/sq_counters_small_multigas_f64_10k.csv $OUT/valu.json 750 $OUT/pmc_sqa_small3 > /dev/null
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_config2 -- python3 $R/bench.py --workload config2 --mode auto --no-cpu-baseline \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_config2 -- python3 $R/bench.py --full --workload config2 --mode auto --no-cpu-baseline \
     > $OUT/bench_config2_auto_under_rocprof.json 2> $OUT/trace_config2.err || echo "config2 trace failed"
 echo "== the streamed histogram pipeline under --kernel-trace --stats; LDS conflicts of the histogram kernels; fused traffic =="
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_config5_demo -- python3 $R/tools/config5_demo.py > $OUT/trace_config5_demo.log 2>&1
@@ -80,18 +80,18 @@ fi
 if [ "$QUICK" != "quick" ]; then
 if [ "$QUICK" != "sweeps" ]; then          # (sweeps = the tables only: tools/collect_final_bench_lines.sh regenerates every bench line)
 echo "== other bench lines =="
-python3 $R/bench.py --no-cpu-baseline --mode fused > $OUT/bench_config3_fused.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --mode graph > $OUT/bench_config3_graph.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config2 > $OUT/bench_config2_per_step.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config2 --mode graph > $OUT/bench_config2_graph.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config2 --mode auto > $OUT/bench_config2_auto.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config2 --mode ksteps > $OUT/bench_config2_ksteps.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config2 --mode fused > $OUT/bench_config2_fused.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config4 > $OUT/bench_config4_per_gpu_shard.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config5 --dtype f32 --steps 300 > $OUT/bench_config5_f32_per_gpu_shard.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --dtype f32 > $OUT/bench_config3_f32.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --dtype f32 --mode fused > $OUT/bench_config3_f32_fused.json 2>/dev/null
-python3 $R/bench.py --no-cpu-baseline --workload config5 --dtype f32 --mode fused --no-trajectory > $OUT/bench_config5_f32_fused_no_trajectory.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --mode fused > $OUT/bench_config3_fused.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --mode graph > $OUT/bench_config3_graph.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config2 > $OUT/bench_config2_per_step.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config2 --mode graph > $OUT/bench_config2_graph.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config2 --mode auto > $OUT/bench_config2_auto.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config2 --mode ksteps > $OUT/bench_config2_ksteps.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config2 --mode fused > $OUT/bench_config2_fused.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config4 > $OUT/bench_config4_per_gpu_shard.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config5 --dtype f32 --steps 300 > $OUT/bench_config5_f32_per_gpu_shard.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --dtype f32 > $OUT/bench_config3_f32.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --dtype f32 --mode fused > $OUT/bench_config3_f32_fused.json 2>/dev/null
+python3 $R/bench.py --full --no-cpu-baseline --workload config5 --dtype f32 --mode fused --no-trajectory > $OUT/bench_config5_f32_fused_no_trajectory.json 2>/dev/null
 fi
 echo "== sweeps =="
 python3 $R/tools/sweep.py --members 100000,250000,500000,1000000,2000000,4000000 --modes per_step,fused 2>&1 | grep -v amdgpu.ids > $OUT/sweep_members.txt
