@@ -26,6 +26,9 @@ class CheckpointMixin:
         out = {"R": self.R.double().cpu().numpy(), "S": self.S.double().cpu().numpy(), "t_next": int(self.t_next)}
         if self.cumE is not None:
             out["cumE"] = self.cumE.double().cpu().numpy()
+        if self.misfit is not None:                              # the misfit accumulators are state: always carried
+            out["misfit"] = self.misfit.cpu().numpy()
+            out["obs_sha256"] = self.observations.sha256
         if include_outputs:
             if self.T_hist is not None:
                 out["T_hist"] = self.T_hist.cpu().numpy()
@@ -53,7 +56,10 @@ class CheckpointMixin:
         cleared, because they describe a run this state is not from."""
         # VALIDATE everything first, then mutate: a checkpoint whose n_steps / n_bins / n_rows do not match raises with the
         # engine exactly as it was (round 5 copied R, S and reset the masks before it looked at the accumulators' shapes)
-        state_names = ("R", "S") + (("cumE",) if self.cumE is not None else ())
+        state_names = ("R", "S") + (("cumE",) if self.cumE is not None else ()) + (("misfit",) if self.misfit is not None else ())
+        mine = None if self.observations is None else self.observations.sha256
+        if state.get("obs_sha256") != mine:
+            raise ValueError(f"checkpoint observation table {state.get('obs_sha256')!r} is not this engine's ({mine!r})")
         if "T_stats" in state and self.collect_stats:
             self._wave_stats()                                   # the checkpoint carries wave records: make room for them (no state touched)
         staged = {}

@@ -204,29 +204,53 @@ struct LaneOf<float> {
     }
 };
 
-template <typename T, bool BINS = false>
-int launch_step(const RunArgs<T>& a, int t, hipStream_t st, const BinRing& br = BinRing()) {
+// the misfit accumulators of the constrained forms (step_kernel / fused_kernel <..., MISFIT = true>): obs [n_steps][4] and
+// misfit [3][ld], fp64 both
+struct MisfitRows {
+    const double* obs = nullptr;
+    double* misfit = nullptr;
+};
+// the layouts with MISFIT instantiations: a lone 4-pool gas (CO2-only) and 4 + 1 + 1 (CO2, CH4, N2O)
+constexpr bool misfit_layout(int p0, int p1, int p2) { return (p0 == 4 && p1 == 0 && p2 == 0) || (p0 == 4 && p1 == 1 && p2 == 1); }
+// ... and the PACKED fp32 fused kernel carries it for 4 + 1 + 1 only.  For {4} the two members' accumulators (12 KiB of LDS per
+// workgroup on top of 20 KiB) would cost the packed form two waves per SIMD (6 -> 4); those runs take the one-member-per-lane
+// fp32 fused kernel, which keeps its plain counterpart's 7 waves (same bits either way: packed lanes mirror the scalar ones).
+constexpr bool misfit_packed_fused(int p0, int p1, int p2) { return p0 == 4 && p1 == 1 && p2 == 1; }
+
+template <typename T, bool BINS = false, bool MISFIT = false>
+int launch_step(const RunArgs<T>& a, int t, hipStream_t st, const BinRing& br = BinRing(), const MisfitRows& mf = MisfitRows()) {
     using P = typename LaneOf<T>::Packed;
+    static_assert(!(BINS && MISFIT), "no misfit in the histogram-ring form");
     const bool packed = LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)br.ring) & 3) == 0);
     const int64_t per_block = (int64_t)FIVEEQ_STEP_BLOCK * (packed ? 2 : 1);
     const int64_t blocks = (a.n + per_block - 1) / per_block;
     if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
     const dim3 grid((unsigned)blocks), block(FIVEEQ_STEP_BLOCK);
     switch (a.code) {
-#define FIVEEQ_STEP_LAUNCH(V, p0, p1, p2, NT)                                                                                  \
-    hipLaunchKernelGGL((step_kernel<V, p0, p1, p2, BINS, NT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, a.r, \
-                       a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w, br.n_bins)
+#define FIVEEQ_STEP_LAUNCH(V, p0, p1, p2, NT, MF)                                                                              \
+    hipLaunchKernelGGL((step_kernel<V, p0, p1, p2, BINS, NT, MF>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, \
+                       a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w,     \
+                       br.n_bins, mf.obs, mf.misfit)
 #define X(p0, p1, p2)                                                                             \
     case (p0) * 100 + (p1) * 10 + (p2):                                                           \
+        if constexpr (MISFIT) {           /* default row policy only (the engine schedules such runs chunk-major) */ \
+            if constexpr (misfit_layout(p0, p1, p2)) {                                            \
+                if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, false, true);                       \
+                else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, false, true);                              \
+                break;                                                                            \
+            } else {                                                                              \
+                return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);     \
+            }                                                                                     \
+        }                                                                                         \
         if constexpr (!BINS) {            /* the streamed row form: plain per-step launches only */ \
             if (a.stream_rows) {                                                                  \
-                if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, true);                              \
-                else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, true);                                     \
+                if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, true, false);                       \
+                else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, true, false);                              \
                 break;                                                                            \
             }                                                                                     \
         }                                                                                         \
-        if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, false);                                     \
-        else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, false);                                            \
+        if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, false, false);                              \
+        else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, false, false);                                     \
         break;
         FIVEEQ_LAYOUTS(X)
 #undef X
@@ -238,29 +262,38 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st, const BinRing& br = 
     return FIVEEQ_OK;
 }
 
-template <typename T, bool INV, bool BINS = false, bool COMP = false>
-int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, T* cumE, hipStream_t st, const BinRing& br = BinRing()) {
+template <typename T, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false>
+int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, T* cumE, hipStream_t st, const BinRing& br = BinRing(),
+                 const MisfitRows& mf = MisfitRows()) {
     using P = typename LaneOf<T>::Packed;
+    static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
     constexpr bool HAS_PACKED = !INV && !std::is_same<P, T>::value;     // the inverse form has no packed instantiation
-    // packed lanes store two 2-byte bin indices as one 4-byte word: the ring rows must be 4-byte aligned too
-    const bool packed = HAS_PACKED && LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)br.ring) & 3) == 0);
+    // packed lanes store two 2-byte bin indices as one 4-byte word: the ring rows must be 4-byte aligned too; the misfit forms
+    // have a packed instantiation for some layouts only (misfit_packed_fused) — decided HERE, before the grid is sized for it
+    const bool packed = HAS_PACKED && (!MISFIT || misfit_packed_fused(a.code / 100, a.code / 10 % 10, a.code % 10)) &&
+                        LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)br.ring) & 3) == 0);
     const int64_t blocks = member_blocks(packed ? (a.n + 1) / 2 : a.n);
     if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
     const dim3 grid((unsigned)blocks), block(FIVEEQ_BLOCK);
     switch (a.code) {
 #define X(p0, p1, p2)                                                                                  \
     case (p0) * 100 + (p1) * 10 + (p2):                                                                \
-        if constexpr (HAS_PACKED) {                                                                    \
+        if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                          \
+            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);              \
+        } else {                                                                                       \
+        if constexpr (HAS_PACKED && (!MISFIT || misfit_packed_fused(p0, p1, p2))) {                    \
             if (packed) {                                                                              \
-                hipLaunchKernelGGL((fused_kernel<P, p0, p1, p2, false, BINS, COMP>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km,  \
-                                   a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, cumE, a.C_traj,        \
-                                   a.T_traj, a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w, br.n_bins);         \
+                hipLaunchKernelGGL((fused_kernel<P, p0, p1, p2, false, BINS, COMP, MISFIT>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, \
+                                   a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, cumE, a.C_traj,  \
+                                   a.T_traj, a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w, br.n_bins, mf.obs,  \
+                                   mf.misfit);                                                         \
                 break;                                                                                 \
             }                                                                                          \
         }                                                                                              \
-        hipLaunchKernelGGL((fused_kernel<T, p0, p1, p2, INV, BINS, COMP>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km, a.drive,   \
-                           a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, cumE, a.C_traj, a.T_traj, a.n_rows,    \
-                           a.stats, br.ring, br.ring_rows, br.lo, br.inv_w, br.n_bins);                \
+        hipLaunchKernelGGL((fused_kernel<T, p0, p1, p2, INV, BINS, COMP, MISFIT>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km,   \
+                           a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, cumE, a.C_traj, a.T_traj,     \
+                           a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w, br.n_bins, mf.obs, mf.misfit);    \
+        }                                                                                              \
         break;
         FIVEEQ_LAYOUTS(X)
 #undef X
@@ -486,6 +519,47 @@ int run_small_comp(const fiveeq_model* m, int64_t n, int64_t ld, const float* dr
     return FIVEEQ_OK;
 }
 
+// ---- the constrained forms: the misfit accumulators carried through a per-step or a (K-step) fused run -------------------
+int misfit_check(const double* obs, double* misfit) {
+    if (!obs || !misfit) return fail(FIVEEQ_E_INVALID, "NULL misfit pointer (obs=%p misfit=%p)", (const void*)obs, (void*)misfit);
+    if ((((uintptr_t)obs) | ((uintptr_t)misfit)) & 7) return fail(FIVEEQ_E_INVALID, "obs and misfit must be 8-byte aligned");
+    return FIVEEQ_OK;
+}
+int misfit_layout_check(int code) {
+    if (!misfit_layout(code / 100, code / 10 % 10, code % 10))
+        return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form (pools {4} and 4+1+1 have)", code);
+    return FIVEEQ_OK;
+}
+
+template <typename T>
+int run_obs(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+            const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, const double* obs,
+            double* misfit, int32_t form, int32_t k_steps, void* stream) {
+    RunArgs<T> a;
+    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    if (int rc = misfit_check(obs, misfit)) return rc;
+    if (form != FIVEEQ_FORM_PER_STEP && form != FIVEEQ_FORM_FUSED)
+        return fail(FIVEEQ_E_INVALID, "form=%d: FIVEEQ_FORM_PER_STEP (0) or FIVEEQ_FORM_FUSED (1)", form);
+    if (int rc = misfit_layout_check(a.code)) return rc;
+    if (k_steps < 0) return fail(FIVEEQ_E_INVALID, "k_steps=%d must be >= 0", k_steps);
+    if (t_begin == t_end) return FIVEEQ_OK;
+    MisfitRows mf;
+    mf.obs = obs;
+    mf.misfit = misfit;
+    hipStream_t st = (hipStream_t)stream;
+    if (form == FIVEEQ_FORM_PER_STEP) {
+        for (int t = t_begin; t < t_end; ++t)
+            if (int rc = launch_step<T, false, true>(a, t, st, BinRing(), mf)) return rc;
+        return FIVEEQ_OK;
+    }
+    if (k_steps == 0 || k_steps > t_end - t_begin) k_steps = t_end - t_begin;
+    for (int t = t_begin; t < t_end; t += k_steps)
+        if (int rc = launch_fused<T, false, false, false, true>(a, t, t + k_steps < t_end ? t + k_steps : t_end, nullptr, st,
+                                                               BinRing(), mf))
+            return rc;
+    return FIVEEQ_OK;
+}
+
 // ---- plans: the per-step launch sequence captured into a hipGraph --------------------------
 struct Plan {
     uint32_t magic;
@@ -496,11 +570,16 @@ constexpr uint32_t PLAN_MAGIC = 0x35455146u;  // "FQE5"
 
 template <typename T>
 int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-                int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void** plan_out) {
+                int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void** plan_out,
+                const MisfitRows* mf = nullptr) {
     if (!plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
     *plan_out = nullptr;
     RunArgs<T> a;
     if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    if (mf) {
+        if (int rc = misfit_check(mf->obs, mf->misfit)) return rc;
+        if (int rc = misfit_layout_check(a.code)) return rc;
+    }
     if (t_begin == t_end) return fail(FIVEEQ_E_INVALID, "empty step range for a plan");
     hipStream_t cap = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
@@ -511,7 +590,8 @@ int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
         return fail(FIVEEQ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(e));
     }
     int rc = FIVEEQ_OK;
-    for (int t = t_begin; t < t_end && rc == FIVEEQ_OK; ++t) rc = launch_step(a, t, cap);
+    for (int t = t_begin; t < t_end && rc == FIVEEQ_OK; ++t)
+        rc = mf ? launch_step<T, false, true>(a, t, cap, BinRing(), *mf) : launch_step(a, t, cap);
     e = hipStreamEndCapture(cap, &graph);
     (void)hipStreamDestroy(cap);
     if (rc != FIVEEQ_OK) {
@@ -715,6 +795,47 @@ int fiveeq_run_small_comp_f32(const fiveeq_model* model, int64_t n_members, int6
                               float* T_traj, int32_t n_rows, double* T_stats, void* stream) {
     return run_small_comp(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats, stream);
 }
+int fiveeq_run_obs_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                       int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
+                       double* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit, int32_t form,
+                       int32_t k_steps, void* stream) {
+    return run_obs<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats, obs,
+                           misfit, form, k_steps, stream);
+}
+int fiveeq_run_obs_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                       int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
+                       float* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit, int32_t form,
+                       int32_t k_steps, void* stream) {
+    return run_obs<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats, obs,
+                          misfit, form, k_steps, stream);
+}
+int fiveeq_plan_create_obs_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                               int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
+                               double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit,
+                               void** plan_out) {
+    MisfitRows mf;
+    mf.obs = obs;
+    mf.misfit = misfit;
+    return plan_create<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                               plan_out, &mf);
+}
+int fiveeq_plan_create_obs_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                               int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
+                               float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit,
+                               void** plan_out) {
+    MisfitRows mf;
+    mf.obs = obs;
+    mf.misfit = misfit;
+    return plan_create<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                              plan_out, &mf);
+}
+int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t* n_pools) {
+    if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;
+    int p[3] = {0, 0, 0};
+    for (int g = 0; g < n_gas; ++g) p[g] = n_pools[g];
+    return misfit_layout(p[0], p[1], p[2]) ? 1 : 0;
+}
+
 int32_t fiveeq_small_lanes(int32_t n_gas, const int32_t* n_pools) {
     if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;
     int p[3] = {0, 0, 0};

@@ -484,6 +484,27 @@ __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& k
     member_step<V, L, false>(km, drv, rr, qq, R, S, C, Tnew, unused);
 }
 
+// ---------------------------------------------------------------------------------
+// THE MISFIT UPDATE (round 7, ABI v12): one member's running misfit against an observed series, three fp64 accumulators
+// A, U, V per member.  obs [n_steps][4] fp64 holds per step (o_t, p_t = 1/sigma_t^2 or 0, b_t = 1/n_ref inside the
+// reference period or 0, 0); Tw is the member's T after the step, widened exactly.  Every operation is rounded on its
+// own (contraction is off in this file, no fma is written): every kernel that carries the accumulators calls this one
+// function, so every form gives the same bits.  A step with p_t == 0 && b_t == 0 is skipped by the caller (the rows are
+// not touched), in every form alike.  The host then scores chi2 = V - 2 A U + A^2 P, P = sum_t p_t.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ void misfit_update(const double o, const double p, const double b, const double Tw, double& A,
+                                              double& U, double& Vq) {
+    A = A + b * Tw;
+    const double d = Tw - o;
+    const double pd = p * d;
+    U = U + pd;
+    Vq = Vq + pd * d;
+}
+// the lane's members: one (scalar lanes) or two (packed lanes); Tw of member j of the lane
+__device__ __forceinline__ double lane_member(const double v, int) { return v; }
+__device__ __forceinline__ double lane_member(const float v, int) { return (double)v; }
+__device__ __forceinline__ double lane_member(const float2v v, int j) { return (double)(j == 0 ? v.x : v.y); }
+
 // The shared model is the FIRST kernel argument (by value): its bytes sit at offset 0 of the
 // kernarg segment.  With ~45 fp64 constants per 3-gas layout plus the polynomial literals it does
 // not fit the 102-SGPR budget (118 SGPR spills -> v_readlane/v_writelane in the VALU stream), so
@@ -840,7 +861,11 @@ __device__ __forceinline__ unsigned int hist_bin2(const HistRule<float> r, const
 #else
 #define FIVEEQ_STEP_ATTR
 #endif
-template <typename V, int P0, int P1, int P2, bool BINS = false, bool NT = false>
+// MISFIT = true (round 7): the step also carries the member's misfit accumulators misfit [3][ld] fp64 (misfit_update()).  The
+// step's obs record is wave-uniform and read with scalar loads; on a step outside the window (p_t == 0 && b_t == 0) the
+// rows are neither read nor written, so such a step moves the bytes of the plain kernel.  Inside it: 24 B read + 24 B
+// written per member-step.  Instantiated for the {4} and 4 + 1 + 1 layouts, default row policy only.
+template <typename V, int P0, int P1, int P2, bool BINS = false, bool NT = false, bool MISFIT = false>
 __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kernel(
     const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
     const int64_t n, const int64_t ld,
@@ -850,7 +875,8 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
     typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
     const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
     unsigned short* __restrict__ bin_ring /* BINS: [ring_rows][ld], row t mod ring_rows */, const int ring_rows,
-    const double hist_lo, const double hist_inv_w, const int n_bins) {
+    const double hist_lo, const double hist_inv_w, const int n_bins,
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */) {
     using L = Layout<P0, P1, P2>;
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
@@ -905,6 +931,22 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
             }
             if (T_traj != nullptr) store_row<NTT>(T_traj + (int64_t)row * ld + m, Tn, full);
         }
+        if constexpr (MISFIT) {
+            const double o_t = obs[(int64_t)t * 4], p_t = obs[(int64_t)t * 4 + 1], b_t = obs[(int64_t)t * 4 + 2];   // scalar loads
+            if (p_t != 0.0 || b_t != 0.0) {
+#pragma unroll
+                for (int j = 0; j < W; ++j) {
+                    if (j == 0 || full) {
+                        double* mf = misfit + m + j;
+                        double A = mf[0], U = mf[ld], Vq = mf[2 * ld];
+                        misfit_update(o_t, p_t, b_t, lane_member(Tn, j), A, U, Vq);
+                        mf[0] = A;
+                        mf[ld] = U;
+                        mf[2 * ld] = Vq;
+                    }
+                }
+            }
+        }
         if constexpr (BINS) {                                            // the histogram bin of T, 2 bytes per member
             unsigned short* o = bin_ring + (int64_t)(t % ring_rows) * ld + m;
             const HistRule<T> rule = make_rule(T(0), hist_lo, hist_inv_w, n_bins);
@@ -942,7 +984,19 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
 // INV = true: concentration-driven form.  drive[t][0..2] are target concentrations, cumE [G][ld] is
 // per-member cumulative-emission state (in/out), and C_traj receives the DIAGNOSED EMISSIONS.
 // (112 VGPRs at fp64 4+1+1 = 4 waves/SIMD; launch-bounds hints for 5 or 6 waves spill: -3 % / -16 %.)
-template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false>
+//
+// MISFIT = true (round 7; INV, BINS and COMP false): the member's misfit accumulators (misfit_update()) are loaded from
+// misfit [3][ld] fp64 once at launch start, carried on chip and stored once at the end — 48 B per member and launch.
+// THE CARRIER IS LDS, NOT REGISTERS: three fp64 per member are 6 VGPRs (12 on a packed lane), and in registers they cost the
+// fp64 {4} form a wave per SIMD (93 -> 105 VGPRs: 5 -> 4 waves) and the fp32 {4} form one too (66 -> 74: 7 -> 6).  Each lane
+// keeps its own words in a lane-private LDS slot (acc_s[3 W][FIVEEQ_BLOCK]: consecutive lanes, consecutive 8-byte words,
+// no bank conflicts, no barrier — a wave's LDS operations complete in program order); a window step adds 3 ds_read_b64 +
+// 3 ds_write_b64 per member beside the step's VALU.  The step's obs record is wave-uniform and read with SCALAR loads
+// straight from obs [n_steps][4] (no LDS staging: the 3 KB a chunk of records would take is what keeps the fp64 {4} form at
+// five workgroups per CU, 5 x 31 KB of 160 KB), so the window test is a scalar branch.  Every MISFIT instantiation keeps
+// its plain counterpart's waves per SIMD with no scratch (tools/kernel_isa_stats.py); the packed fp32 form is instantiated
+// for 4 + 1 + 1 only (fiveeq_capi.hip, misfit_packed_fused).
+template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false>
 __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps,
     const int t_begin, const int t_end, const int64_t n, const int64_t ld,
@@ -953,12 +1007,15 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
     const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
     unsigned short* __restrict__ bin_ring /* BINS: [ring_rows][ld] */, const int ring_rows, const double hist_lo,
-    const double hist_inv_w, const int n_bins) {
+    const double hist_inv_w, const int n_bins,
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */) {
     using L = Layout<P0, P1, P2>;
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     static_assert(!(INV && BINS), "no streamed histograms in the concentration-driven form");
+    static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
     __shared__ T drv[FIVEEQ_FUSED_CHUNK * DRIVE_STRIDE];
+    __shared__ double acc_s[MISFIT ? 3 * W * FIVEEQ_BLOCK : 1];       // MISFIT: [3 W][FIVEEQ_BLOCK], lane-private
     __shared__ V stat_tile[FIVEEQ_BLOCK / 64][STAT_STEPS * STAT_ROW];
     __shared__ KModel<T> km_s;
     stage_model(&km_s);
@@ -994,6 +1051,15 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_lane<V>(r + k * ld + mm);
 #pragma unroll
     for (int k = 0; k < 2; ++k) qq[k] = load_lane<V>(q + k * ld + mm);
+    double* const acc = &acc_s[threadIdx.x];             // MISFIT: word k of member j of this lane at acc[(3 j + k) * FIVEEQ_BLOCK]
+    if constexpr (MISFIT) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const int64_t mj = (j == 0 || full) ? mm + j : mm;    // a packed lane's missing second member shadows the first
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc[(3 * j + k) * FIVEEQ_BLOCK] = misfit[k * ld + mj];
+        }
+    }
 
     for (int tc = t_begin; tc < t_end; tc += FIVEEQ_FUSED_CHUNK) {
         const int nt = min(FIVEEQ_FUSED_CHUNK, t_end - tc);
@@ -1004,6 +1070,21 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
         for (int k = 0; k < nt; ++k) {
             const T* d = &drv[k * DRIVE_STRIDE];
             member_step<V, L, INV, COMP>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo);
+            if constexpr (MISFIT) {
+                const double* ob = obs + (int64_t)(tc + k) * 4;                 // wave-uniform: scalar loads, scalar branch
+                const double o_t = ob[0], p_t = ob[1], b_t = ob[2];
+                if (p_t != 0.0 || b_t != 0.0) {
+#pragma unroll
+                    for (int j = 0; j < W; ++j) {
+                        double* a = acc + 3 * j * FIVEEQ_BLOCK;
+                        double A = a[0], U = a[FIVEEQ_BLOCK], Vq = a[2 * FIVEEQ_BLOCK];
+                        misfit_update(o_t, p_t, b_t, lane_member(Tn, j), A, U, Vq);
+                        a[0] = A;
+                        a[FIVEEQ_BLOCK] = U;
+                        a[2 * FIVEEQ_BLOCK] = Vq;
+                    }
+                }
+            }
             // the output row is wave-uniform: read it once into an SGPR so that the row test is a
             // scalar branch and the row offsets are scalar arithmetic, not 64-bit VALU per lane
             const int row = __builtin_amdgcn_readfirstlane((int)d[7]);
@@ -1052,6 +1133,15 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
         if constexpr (INV) {
 #pragma unroll
             for (int g = 0; g < L::G; ++g) cumE[g * ld + m] = cum[g];
+        }
+        if constexpr (MISFIT) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                if (j == 0 || full) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) misfit[k * ld + m + j] = acc[(3 * j + k) * FIVEEQ_BLOCK];
+                }
+            }
         }
     }
 }

@@ -92,7 +92,7 @@ class EnsembleEngine(CheckpointMixin):
                  device=None, store_trajectory=True, output_steps=None, store_concentrations=True,
                  collect_stats=False, hist=None, hist_ring_steps="auto", concentration_driven=False,
                  chunk_members="auto", per_step_streams="auto", fused_span="auto", small_lanes="auto", compensated=False,
-                 R0=None, S0=None, lib_path=None):
+                 R0=None, S0=None, lib_path=None, observations=None):
         """store_trajectory / output_steps: True stores C, T of every step; a list of step indices
         stores only those (rows in increasing step order, see `out_steps`); False stores nothing.
         store_concentrations=False keeps only the T rows (a 100M-member fp32 run then stores 4 B instead
@@ -134,7 +134,12 @@ class EnsembleEngine(CheckpointMixin):
         (fiveeq_run_small_comp_f32), which is what 'auto' takes for a launch-bound ensemble.
         small_lanes: mode='small' (no in-loop histograms): lanes per member, 4 (a lone 4-pool gas: one pool per lane of a
         quad), 8 (the 4 + 1 + 1 layout: one pool per lane of an octet; no collect_stats), 1 (any layout), or "auto" = the widest
-        form the layout has while the ensemble is small enough for it (SMALL_*_MEMBERS_PER_CU), else 1."""
+        form the layout has while the ensemble is small enough for it (SMALL_*_MEMBERS_PER_CU), else 1.
+        observations: a constrain.Observations table over this run's steps.  Every member then carries its misfit
+        accumulators `misfit` [3, N] fp64 (A, U, V: include/fiveeq.h "CONSTRAINED RUNS") through modes 'per_step', 'graph',
+        'fused' and 'ksteps' — the same bits in each, and C, T, R, S exactly as without it; `chi2()` scores the members.
+        Pool layouts {4} and 4 + 1 + 1; not with compensated=True, concentration_driven=True or hist=, and never in mode
+        'small' ('auto' takes 'per_step', 'ksteps' or 'fused' instead)."""
         if dtype not in _DTYPES:
             raise ValueError("dtype must be torch.float64 or torch.float32")
         self.lib = _capi.load(lib_path)    # raises if the HIP library is not built
@@ -222,6 +227,19 @@ class EnsembleEngine(CheckpointMixin):
             # kernel, "same" = behind each chunk on the caller's stream
             self.hist_pass_stream = _env_choice("FIVEEQ_HIST_PASS_STREAM", "side", ("side", "same"))
             self._bins = None            # the bin-index ring, allocated by the first run that fills T_hist
+            self.observations, self.obs, self.misfit = None, None, None
+            if observations is not None:
+                if self.compensated or self.concentration_driven or hist is not None:
+                    raise ValueError("observations= cannot be combined with compensated=True, concentration_driven=True or "
+                                     "hist=: the misfit is carried by the plain forward forms only")
+                if not self.lib.fiveeq_misfit_layout_supported(G, n_pools):
+                    raise ValueError(f"observations=: pool layout {self.pools} has no misfit form (pools [4] and [4, 1, 1] have)")
+                table = np.asarray(observations.table, dtype=np.float64)
+                if table.shape != (self.n_steps, 4):
+                    raise ValueError(f"observations: table of {table.shape[0]} steps for a run of {self.n_steps}")
+                self.observations = observations
+                self.obs = torch.from_numpy(np.array(table, order="C")).to(dev)      # uploaded once
+                self.misfit = torch.zeros((3, N), dtype=torch.float64, device=dev)
         if chunk_members == "auto":
             chunk_members = self.auto_chunk(N, SP, G, dtype)
         self.chunk_members = int(chunk_members or 0) // 256 * 256
@@ -266,7 +284,9 @@ class EnsembleEngine(CheckpointMixin):
             return n_steps
         if self.fused_span != "auto":
             return min(self.fused_span, n_steps)
-        per_wave = 128 if self.dtype == torch.float32 and self.n_members % 2 == 0 else 64      # packed fp32 lanes carry two members
+        # packed fp32 lanes carry two members (with observations= only the 4 + 1 + 1 layout has a packed fused form)
+        packs = self.dtype == torch.float32 and self.n_members % 2 == 0 and (self.observations is None or self.pools == [4, 1, 1])
+        per_wave = 128 if packs else 64
         slots = 16 * torch.cuda.get_device_properties(self.device).multi_processor_count       # 4 waves on each of a CU's 4 SIMDs
         rounds = -(-self.n_members // per_wave) / slots
         # (below a quarter of a round the launches themselves weigh more than the tail: 10k members lose 3 %)
@@ -283,7 +303,7 @@ class EnsembleEngine(CheckpointMixin):
     def small_form(self):
         """Lanes per member mode='small' would run with now (4 or 1); 0 = the small-ensemble kernel does not apply: a run that
         wants in-loop histograms or the concentration-driven form."""
-        if not self.small_widest or self.T_hist is not None or self.concentration_driven:
+        if not self.small_widest or self.T_hist is not None or self.concentration_driven or self.observations is not None:
             return 0
         if self.compensated:                                     # fiveeq_run_small_comp_f32: one member per lane, every layout
             return 1 if self.small_lanes in ("auto", 1) else 0
@@ -335,6 +355,8 @@ class EnsembleEngine(CheckpointMixin):
             self.S.copy_(torch.from_numpy(self._S0).to(self.dtype))
         if self.cumE is not None:
             self.cumE.zero_()
+        if self.misfit is not None:
+            self.misfit.zero_()
         if self.T_hist is not None:
             self.T_hist.zero_()
         self._step_sums_valid[:] = False
@@ -373,6 +395,14 @@ class EnsembleEngine(CheckpointMixin):
             return [(0, N)]
         return [(m0, min(c, N - m0)) for m0 in range(0, N, c)]
 
+    def _obs_args(self, m0=0):
+        """(obs, misfit) C-ABI pointers for members [m0, ...) of the misfit rows (ld = N)."""
+        return self._ptr(self.obs), self._ptr(self.misfit, m0 * 8)
+
+    def _run_obs(self, t_begin, t_end, stream, form, k_steps=0, m0=0, n=None):
+        return self._fn("run_obs")(*self._run_args(t_begin, t_end, m0, n), *self._obs_args(m0), form, int(k_steps),
+                                   self._stream(stream))
+
     def _run_inverse(self, t_begin, t_end, stream):
         a = self._run_args(t_begin, t_end)
         return self._fn("run_inverse")(*a[:11], self._ptr(self.cumE), *a[11:], self._stream(stream))
@@ -389,6 +419,8 @@ class EnsembleEngine(CheckpointMixin):
         with torch.cuda.device(self.device):
             if self.concentration_driven:
                 rc = self._run_inverse(t, t + 1, stream)
+            elif self.observations is not None:
+                rc = self._run_obs(t, t + 1, stream, _capi.FORM_PER_STEP)
             else:
                 a = self._run_args(t, t + 1)
                 rc = self._fn("step")(*a[:5], t, *a[7:], self._stream(stream))
@@ -423,6 +455,9 @@ class EnsembleEngine(CheckpointMixin):
         if self.compensated and mode not in ("fused", "ksteps", "small"):
             raise ValueError(f"mode {mode!r} has no compensated form: the compensation words live in registers, so only the "
                              "time-fused kernel ('fused', 'ksteps') and the small-ensemble kernel ('small', one lane) carry them")
+        if self.observations is not None and mode == "small":
+            raise ValueError("mode 'small' does not carry the misfit of observations=: use 'per_step', 'graph', 'fused', "
+                             "'ksteps' or 'auto'")
         if mode == "small" and not self.small_form():
             raise ValueError("mode 'small' serves runs without in-loop histograms or the inverse form, with 4 lanes per "
                              "member for a lone 4-pool gas only and 8 for pools [4, 1, 1] without collect_stats "
@@ -445,6 +480,10 @@ class EnsembleEngine(CheckpointMixin):
                         max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
                 rc = self.lib.fiveeq_run_fused_comp_f32(*self._run_args(t_begin, t_end), span, 0.0, 1.0, 1, None, 0,
                                                         self._stream(stream))
+            elif self.observations is not None and mode in ("fused", "ksteps"):
+                k = (self.fused_span_steps(t_end - t_begin) if mode == "fused" else
+                     max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
+                rc = self._run_obs(t_begin, t_end, stream, _capi.FORM_FUSED, k)
             elif mode == "fused":
                 span = self.fused_span_steps(t_end - t_begin)
                 if span < t_end - t_begin:                       # the same kernel, relaunched every `span` steps
@@ -571,6 +610,10 @@ class EnsembleEngine(CheckpointMixin):
         kernel also writes every member's histogram bin into a ring strip [S, N] of uint16 (row t mod S); after S steps each
         part counts its strip into T_hist (fiveeq_hist_bins) on its own stream — 2 bytes written + 2 read per member-step on
         top of the step's 124 / 248."""
+        if self.observations is not None:
+            block = PER_STEP_BLOCK if self.per_step_streams > 1 else None
+            return self._per_step_schedule(t_begin, t_end, stream, join, block, lambda t, t1, m0, n, s: self._run_obs(
+                t, t1, s, _capi.FORM_PER_STEP, 0, m0, n))
         if self.T_hist is None:
             # several streams: short blocks keep every stream's queue fed; one stream: one C call per chunk
             block = PER_STEP_BLOCK if self.per_step_streams > 1 else None
@@ -646,11 +689,12 @@ class EnsembleEngine(CheckpointMixin):
         if plans is None:
             plans = []
             self._wave_stats()
-            fn = self._fn("plan_create")
+            fn = self._fn("plan_create" if self.observations is None else "plan_create_obs")
             with torch.cuda.device(self.device):
                 for m0, n, _ in self.per_step_launches():
                     plan = ctypes.c_void_p()
-                    _capi.check(self.lib, fn(*self._run_args(t_begin, t_end, m0, n), ctypes.byref(plan)))
+                    extra = () if self.observations is None else self._obs_args(m0)
+                    _capi.check(self.lib, fn(*self._run_args(t_begin, t_end, m0, n), *extra, ctypes.byref(plan)))
                     plans.append(plan)
             self._plans[key] = plans
         return plans
@@ -694,11 +738,29 @@ class EnsembleEngine(CheckpointMixin):
         from .distributed import moments_from_sums
         return moments_from_sums(self.stats_sums(t_begin, t_end))
 
-    def gather_summary(self, steps, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, gas=None):
+    def chi2(self):
+        """[N] fp64 on the device: each member's score against the observations, chi2 = V - 2 A U + A^2 P
+        (constrain.chi2_from_misfit).  Raises until the run has passed the last step with a nonzero weight: before that, A and
+        the sums describe part of the window only."""
+        if self.observations is None:
+            raise RuntimeError("engine was built without observations=")
+        last = self.observations.window[1]
+        if self.t_next < last:
+            raise RuntimeError(f"chi2: the run is at step {self.t_next}, the observation window ends at step {last}")
+        if self._ps_unjoined:
+            self.join()
+        from .constrain import chi2_from_misfit
+        return chi2_from_misfit(self.misfit, self.observations.P)
+
+    def gather_summary(self, steps, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, gas=None, accepted=None):
         """End-of-run summary of T — or, with `gas` = a gas index, of that gas's concentration C — at the stored `steps` over
         ALL members of all ranks (collective over `group`; see distributed.gather_summary): merged moments on every rank,
         exact percentiles on rank `dst`.  With collect_stats the moments of T come from the records the kernels wrote while
-        stepping — the summary then reads the rows twice (histogram, selection) instead of three times."""
+        stepping — the summary then reads the rows twice (histogram, selection) instead of three times.
+        accepted: a boolean [N] mask of this shard's members (constrain.accept_*): the summary is then over the ACCEPTED
+        members of all ranks only — the selected rows are compacted on the device and go through the same passes (the
+        in-kernel moment records cover every member, so they are not used); `count` is the global number accepted.  A rank
+        with no accepted member still takes part in every collective."""
         from .distributed import gather_summary
         stored = self.T if gas is None else self.C
         if stored is None or self.concentration_driven and gas is not None:
@@ -713,6 +775,11 @@ class EnsembleEngine(CheckpointMixin):
             raise ValueError(f"steps {missing} are not stored (out_steps)")
         picked = [row_of[int(t)] for t in steps]
         rows = self.T[picked] if gas is None else self.C[picked, int(gas)]
+        if accepted is not None:
+            mask = torch.as_tensor(accepted, device=self.device)
+            if mask.dtype != torch.bool or tuple(mask.shape) != (self.n_members,):
+                raise ValueError(f"accepted: want a boolean mask of shape [{self.n_members}]")
+            return gather_summary(rows[:, mask].contiguous(), percentiles, dst=dst, group=group, stats=stats)
         sums = None
         if gas is None and self.collect_stats and all(self._stats_have[int(t)] for t in steps):   # else: the moments pass over the rows
             sums = torch.cat([self.stats_sums(int(t), int(t) + 1) for t in steps])[:, 1:5].contiguous()
@@ -754,11 +821,16 @@ class EnsembleEngine(CheckpointMixin):
                          ring length);
         ksteps:          w (G + 1) + w (2 SP + 3 G + 6) / k_steps  (state + parameters once per k_steps).
         Statistics add one 32-byte record per wave of 64 members and step; with `hist=` the bin ring adds 2 B written + 2 B
-        read per member-step."""
+        read per member-step.  With `observations=` the misfit accumulators add, per_step: 48 B (3 fp64 read + written) per
+        member and step of the observation window, averaged over the run's steps; the fused forms: 48 B per member and launch."""
         w, G, SP = self._w, self.n_gas, self.sum_pools
         out = ((G if self.C is not None else 0) + 1) * self.n_rows / self.n_steps      # stored rows only
         extra = (32.0 / 64.0) if self.collect_stats else 0.0
         ring = 4.0 if (self.T_hist is not None and mode in ("fused", "per_step")) else 0.0
+        if self.observations is not None:
+            tab = self.observations.table
+            if mode == "per_step":
+                extra += 48.0 * np.count_nonzero((tab[:, 1] != 0) | (tab[:, 2] != 0)) / self.n_steps
         if mode == "per_step":
             return w * (2 * SP + 3 * G + 6 + out) + extra + ring
         if mode == "fused":
@@ -769,6 +841,8 @@ class EnsembleEngine(CheckpointMixin):
             span = self.n_steps
         else:
             raise ValueError(f"no byte count for mode {mode!r}")
+        if self.observations is not None:
+            extra += 48.0 / max(int(span), 1)
         return w * (out + (2 * SP + 3 * G + 6) / max(int(span), 1)) + extra + ring
 
 

@@ -139,3 +139,37 @@ def read_summary_csv(path):
     out["levels"] = [float(header[i][1:]) for i in pcols]
     out["percentiles"] = data[:, pcols]
     return data[:, 0], out
+
+
+def read_observations_csv(path):
+    """(years [n], T [n], sigma [n]) fp64 from an observed-temperature CSV with the columns YEAR, T, SIGMA (a header row
+    naming them, then one row per year; blank lines and lines starting with '#' are skipped).  Raises ValueError on a
+    malformed file.  Build the engine's table from it with constrain.Observations.from_years."""
+    with open(path, newline="") as fh:
+        rows = [[c.strip() for c in row] for row in csv.reader(fh) if row and not row[0].lstrip().startswith("#")]
+    rows = [r for r in rows if any(c != "" for c in r)]
+    if not rows or [c.upper() for c in rows[0][:3]] != ["YEAR", "T", "SIGMA"]:
+        raise ValueError(f"{path}: want a header row YEAR, T, SIGMA")
+    try:
+        table = np.array([[float(c) for c in r[:3]] for r in rows[1:]], dtype=np.float64).reshape(-1, 3)
+    except ValueError as exc:
+        raise ValueError(f"{path}: non-numeric data row ({exc})") from None
+    if table.shape[0] == 0:
+        raise ValueError(f"{path}: no data rows")
+    return table[:, 0].copy(), table[:, 1].copy(), table[:, 2].copy()
+
+
+def write_observations_csv(path, years, T, sigma, comment=None):
+    """Write the YEAR, T, SIGMA layout read_observations_csv reads (values with 17 significant digits: a round trip is exact)."""
+    years, T = np.asarray(years, dtype=np.float64).reshape(-1), np.asarray(T, dtype=np.float64).reshape(-1)
+    sigma = np.broadcast_to(np.asarray(sigma, dtype=np.float64), years.shape)
+    if T.shape != years.shape:
+        raise ValueError("years and T differ in length")
+    with open(path, "w", newline="") as fh:
+        if comment:
+            for line in str(comment).splitlines():
+                fh.write(f"# {line}\n")
+        w = csv.writer(fh, lineterminator="\n")
+        w.writerow(["YEAR", "T", "SIGMA"])
+        for y, t, s in zip(years, T, sigma):
+            w.writerow([repr(float(y)) if y != int(y) else str(int(y)), repr(float(t)), repr(float(s))])

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define FIVEEQ_ABI_VERSION   11
+#define FIVEEQ_ABI_VERSION   12
 #define FIVEEQ_MAX_GAS       3
 #define FIVEEQ_MAX_POOLS     4
 #define FIVEEQ_N_BOX         2
@@ -201,6 +201,54 @@ int fiveeq_run_ksteps_f32(const fiveeq_model *model, int64_t n_members, int64_t 
                           const float *r, const float *q, float *R, float *S,
                           float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
                           int32_t k_steps, void *stream);
+
+/* CONSTRAINED RUNS — the in-loop misfit against an observed series (new, ABI v12).  Replaces storing every T row of the
+ * observed period and scoring it afterwards (170 steps x N x w bytes): each member carries three fp64 accumulators
+ * misfit dev [3][ld] = (A, U, V), read and written in place (zero them before the first step of the window).
+ *   obs dev [n_steps][4] fp64, shared: per step t (o_t, p_t, b_t, 0) — o_t the observed anomaly, p_t = 1/sigma_t^2 (0 = no
+ *       observation), b_t the baseline weight (1/n_ref inside the reference period, else 0).
+ * With Tw = T after step t (the value T_traj would store; fp32 widened exactly) every form updates, in step order and with
+ * each operation rounded separately (no fma):
+ *     A = A + b_t Tw;  d = Tw - o_t;  pd = p_t d;  U = U + pd;  V = V + pd d
+ * and leaves the rows untouched on steps with p_t == 0 && b_t == 0.  The score of the baseline-corrected series is then
+ * chi2 = V - 2 A U + A^2 P with P = sum_t p_t (= sum_t p_t (T_t - mean_ref T - o_t)^2), computed by the caller.
+ * Everything else — C_traj, T_traj, the row map, T_stats, R, S — exactly as in fiveeq_run_* / fiveeq_run_ksteps_*, bit for
+ * bit; the accumulators are the same bits in every form and for every split of the range into calls.
+ *   form FIVEEQ_FORM_PER_STEP: one launch of the per-step kernel per step (fiveeq_run_*); the obs record is read with scalar
+ *       loads and a step inside the window moves 48 B more per member (24 read + 24 written), one outside it nothing more;
+ *   form FIVEEQ_FORM_FUSED: the time-fused kernel over spans of k_steps (0 = one launch for the range; fiveeq_run_fused_* /
+ *       fiveeq_run_ksteps_*): the accumulators stay on chip — in a lane-private LDS slot, not registers, so that every
+ *       layout keeps its plain kernel's waves per SIMD — and cross HBM once per launch (48 B per member).  fp32 {4} runs
+ *       one member per lane (no packed misfit form for that layout); fp32 4 + 1 + 1 packs two members per lane as usual.
+ * Pool layouts {4} and 4 + 1 + 1 only (fiveeq_misfit_layout_supported); not in the small-ensemble, concentration-driven,
+ * compensated or histogram-ring forms.  FIVEEQ_E_INVALID for NULL or unaligned obs / misfit, an unknown form, k_steps < 0,
+ * a step range outside [0, n_steps) or a layout without a misfit form — before anything is launched. */
+#define FIVEEQ_FORM_PER_STEP 0
+#define FIVEEQ_FORM_FUSED    1
+int fiveeq_run_obs_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                       const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                       const double *r, const double *q, double *R, double *S,
+                       double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                       const double *obs, double *misfit, int32_t form, int32_t k_steps, void *stream);
+int fiveeq_run_obs_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                       const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                       const float *r, const float *q, float *R, float *S,
+                       float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                       const double *obs, double *misfit, int32_t form, int32_t k_steps, void *stream);
+/* new — fiveeq_plan_create_* of the per-step form above: the launches of [t_begin, t_end) with the misfit, captured once;
+ * the plan bakes in obs and misfit too. */
+int fiveeq_plan_create_obs_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                               const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                               const double *r, const double *q, double *R, double *S,
+                               double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                               const double *obs, double *misfit, void **plan_out);
+int fiveeq_plan_create_obs_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                               const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                               const float *r, const float *q, float *R, float *S,
+                               float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                               const double *obs, double *misfit, void **plan_out);
+/* new — 1 if the pool layout has the misfit forms above, else 0 */
+int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t *n_pools);
 
 /* SMALL ENSEMBLES (BASELINE configs[1], 10k CO2-only members): the time-fused step with ONE MEMBER
  * SPREAD OVER SEVERAL LANES.  An ensemble of fewer waves than the chip has SIMDs (1024) is bound by the number of
