@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FIVEEQ_LIB_PATH selects another build of the same library (e.g. the host-sanitizer build of tools/sanitize_host.sh)
 LIB_PATH = os.environ.get("FIVEEQ_LIB_PATH") or os.path.join(_HERE, "csrc", "libfiveeq_hip.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_GAS = 3
 MAX_POOLS = 4
 N_BOX = 2
@@ -104,6 +104,11 @@ SIGNATURES = {
     "fiveeq_plan_create_obs_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, ctypes.POINTER(_p)]),
     "fiveeq_plan_create_obs_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, ctypes.POINTER(_p)]),
     "fiveeq_misfit_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32)]),
+    "fiveeq_run_scen_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_i32, _i32, _p]),
+    "fiveeq_run_scen_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_i32, _i32, _p]),
+    "fiveeq_plan_create_scen_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [ctypes.POINTER(_p)]),
+    "fiveeq_plan_create_scen_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [ctypes.POINTER(_p)]),
+    "fiveeq_max_scenarios": (_i32, []),
     "fiveeq_small_lanes": (_i32, [_i32, ctypes.POINTER(_i32)]),
     "fiveeq_set_f32_packing": (ctypes.c_int, [ctypes.c_int]),
     "fiveeq_set_row_policy": (ctypes.c_int, [_i32]),

@@ -29,6 +29,9 @@ class CheckpointMixin:
         if self.misfit is not None:                              # the misfit accumulators are state: always carried
             out["misfit"] = self.misfit.cpu().numpy()
             out["obs_sha256"] = self.observations.sha256
+        if self.scenario_axis:                                   # which scenario set the per-scenario state belongs to
+            out["n_scenarios"] = int(self.n_scenarios)
+            out["drive_sha256"] = self.drive_sha256
         if include_outputs:
             if self.T_hist is not None:
                 out["T_hist"] = self.T_hist.cpu().numpy()
@@ -36,12 +39,15 @@ class CheckpointMixin:
                 # only the steps this engine HAS moments for (it ran them, or a checkpoint brought them): a run that began
                 # at t_begin > 0, or a state-only checkpoint loaded before it, leaves the earlier steps out — their
                 # zero-filled records are not moments
-                sums = np.zeros((self.n_steps, 5), dtype=np.float64)
+                scens = range(self.n_scenarios) if self.scenario_axis else [None]
+                sums = np.zeros((len(scens), self.n_steps, 5), dtype=np.float64)
                 valid = self._stats_have.copy()
                 if valid.any():
                     lo_t, hi_t = int(np.nonzero(valid)[0][0]), int(np.nonzero(valid)[0][-1]) + 1
-                    sums[lo_t:hi_t] = self.stats_sums(lo_t, hi_t).cpu().numpy()
-                    sums[~valid] = 0.0
+                    for i, sc in enumerate(scens):
+                        sums[i, lo_t:hi_t] = self.stats_sums(lo_t, hi_t, scenario=sc).cpu().numpy()
+                    sums[:, ~valid] = 0.0
+                sums = sums if self.scenario_axis else sums[0]
                 out["_step_sums"], out["_step_sums_valid"] = sums, valid
         if include_outputs is True:
             for name in ("T_stats", "C", "T"):
@@ -60,6 +66,10 @@ class CheckpointMixin:
         mine = None if self.observations is None else self.observations.sha256
         if state.get("obs_sha256") != mine:
             raise ValueError(f"checkpoint observation table {state.get('obs_sha256')!r} is not this engine's ({mine!r})")
+        mine = (self.n_scenarios, self.drive_sha256) if self.scenario_axis else None
+        theirs = (int(state["n_scenarios"]), state.get("drive_sha256")) if "n_scenarios" in state else None
+        if theirs != mine:
+            raise ValueError(f"checkpoint scenario set (n_scenarios, drive sha256) {theirs!r} is not this engine's {mine!r}")
         if "T_stats" in state and self.collect_stats:
             self._wave_stats()                                   # the checkpoint carries wave records: make room for them (no state touched)
         staged = {}

@@ -560,6 +560,125 @@ int run_obs(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_
     return FIVEEQ_OK;
 }
 
+// ---- the scenario axis: one parameter ensemble under n_scen emission scenarios (step_scen_kernel, fused_kernel<.., SCEN>) ----
+constexpr int MAX_SCENARIOS = 64;
+
+// the row policy of kernel 1s: as rows_streamed(), with the S-fold state counted — n_scen (SP + 2) state rows beside the
+// 3G + 2 shared parameter rows per member
+bool rows_streamed_scen(int policy, int n_gas, int sum_pools, int n_scen, int64_t n, int64_t ld, int word) {
+    if (policy != FIVEEQ_ROWS_AUTO) return policy == FIVEEQ_ROWS_STREAMED;
+    const int64_t per_member = (int64_t)word * ((int64_t)n_scen * (sum_pools + 2) + 3 * n_gas + 2);
+    return n * per_member >= INFINITY_CACHE_BYTES && ld * per_member >= 2 * INFINITY_CACHE_BYTES;
+}
+
+template <typename T>
+int launch_step_scen(const RunArgs<T>& a, int t, int n_scen, bool nt, hipStream_t st) {
+    using P = typename LaneOf<T>::Packed;
+    const bool packed = LaneOf<T>::can_pack(a);
+    const int64_t per_block = (int64_t)FIVEEQ_STEP_BLOCK * (packed ? 2 : 1);
+    const int64_t blocks = (a.n + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
+    const dim3 grid((unsigned)blocks), block(FIVEEQ_STEP_BLOCK);
+    switch (a.code) {
+#define FIVEEQ_SCEN_LAUNCH(V, p0, p1, p2, NT)                                                                                   \
+    hipLaunchKernelGGL((step_scen_kernel<V, p0, p1, p2, NT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, n_scen, \
+                       a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats)
+#define X(p0, p1, p2)                                                                             \
+    case (p0) * 100 + (p1) * 10 + (p2):                                                           \
+        if (nt) {                                                                                 \
+            if (packed) FIVEEQ_SCEN_LAUNCH(P, p0, p1, p2, true);                                  \
+            else FIVEEQ_SCEN_LAUNCH(T, p0, p1, p2, true);                                         \
+        } else {                                                                                  \
+            if (packed) FIVEEQ_SCEN_LAUNCH(P, p0, p1, p2, false);                                 \
+            else FIVEEQ_SCEN_LAUNCH(T, p0, p1, p2, false);                                        \
+        }                                                                                         \
+        break;
+        FIVEEQ_LAYOUTS(X)
+#undef X
+#undef FIVEEQ_SCEN_LAUNCH
+        default:
+            return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+    }
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+
+template <typename T>
+int launch_fused_scen(const RunArgs<T>& a, int t_begin, int t_end, int n_scen, hipStream_t st) {
+    using P = typename LaneOf<T>::Packed;
+    constexpr bool HAS_PACKED = !std::is_same<P, T>::value;
+    const bool packed = HAS_PACKED && LaneOf<T>::can_pack(a);
+    const int64_t blocks = member_blocks(packed ? (a.n + 1) / 2 : a.n);
+    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
+    const dim3 grid((unsigned)blocks, (unsigned)n_scen), block(FIVEEQ_BLOCK);
+    switch (a.code) {
+#define FIVEEQ_SCEN_FUSED(V, p0, p1, p2)                                                                                        \
+    hipLaunchKernelGGL((fused_kernel<V, p0, p1, p2, false, false, false, false, true>), grid, block, FIVEEQ_FUSED_DYN_LDS, st,   \
+                       a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, nullptr, a.C_traj, a.T_traj,   \
+                       a.n_rows, a.stats, nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr)
+#define X(p0, p1, p2)                                                                             \
+    case (p0) * 100 + (p1) * 10 + (p2):                                                           \
+        if constexpr (HAS_PACKED) {                                                               \
+            if (packed) {                                                                         \
+                FIVEEQ_SCEN_FUSED(P, p0, p1, p2);                                                 \
+                break;                                                                            \
+            }                                                                                     \
+        }                                                                                         \
+        FIVEEQ_SCEN_FUSED(T, p0, p1, p2);                                                         \
+        break;
+        FIVEEQ_LAYOUTS(X)
+#undef X
+#undef FIVEEQ_SCEN_FUSED
+        default:
+            return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+    }
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+
+int scen_check(int32_t n_scen) {
+    if (n_scen < 1 || n_scen > MAX_SCENARIOS) return fail(FIVEEQ_E_INVALID, "n_scen=%d outside 1..%d", n_scen, MAX_SCENARIOS);
+    return FIVEEQ_OK;
+}
+
+// make_args() for the scenario forms: the scenario count checked first, the row policy counted with the S-fold state
+template <typename T>
+int make_scen_args(RunArgs<T>& a, bool& nt, const fiveeq_model* m, int64_t n, int64_t ld, int32_t n_scen, const T* drive,
+                   int32_t n_steps, int32_t t_begin, int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj,
+                   int n_rows, double* stats) {
+    if (int rc = scen_check(n_scen)) return rc;
+    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    int sum_pools = 0;
+    for (int g = 0; g < m->n_gas; ++g) sum_pools += m->gas[g].n_pools;
+    nt = rows_streamed_scen(g_row_policy.load(std::memory_order_relaxed), m->n_gas, sum_pools, n_scen, n, ld, (int)sizeof(T));
+    return FIVEEQ_OK;
+}
+
+template <typename T>
+int run_scen(const fiveeq_model* m, int64_t n, int64_t ld, int32_t n_scen, const T* drive, int32_t n_steps, int32_t t_begin,
+             int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, int32_t form,
+             int32_t k_steps, void* stream) {
+    RunArgs<T> a;
+    bool nt = false;
+    if (int rc = make_scen_args(a, nt, m, n, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                                stats))
+        return rc;
+    if (form != FIVEEQ_FORM_PER_STEP && form != FIVEEQ_FORM_FUSED)
+        return fail(FIVEEQ_E_INVALID, "form=%d: FIVEEQ_FORM_PER_STEP (0) or FIVEEQ_FORM_FUSED (1)", form);
+    if (k_steps < 0) return fail(FIVEEQ_E_INVALID, "k_steps=%d must be >= 0", k_steps);
+    if (t_begin == t_end) return FIVEEQ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (form == FIVEEQ_FORM_PER_STEP) {
+        for (int t = t_begin; t < t_end; ++t)
+            if (int rc = launch_step_scen(a, t, n_scen, nt, st)) return rc;
+        return FIVEEQ_OK;
+    }
+    if (k_steps == 0 || k_steps > t_end - t_begin) k_steps = t_end - t_begin;
+    for (int t = t_begin; t < t_end; t += k_steps)
+        if (int rc = launch_fused_scen(a, t, t + k_steps < t_end ? t + k_steps : t_end, n_scen, st)) return rc;
+    return FIVEEQ_OK;
+}
+
 // ---- plans: the per-step launch sequence captured into a hipGraph --------------------------
 struct Plan {
     uint32_t magic;
@@ -571,11 +690,18 @@ constexpr uint32_t PLAN_MAGIC = 0x35455146u;  // "FQE5"
 template <typename T>
 int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
                 int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void** plan_out,
-                const MisfitRows* mf = nullptr) {
+                const MisfitRows* mf = nullptr, int32_t n_scen = 0 /* > 0: the scenario form, step_scen_kernel */) {
     if (!plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
     *plan_out = nullptr;
     RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    bool scen_nt = false;
+    if (n_scen != 0) {
+        if (int rc = make_scen_args(a, scen_nt, m, n, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                    n_rows, stats))
+            return rc;
+    } else if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) {
+        return rc;
+    }
     if (mf) {
         if (int rc = misfit_check(mf->obs, mf->misfit)) return rc;
         if (int rc = misfit_layout_check(a.code)) return rc;
@@ -591,7 +717,8 @@ int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
     }
     int rc = FIVEEQ_OK;
     for (int t = t_begin; t < t_end && rc == FIVEEQ_OK; ++t)
-        rc = mf ? launch_step<T, false, true>(a, t, cap, BinRing(), *mf) : launch_step(a, t, cap);
+        rc = n_scen ? launch_step_scen(a, t, n_scen, scen_nt, cap)
+                    : (mf ? launch_step<T, false, true>(a, t, cap, BinRing(), *mf) : launch_step(a, t, cap));
     e = hipStreamEndCapture(cap, &graph);
     (void)hipStreamDestroy(cap);
     if (rc != FIVEEQ_OK) {
@@ -835,6 +962,38 @@ int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     for (int g = 0; g < n_gas; ++g) p[g] = n_pools[g];
     return misfit_layout(p[0], p[1], p[2]) ? 1 : 0;
 }
+
+int fiveeq_run_scen_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
+                        int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
+                        double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, int32_t form, int32_t k_steps,
+                        void* stream) {
+    return run_scen<double>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                            T_stats, form, k_steps, stream);
+}
+int fiveeq_run_scen_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
+                        int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
+                        float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, int32_t form, int32_t k_steps,
+                        void* stream) {
+    return run_scen<float>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                           T_stats, form, k_steps, stream);
+}
+int fiveeq_plan_create_scen_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
+                                int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
+                                double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
+    if (plan_out) *plan_out = nullptr;
+    if (int rc = scen_check(n_scen)) return rc;
+    return plan_create<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                               plan_out, nullptr, n_scen);
+}
+int fiveeq_plan_create_scen_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
+                                int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
+                                float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
+    if (plan_out) *plan_out = nullptr;
+    if (int rc = scen_check(n_scen)) return rc;
+    return plan_create<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                              plan_out, nullptr, n_scen);
+}
+int32_t fiveeq_max_scenarios(void) { return MAX_SCENARIOS; }
 
 int32_t fiveeq_small_lanes(int32_t n_gas, const int32_t* n_pools) {
     if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;

@@ -974,6 +974,94 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
 }
 
 // ---------------------------------------------------------------------------------
+// Kernel 1s — SCENARIOS (ABI v13): one step of every parameter member under each of n_scen emission scenarios.  Same
+// block shape, lane packing and row policy (NT) as step_kernel; the lane loads its member's 3G + 2 parameter rows ONCE
+// and then, scenario by scenario, loads that scenario's R and S, calls the same member_step() with that scenario's drive
+// record, and stores R, S, the stored rows and the wave's statistics record: member-scenario (m, s) is bit for bit member
+// m of step_kernel run on scenario s's drive table.  Per member-scenario-step: w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / S.
+// The drive records are wave-uniform (a workgroup is one wave) and are read with scalar loads straight from
+// drive [n_scen][n_steps][8] — no LDS staging and no barrier per scenario.  Every scenario stride derives from ld:
+//   R [n_scen][SP][ld], S [n_scen][2][ld], C_traj [n_scen][n_rows][G][ld], T_traj [n_scen][n_rows][ld],
+//   stats [n_scen][ceil(ld/64)][n_steps][4]
+// so a member sub-range [m0, m0 + n) is a plain pointer offset, as for step_kernel.
+// ---------------------------------------------------------------------------------
+template <typename V, int P0, int P1, int P2, bool NT = false>
+__global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_scen_kernel(
+    const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
+    const int64_t n, const int64_t ld, const int n_scen,
+    const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
+    typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
+    typename Lane<V>::S* __restrict__ C_traj, typename Lane<V>::S* __restrict__ T_traj,
+    const int n_rows, double* __restrict__ stats) {
+    using L = Layout<P0, P1, P2>;
+    using T = typename Lane<V>::S;
+    constexpr int W = Lane<V>::W;                 // members per lane
+    constexpr bool NTT = true;                    // the stored C / T rows: written once, never read by a stepping kernel
+    const int64_t m = ((int64_t)blockIdx.x * FIVEEQ_STEP_BLOCK + threadIdx.x) * W;
+    const bool active = m < n;
+    const bool full = m + (W - 1) < n;
+    const int64_t mm = active ? m : ((n - 1) & ~(int64_t)(W - 1));
+    __shared__ KModel<T> km_s;
+    constexpr int NW = sizeof(KModel<T>) / sizeof(T);
+    static_assert(NW <= FIVEEQ_STEP_BLOCK, "model must stage in one pass");
+    const T* kargs = (const T*)__builtin_amdgcn_kernarg_segment_ptr();
+    T stage_v = T(0);
+    if (threadIdx.x < NW) stage_v = kargs[threadIdx.x];
+    const KModel<T>& kmr = km_s;
+
+    V rr[3 * L::G], qq[2], Rv[L::SP], Sv[2], Cv[L::G];
+#pragma unroll
+    for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_row<V, NT>(r + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) qq[k] = load_row<V, NT>(q + k * ld + mm);
+    if (threadIdx.x < NW) reinterpret_cast<T*>(&km_s)[threadIdx.x] = stage_v;
+    __syncthreads();
+
+    const int64_t n_rec = (n + 63) >> 6;
+    const int64_t wave = (int64_t)blockIdx.x * (FIVEEQ_STEP_BLOCK / 64) + (threadIdx.x >> 6);
+    const int64_t rec_stride = ((ld + 63) >> 6) * n_steps * 4;       // one scenario's statistics records
+    // one 64-bit lane base per array, advanced by a scenario stride; the row offsets inside a scenario are wave-uniform (an
+    // active lane stores where it loaded: m == mm) — per-row lane addresses kept live across the loop cost 50 VGPRs
+    T* Rl = R + mm;
+    T* Sl = S + mm;
+#pragma unroll 1
+    for (int sc = 0; sc < n_scen; ++sc, Rl += (int64_t)L::SP * ld, Sl += 2 * ld) {
+#pragma unroll
+        for (int k = 0; k < L::SP; ++k) Rv[k] = load_row<V, NT>(Rl + k * ld);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) Sv[k] = load_row<V, NT>(Sl + k * ld);
+        const T* d = drive + ((int64_t)sc * n_steps + t) * DRIVE_STRIDE;    // wave-uniform: scalar loads
+        V Tn = (V)T(0);
+        member_step<V, L>(kmr, d, rr, qq, Rv, Sv, Cv, Tn);
+        if (active) {
+#pragma unroll
+            for (int k = 0; k < L::SP; ++k) store_row<NT>(Rl + k * ld, Rv[k], full);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) store_row<NT>(Sl + k * ld, Sv[k], full);
+            const int row = __builtin_amdgcn_readfirstlane((int)d[7]);
+            if (row >= 0 && row < n_rows) {
+                if (C_traj != nullptr) {
+                    T* c = C_traj + ((int64_t)sc * n_rows + row) * L::G * ld + m;
+#pragma unroll
+                    for (int g = 0; g < L::G; ++g) store_row<NTT>(c + g * ld, Cv[g], full);
+                }
+                if (T_traj != nullptr) store_row<NTT>(T_traj + ((int64_t)sc * n_rows + row) * ld + m, Tn, full);
+            }
+        }
+        if (stats != nullptr) {
+            double* const st = stats + sc * rec_stride;
+            if constexpr (W == 1) {
+                if (wave < n_rec) wave_stats(active, Tn, st + (wave * n_steps + t) * 4);
+            } else {
+                if (2 * wave < n_rec)
+                    wave_stats(active, full, Tn, st + (2 * wave * n_steps + t) * 4,
+                               2 * wave + 1 < n_rec ? st + ((2 * wave + 1) * n_steps + t) * 4 : nullptr);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // Kernel 2 — TIME-FUSED: one launch advances [t_begin, t_end); a member's state and
 // parameters stay in registers for the whole span, the drive table is staged into LDS
 // FIVEEQ_FUSED_CHUNK steps at a time, and only the C/T rows of stored steps go to HBM.
@@ -996,7 +1084,13 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
 // five workgroups per CU, 5 x 31 KB of 160 KB), so the window test is a scalar branch.  Every MISFIT instantiation keeps
 // its plain counterpart's waves per SIMD with no scratch (tools/kernel_isa_stats.py); the packed fp32 form is instantiated
 // for 4 + 1 + 1 only (fiveeq_capi.hip, misfit_packed_fused).
-template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false>
+//
+// SCEN = true (ABI v13; INV, BINS, COMP and MISFIT false): the grid's y dimension is the emission scenario.  A workgroup is
+// scenario-uniform: it stages its own scenario's drive chunk and offsets the state, row and statistics pointers by the
+// scenario strides of kernel 1s (all derived from ld, n_steps and n_rows, so no argument is added).  With SCEN false not
+// one instruction of the kernel changes.
+template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false,
+          bool SCEN = false>
 __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps,
     const int t_begin, const int t_end, const int64_t n, const int64_t ld,
@@ -1014,6 +1108,16 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     constexpr int W = Lane<V>::W;                 // members per lane
     static_assert(!(INV && BINS), "no streamed histograms in the concentration-driven form");
     static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
+    static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
+    if constexpr (SCEN) {
+        const int64_t sc = blockIdx.y;
+        drive += sc * n_steps * DRIVE_STRIDE;
+        R += sc * L::SP * ld;
+        S += sc * 2 * ld;
+        if (C_traj != nullptr) C_traj += sc * n_rows * L::G * ld;
+        if (T_traj != nullptr) T_traj += sc * n_rows * ld;
+        if (stats != nullptr) stats += sc * ((ld + 63) >> 6) * n_steps * 4;
+    }
     __shared__ T drv[FIVEEQ_FUSED_CHUNK * DRIVE_STRIDE];
     __shared__ double acc_s[MISFIT ? 3 * W * FIVEEQ_BLOCK : 1];       // MISFIT: [3 W][FIVEEQ_BLOCK], lane-private
     __shared__ V stat_tile[FIVEEQ_BLOCK / 64][STAT_STEPS * STAT_ROW];

@@ -70,3 +70,26 @@ def make_drive(emissions, F_ext=None, dt=1.0, output_steps=None, concentration_d
         drive[:, 7] = -1.0
         drive[steps, 7] = np.arange(steps.size)
     return drive
+
+
+def make_scenario_drive(emissions, F_ext=None, dt=1.0, output_steps=None):
+    """The drive tables of S emission scenarios, stacked: emissions [S, n_steps, G] (or a sequence of S [n_steps, G]
+    arrays) -> drive [S, n_steps, 8] fp64, scenario s being make_drive(emissions[s], F_ext[s], dt, output_steps) — each
+    scenario's own cumulative-emission columns, ONE row map (column 7) for all.  F_ext: None, [n_steps] (shared) or
+    [S, n_steps]."""
+    try:
+        E = np.asarray(emissions, dtype=np.float64)
+    except ValueError as exc:
+        raise ValueError("scenario emissions: every scenario needs the same [n_steps, G] shape") from exc
+    if E.ndim != 3 or E.shape[0] < 1:
+        raise ValueError(f"scenario emissions shape {E.shape}: want [S>=1, n_steps, G]")
+    S, n_steps = E.shape[0], E.shape[1]
+    if F_ext is None:
+        F = [None] * S
+    else:
+        F = np.asarray(F_ext, dtype=np.float64)
+        if F.ndim == 1 and F.shape[0] == n_steps:
+            F = [F] * S
+        elif F.shape != (S, n_steps):
+            raise ValueError(f"F_ext shape {F.shape}: want [{n_steps}] or [{S}, {n_steps}]")
+    return np.stack([make_drive(E[s], F[s], dt, output_steps) for s in range(S)])

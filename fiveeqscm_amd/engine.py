@@ -26,7 +26,7 @@ import torch
 
 from . import _capi
 from .checkpoint import CheckpointMixin
-from .emissions import make_drive
+from .emissions import emissions_sha256, make_drive, make_scenario_drive
 from .params import make_model, n_gas_of, pools_of
 from .tuning import (_env_choice, _env_positive, calibrate, concurrent_side_streams,  # noqa: F401  (calibrate: part of this
                      side_stream_report)                                               # module's interface)
@@ -83,6 +83,13 @@ def _rows(x, K, N, name):
     return x
 
 
+def _is_scenario_set(emissions):
+    """True for emissions of several scenarios: a 3-D array, or a sequence of 2-D [n_steps, G] arrays."""
+    if isinstance(emissions, (list, tuple)):
+        return len(emissions) > 0 and all(np.ndim(e) == 2 for e in emissions)
+    return np.ndim(emissions) == 3
+
+
 class EnsembleEngine(CheckpointMixin):
     """Advance N ensemble members of the five-equation model on one MI355X."""
 
@@ -92,7 +99,7 @@ class EnsembleEngine(CheckpointMixin):
                  device=None, store_trajectory=True, output_steps=None, store_concentrations=True,
                  collect_stats=False, hist=None, hist_ring_steps="auto", concentration_driven=False,
                  chunk_members="auto", per_step_streams="auto", fused_span="auto", small_lanes="auto", compensated=False,
-                 R0=None, S0=None, lib_path=None, observations=None):
+                 R0=None, S0=None, lib_path=None, observations=None, scenario_names=None):
         """store_trajectory / output_steps: True stores C, T of every step; a list of step indices
         stores only those (rows in increasing step order, see `out_steps`); False stores nothing.
         store_concentrations=False keeps only the T rows (a 100M-member fp32 run then stores 4 B instead
@@ -139,7 +146,15 @@ class EnsembleEngine(CheckpointMixin):
         accumulators `misfit` [3, N] fp64 (A, U, V: include/fiveeq.h "CONSTRAINED RUNS") through modes 'per_step', 'graph',
         'fused' and 'ksteps' — the same bits in each, and C, T, R, S exactly as without it; `chi2()` scores the members.
         Pool layouts {4} and 4 + 1 + 1; not with compensated=True, concentration_driven=True or hist=, and never in mode
-        'small' ('auto' takes 'per_step', 'ksteps' or 'fused' instead)."""
+        'small' ('auto' takes 'per_step', 'ksteps' or 'fused' instead).
+        SCENARIOS: `emissions` of shape [S, n_steps, G] (or a sequence of S [n_steps, G] arrays) advances every parameter
+        member under each of the S emission scenarios (include/fiveeq.h "SCENARIOS"): member-scenario (m, s) is bit for bit
+        member m of a one-scenario engine on scenario s.  The parameter rows are shared; R [S, SP, N], S [S, 2, N],
+        C [S, n_rows, G, N], T [S, n_rows, N] and the statistics carry one slice per scenario (stats(), stats_sums(),
+        gather_summary() and T_histogram() then take scenario=).  F_ext: [n_steps] (shared) or [S, n_steps]; R0 / S0: one
+        [SP, N] / [2, N] state for every scenario, or [S, ...].  scenario_names: S labels (default "0", "1", ...).  Modes
+        'per_step', 'graph', 'fused', 'ksteps' and 'auto' (never 'small'); not with concentration_driven=True, hist=,
+        observations= or compensated=True.  `n_scenarios` is S (1 for an engine without the scenario axis)."""
         if dtype not in _DTYPES:
             raise ValueError("dtype must be torch.float64 or torch.float32")
         self.lib = _capi.load(lib_path)    # raises if the HIP library is not built
@@ -171,12 +186,36 @@ class EnsembleEngine(CheckpointMixin):
         self.compensated = bool(compensated)
         if self.compensated and (dtype != torch.float32 or self.concentration_driven):
             raise ValueError("compensated=True is an fp32 form of the emission-driven step (fp64 does not need it)")
-        drive = make_drive(emissions, F_ext, dt, output_steps, self.concentration_driven)
-        self.out_steps = np.nonzero(drive[:, 7] >= 0)[0]          # step index of each stored row
+        # the scenario axis: a 3-D emissions array or a sequence of 2-D ones (both of which make_drive refuses)
+        self.scenario_axis = _is_scenario_set(emissions)
+        if self.scenario_axis:
+            if self.concentration_driven or hist is not None or observations is not None or self.compensated:
+                raise ValueError("an engine with several emission scenarios runs the plain emission-driven forms only: not "
+                                 "with concentration_driven=True, hist=, observations= or compensated=True")
+            drive = make_scenario_drive(emissions, F_ext, dt, output_steps)
+            self.n_scenarios = Sc = int(drive.shape[0])
+            max_s = int(self.lib.fiveeq_max_scenarios())
+            if Sc > max_s:
+                raise ValueError(f"{Sc} scenarios: at most {max_s} per engine")
+            names = [str(i) for i in range(Sc)] if scenario_names is None else [str(x) for x in scenario_names]
+            if len(names) != Sc:
+                raise ValueError(f"scenario_names: {len(names)} names for {Sc} scenarios")
+            self.scenario_names = names
+            self.drive_sha256 = emissions_sha256(drive)
+            row_map = drive[0]
+        else:
+            if scenario_names is not None:
+                raise ValueError("scenario_names= needs emissions of several scenarios ([S, n_steps, G])")
+            drive = make_drive(emissions, F_ext, dt, output_steps, self.concentration_driven)
+            self.n_scenarios = Sc = 1
+            self.scenario_names = None
+            row_map = drive
+        self.out_steps = np.nonzero(row_map[:, 7] >= 0)[0]          # step index of each stored row
         self.n_rows = int(self.out_steps.size)
-        if drive[:, G:3].any():
+        if drive[..., G:3].any():
             raise ValueError("emissions carry more gases than the parameter set")
-        self.n_steps = int(drive.shape[0])
+        self.n_steps = int(row_map.shape[0])
+        lead = (Sc,) if self.scenario_axis else ()          # the leading scenario axis of the state, rows and records
 
         dev, dt_ = self.device, dtype
         with torch.cuda.device(dev):
@@ -192,20 +231,20 @@ class EnsembleEngine(CheckpointMixin):
                                       axis=0)                                  # [3G, N]
                 self.r = torch.from_numpy(np.array(rows, dtype=np.float64, order="C")).to(dev, dt_).contiguous()
                 self.q = torch.from_numpy(np.array(q_rows, dtype=np.float64, order="C")).to(dev, dt_).contiguous()
-            self.R = torch.zeros((SP, N), dtype=dt_, device=dev)
-            self.S = torch.zeros((2, N), dtype=dt_, device=dev)
+            self.R = torch.zeros(lead + (SP, N), dtype=dt_, device=dev)
+            self.S = torch.zeros(lead + (2, N), dtype=dt_, device=dev)
             # zero-filled, not torch.empty: rows of steps that were not run read as 0 rather than as stale
             # device memory (and the fill touches every page once, at construction)
-            self.C = (torch.zeros((self.n_rows, G, N), dtype=dt_, device=dev)
+            self.C = (torch.zeros(lead + (self.n_rows, G, N), dtype=dt_, device=dev)
                       if self.n_rows and (store_concentrations or concentration_driven) else None)
-            self.T = torch.zeros((self.n_rows, N), dtype=dt_, device=dev) if self.n_rows else None
+            self.T = torch.zeros(lead + (self.n_rows, N), dtype=dt_, device=dev) if self.n_rows else None
             self.cumE = torch.zeros((G, N), dtype=dt_, device=dev) if self.concentration_driven else None
             self.E = self.C if self.concentration_driven else None
             self.n_waves = int(self.lib.fiveeq_stats_waves(N))
             self.collect_stats = bool(collect_stats)
             self.T_stats = None          # per-wave records: 4.7 GB at 12.5M members x 750 steps, so allocated on demand
             # per-step (count, sum, sum^2, min, max) folded from the wave records: what a checkpoint's "summaries" carry
-            self._step_sums = (torch.zeros((self.n_steps, 5), dtype=torch.float64, device=dev) if collect_stats else None)
+            self._step_sums = (torch.zeros(lead + (self.n_steps, 5), dtype=torch.float64, device=dev) if collect_stats else None)
             self._step_sums_valid = np.zeros(self.n_steps, dtype=bool)     # steps whose folded sums (above) are current
             # steps whose moments THIS engine holds (wave records written by its launches, or records / folded sums restored
             # from a checkpoint): only these are saved as valid by state_dict("summaries")
@@ -241,10 +280,11 @@ class EnsembleEngine(CheckpointMixin):
                 self.obs = torch.from_numpy(np.array(table, order="C")).to(dev)      # uploaded once
                 self.misfit = torch.zeros((3, N), dtype=torch.float64, device=dev)
         if chunk_members == "auto":
-            chunk_members = self.auto_chunk(N, SP, G, dtype)
+            chunk_members = self.auto_chunk(N, SP, G, dtype, n_scenarios=Sc)
         self.chunk_members = int(chunk_members or 0) // 256 * 256
         if per_step_streams == "auto":
-            t_step = min(N, self.chunk_members or N) * self._w * (2 * SP + 4 * G + 7) / HBM_STREAM_BYTES_PER_S
+            t_step = (min(N, self.chunk_members or N) * self._w * (Sc * (2 * SP + G + 5) + 3 * G + 2)
+                      / HBM_STREAM_BYTES_PER_S)
             per_step_streams = 2 if t_step >= PER_STEP_SPLIT_MIN_S else 1
         self.per_step_streams = max(1, int(per_step_streams))
         if fused_span not in ("auto", None) and int(fused_span) < 1:
@@ -256,8 +296,8 @@ class EnsembleEngine(CheckpointMixin):
         # run(..., join=False) left work nobody has waited for: the streams of THAT run ([its main, its side streams]) — join()
         # waits for exactly these, whichever stream the consumer is on; None = nothing outstanding
         self._ps_unjoined = None
-        self._R0 = None if R0 is None else np.asarray(R0, dtype=np.float64).reshape(SP, N)
-        self._S0 = None if S0 is None else np.asarray(S0, dtype=np.float64).reshape(2, N)
+        self._R0 = None if R0 is None else self._initial_state(R0, SP, "R0")
+        self._S0 = None if S0 is None else self._initial_state(S0, 2, "S0")
         self.t_next = 0                     # first step not yet run (bookkeeping for checkpoints)
         self.last_mode = None               # the mode the last run() used after resolving 'auto'
         self.reset_state()
@@ -265,13 +305,39 @@ class EnsembleEngine(CheckpointMixin):
         with torch.cuda.device(self.device):
             self.probe_streams()            # construction is synchronous anyway: the one place the probe may clock streams
 
+    def _initial_state(self, x, K, name):
+        """R0 / S0 as a host fp64 array: [K, N], or with the scenario axis [S, K, N] (a [K, N] state broadcast to every
+        scenario)."""
+        if isinstance(x, torch.Tensor):
+            x = x.detach().double().cpu().numpy()
+        x = np.asarray(x, dtype=np.float64)
+        N = self.n_members
+        if not self.scenario_axis:
+            return x.reshape(K, N)
+        if x.size == K * N:
+            return np.broadcast_to(x.reshape(1, K, N), (self.n_scenarios, K, N)).copy()
+        if x.shape != (self.n_scenarios, K, N):
+            raise ValueError(f"{name}: shape {x.shape}, want [{K}, {N}] or [{self.n_scenarios}, {K}, {N}]")
+        return x
+
+    def _scen(self, scenario):
+        """The scenario index a per-scenario accessor reads: required with the scenario axis, ignored without it."""
+        if not self.scenario_axis:
+            return None
+        if scenario is None:
+            raise ValueError(f"this engine runs {self.n_scenarios} scenarios: pass scenario= (0..{self.n_scenarios - 1})")
+        s = int(scenario)
+        if not 0 <= s < self.n_scenarios:
+            raise ValueError(f"scenario {scenario}: the engine has scenarios 0..{self.n_scenarios - 1}")
+        return s
+
     @staticmethod
-    def auto_chunk(n_members, sum_pools, n_gas, dtype, cache_bytes=INFINITY_CACHE_BYTES):
+    def auto_chunk(n_members, sum_pools, n_gas, dtype, cache_bytes=INFINITY_CACHE_BYTES, n_scenarios=1):
         """Members per chunk of the chunk-major schedule: the fewest EVEN chunks whose state + parameter rows take at most
         CHUNK_CACHE_SHARE of the Infinity Cache each (a multiple of 256 members); 0 = do not chunk: the ensemble's rows fit the
-        cache by themselves."""
+        cache by themselves.  With n_scenarios, every member carries that many copies of the state rows."""
         w = 8 if dtype == torch.float64 else 4
-        rows_bytes = n_members * w * (sum_pools + 2 + 3 * n_gas + 2)
+        rows_bytes = n_members * w * (n_scenarios * (sum_pools + 2) + 3 * n_gas + 2)
         if rows_bytes <= cache_bytes:
             return 0
         k = -(-rows_bytes // int(CHUNK_CACHE_SHARE * cache_bytes))
@@ -288,7 +354,7 @@ class EnsembleEngine(CheckpointMixin):
         packs = self.dtype == torch.float32 and self.n_members % 2 == 0 and (self.observations is None or self.pools == [4, 1, 1])
         per_wave = 128 if packs else 64
         slots = 16 * torch.cuda.get_device_properties(self.device).multi_processor_count       # 4 waves on each of a CU's 4 SIMDs
-        rounds = -(-self.n_members // per_wave) / slots
+        rounds = -(-self.n_members // per_wave) * self.n_scenarios / slots          # the scenarios are rows of the grid
         # (below a quarter of a round the launches themselves weigh more than the tail: 10k members lose 3 %)
         return min(FUSED_SPAN_STEPS, n_steps) if FUSED_SPAN_MIN_ROUNDS <= rounds <= FUSED_SPAN_MAX_ROUNDS else n_steps
 
@@ -297,13 +363,14 @@ class EnsembleEngine(CheckpointMixin):
         hides the dependent-launch boundary (at least three boundaries' worth: ~160k three-gas fp64 members), otherwise —
         the ensemble is launch-bound, not bandwidth-bound — KSTEPS_LAUNCH_BOUND: state and parameters cross HBM once per
         launch, so nothing is gained by a shorter span (round 4 scaled K with the ensemble and ran 110k members at K = 2)."""
-        t_step = self.n_members * self.bytes_per_member_step("per_step") / HBM_STREAM_BYTES_PER_S
+        t_step = self.n_members * self.n_scenarios * self.bytes_per_member_step("per_step") / HBM_STREAM_BYTES_PER_S
         return 1 if t_step >= 3.0 * LAUNCH_BOUNDARY_S else min(KSTEPS_LAUNCH_BOUND, self.n_steps)
 
     def small_form(self):
         """Lanes per member mode='small' would run with now (4 or 1); 0 = the small-ensemble kernel does not apply: a run that
         wants in-loop histograms or the concentration-driven form."""
-        if not self.small_widest or self.T_hist is not None or self.concentration_driven or self.observations is not None:
+        if (not self.small_widest or self.T_hist is not None or self.concentration_driven or self.observations is not None
+                or self.scenario_axis):
             return 0
         if self.compensated:                                     # fiveeq_run_small_comp_f32: one member per lane, every layout
             return 1 if self.small_lanes in ("auto", 1) else 0
@@ -366,7 +433,8 @@ class EnsembleEngine(CheckpointMixin):
     def _wave_stats(self):
         """The per-wave record buffer of the in-kernel statistics, allocated by the first launch that writes it."""
         if self.collect_stats and self.T_stats is None:
-            self.T_stats = torch.zeros((self.n_waves, self.n_steps, 4), dtype=torch.float64, device=self.device)
+            lead = (self.n_scenarios,) if self.scenario_axis else ()
+            self.T_stats = torch.zeros(lead + (self.n_waves, self.n_steps, 4), dtype=torch.float64, device=self.device)
         return self.T_stats
 
     # -- launches ----------------------------------------------------------------------
@@ -403,6 +471,11 @@ class EnsembleEngine(CheckpointMixin):
         return self._fn("run_obs")(*self._run_args(t_begin, t_end, m0, n), *self._obs_args(m0), form, int(k_steps),
                                    self._stream(stream))
 
+    def _run_scen(self, t_begin, t_end, stream, form, k_steps=0, m0=0, n=None):
+        """fiveeq_run_scen_*: members [m0, m0 + n) under every scenario (the scenario strides derive from ld = N)."""
+        a = self._run_args(t_begin, t_end, m0, n)
+        return self._fn("run_scen")(*a[:3], self.n_scenarios, *a[3:], form, int(k_steps), self._stream(stream))
+
     def _run_inverse(self, t_begin, t_end, stream):
         a = self._run_args(t_begin, t_end)
         return self._fn("run_inverse")(*a[:11], self._ptr(self.cumE), *a[11:], self._stream(stream))
@@ -419,6 +492,8 @@ class EnsembleEngine(CheckpointMixin):
         with torch.cuda.device(self.device):
             if self.concentration_driven:
                 rc = self._run_inverse(t, t + 1, stream)
+            elif self.scenario_axis:
+                rc = self._run_scen(t, t + 1, stream, _capi.FORM_PER_STEP)
             elif self.observations is not None:
                 rc = self._run_obs(t, t + 1, stream, _capi.FORM_PER_STEP)
             else:
@@ -455,6 +530,8 @@ class EnsembleEngine(CheckpointMixin):
         if self.compensated and mode not in ("fused", "ksteps", "small"):
             raise ValueError(f"mode {mode!r} has no compensated form: the compensation words live in registers, so only the "
                              "time-fused kernel ('fused', 'ksteps') and the small-ensemble kernel ('small', one lane) carry them")
+        if self.scenario_axis and mode == "small":
+            raise ValueError("mode 'small' has no scenario form: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'")
         if self.observations is not None and mode == "small":
             raise ValueError("mode 'small' does not carry the misfit of observations=: use 'per_step', 'graph', 'fused', "
                              "'ksteps' or 'auto'")
@@ -480,6 +557,10 @@ class EnsembleEngine(CheckpointMixin):
                         max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
                 rc = self.lib.fiveeq_run_fused_comp_f32(*self._run_args(t_begin, t_end), span, 0.0, 1.0, 1, None, 0,
                                                         self._stream(stream))
+            elif self.scenario_axis and mode in ("fused", "ksteps"):
+                k = (self.fused_span_steps(t_end - t_begin) if mode == "fused" else
+                     max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
+                rc = self._run_scen(t_begin, t_end, stream, _capi.FORM_FUSED, k)
             elif self.observations is not None and mode in ("fused", "ksteps"):
                 k = (self.fused_span_steps(t_end - t_begin) if mode == "fused" else
                      max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
@@ -610,6 +691,10 @@ class EnsembleEngine(CheckpointMixin):
         kernel also writes every member's histogram bin into a ring strip [S, N] of uint16 (row t mod S); after S steps each
         part counts its strip into T_hist (fiveeq_hist_bins) on its own stream — 2 bytes written + 2 read per member-step on
         top of the step's 124 / 248."""
+        if self.scenario_axis:
+            block = PER_STEP_BLOCK if self.per_step_streams > 1 else None
+            return self._per_step_schedule(t_begin, t_end, stream, join, block, lambda t, t1, m0, n, s: self._run_scen(
+                t, t1, s, _capi.FORM_PER_STEP, 0, m0, n))
         if self.observations is not None:
             block = PER_STEP_BLOCK if self.per_step_streams > 1 else None
             return self._per_step_schedule(t_begin, t_end, stream, join, block, lambda t, t1, m0, n, s: self._run_obs(
@@ -690,6 +775,9 @@ class EnsembleEngine(CheckpointMixin):
             plans = []
             self._wave_stats()
             fn = self._fn("plan_create" if self.observations is None else "plan_create_obs")
+            if self.scenario_axis:
+                scen = self._fn("plan_create_scen")
+                fn = lambda *a: scen(*a[:3], self.n_scenarios, *a[3:])       # noqa: E731
             with torch.cuda.device(self.device):
                 for m0, n, _ in self.per_step_launches():
                     plan = ctypes.c_void_p()
@@ -712,31 +800,36 @@ class EnsembleEngine(CheckpointMixin):
             pass
 
     # -- on-device summary statistics -----------------------------------------------------
-    def stats_sums(self, t_begin=0, t_end=None):
+    def stats_sums(self, t_begin=0, t_end=None, scenario=None):
         """[n, 5] fp64 per step: (count, sum T, sum T^2, min T, max T) over this shard's members — folded over the
         per-wave records the kernels wrote (or, for steps a checkpoint's summaries brought, as folded by the saver).
-        Additive across shards (fiveeqscm_amd.distributed.reduce_stats)."""
+        Additive across shards (fiveeqscm_amd.distributed.reduce_stats).  scenario: which scenario's moments (required
+        with the scenario axis)."""
         if not self.collect_stats:
             raise RuntimeError("engine was built with collect_stats=False")
+        sc = self._scen(scenario)
         if self._ps_unjoined:
             self.join()
         t_end = self.n_steps if t_end is None else int(t_end)
+        step_sums = self._step_sums if sc is None else self._step_sums[sc]
         valid = self._step_sums_valid[t_begin:t_end]
         if valid.all():                                          # everything came folded from a checkpoint
-            return self._step_sums[t_begin:t_end].clone()
-        s = self._wave_stats()[:, t_begin:t_end]                 # [W, n, 4]
+            return step_sums[t_begin:t_end].clone()
+        recs = self._wave_stats()
+        s = (recs if sc is None else recs[sc])[:, t_begin:t_end]     # [W, n, 4]
         cnt = torch.full((s.shape[1],), float(self.n_members), dtype=torch.float64, device=s.device)
         out = torch.stack([cnt, s[:, :, 0].sum(0), s[:, :, 1].sum(0), s[:, :, 2].min(0).values,
                            s[:, :, 3].max(0).values], dim=1)
         if valid.any():
             pick = torch.from_numpy(valid).to(out.device)
-            out[pick] = self._step_sums[t_begin:t_end][pick]
+            out[pick] = step_sums[t_begin:t_end][pick]
         return out
 
-    def stats(self, t_begin=0, t_end=None):
-        """dict of per-step ensemble moments of T over this shard: mean, var (population), min, max."""
+    def stats(self, t_begin=0, t_end=None, scenario=None):
+        """dict of per-step ensemble moments of T over this shard: mean, var (population), min, max (of `scenario` with the
+        scenario axis)."""
         from .distributed import moments_from_sums
-        return moments_from_sums(self.stats_sums(t_begin, t_end))
+        return moments_from_sums(self.stats_sums(t_begin, t_end, scenario=scenario))
 
     def chi2(self):
         """[N] fp64 on the device: each member's score against the observations, chi2 = V - 2 A U + A^2 P
@@ -752,7 +845,8 @@ class EnsembleEngine(CheckpointMixin):
         from .constrain import chi2_from_misfit
         return chi2_from_misfit(self.misfit, self.observations.P)
 
-    def gather_summary(self, steps, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, gas=None, accepted=None):
+    def gather_summary(self, steps, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, gas=None, accepted=None,
+                       scenario=None):
         """End-of-run summary of T — or, with `gas` = a gas index, of that gas's concentration C — at the stored `steps` over
         ALL members of all ranks (collective over `group`; see distributed.gather_summary): merged moments on every rank,
         exact percentiles on rank `dst`.  With collect_stats the moments of T come from the records the kernels wrote while
@@ -760,8 +854,10 @@ class EnsembleEngine(CheckpointMixin):
         accepted: a boolean [N] mask of this shard's members (constrain.accept_*): the summary is then over the ACCEPTED
         members of all ranks only — the selected rows are compacted on the device and go through the same passes (the
         in-kernel moment records cover every member, so they are not used); `count` is the global number accepted.  A rank
-        with no accepted member still takes part in every collective."""
+        with no accepted member still takes part in every collective.  scenario: the scenario summarised (required with
+        the scenario axis; `accepted` masks the members of that scenario)."""
         from .distributed import gather_summary
+        sc = self._scen(scenario)
         stored = self.T if gas is None else self.C
         if stored is None or self.concentration_driven and gas is not None:
             raise RuntimeError(f"no stored {'T' if gas is None else 'C'} rows to summarise")
@@ -774,7 +870,9 @@ class EnsembleEngine(CheckpointMixin):
         if missing:
             raise ValueError(f"steps {missing} are not stored (out_steps)")
         picked = [row_of[int(t)] for t in steps]
-        rows = self.T[picked] if gas is None else self.C[picked, int(gas)]
+        T_rows = self.T if sc is None else self.T[sc]
+        C_rows = None if self.C is None else (self.C if sc is None else self.C[sc])
+        rows = T_rows[picked] if gas is None else C_rows[picked, int(gas)]
         if accepted is not None:
             mask = torch.as_tensor(accepted, device=self.device)
             if mask.dtype != torch.bool or tuple(mask.shape) != (self.n_members,):
@@ -782,18 +880,21 @@ class EnsembleEngine(CheckpointMixin):
             return gather_summary(rows[:, mask].contiguous(), percentiles, dst=dst, group=group, stats=stats)
         sums = None
         if gas is None and self.collect_stats and all(self._stats_have[int(t)] for t in steps):   # else: the moments pass over the rows
-            sums = torch.cat([self.stats_sums(int(t), int(t) + 1) for t in steps])[:, 1:5].contiguous()
+            sums = torch.cat([self.stats_sums(int(t), int(t) + 1, scenario=sc) for t in steps])[:, 1:5].contiguous()
         return gather_summary(rows, percentiles, dst=dst, group=group, stats=stats, local_sums=sums)
 
-    def T_histogram(self, lo, hi, n_bins=4096, rows=None, out=None, stream=None):
+    def T_histogram(self, lo, hi, n_bins=4096, rows=None, out=None, stream=None, scenario=None):
         """Fixed-bin histograms of the stored T rows on the device: int64 tensor [n_rows, n_bins]
         (bin b counts lo + b w <= T < lo + (b+1) w; outliers land in the edge bins).  `out` lets
-        several calls / shards accumulate; percentiles: distributed.histogram_percentiles."""
+        several calls / shards accumulate; percentiles: distributed.histogram_percentiles.  scenario: whose rows (required
+        with the scenario axis)."""
         if self.T is None:
             raise RuntimeError("no stored T rows to histogram")
+        sc = self._scen(scenario)
         if self._ps_unjoined:
             self.join(stream)
-        x = self.T if rows is None else self.T[rows].contiguous()
+        T_rows = self.T if sc is None else self.T[sc]
+        x = T_rows if rows is None else T_rows[rows].contiguous()
         k = x.shape[0]
         if out is None:
             out = torch.zeros((k, int(n_bins)), dtype=torch.int64, device=self.device)
@@ -822,7 +923,9 @@ class EnsembleEngine(CheckpointMixin):
         ksteps:          w (G + 1) + w (2 SP + 3 G + 6) / k_steps  (state + parameters once per k_steps).
         Statistics add one 32-byte record per wave of 64 members and step; with `hist=` the bin ring adds 2 B written + 2 B
         read per member-step.  With `observations=` the misfit accumulators add, per_step: 48 B (3 fp64 read + written) per
-        member and step of the observation window, averaged over the run's steps; the fused forms: 48 B per member and launch."""
+        member and step of the observation window, averaged over the run's steps; the fused forms: 48 B per member and launch.
+        With the scenario axis the count is per MEMBER-SCENARIO-step: per_step reads the parameter rows once for all S
+        scenarios, w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / S."""
         w, G, SP = self._w, self.n_gas, self.sum_pools
         out = ((G if self.C is not None else 0) + 1) * self.n_rows / self.n_steps      # stored rows only
         extra = (32.0 / 64.0) if self.collect_stats else 0.0
@@ -831,6 +934,8 @@ class EnsembleEngine(CheckpointMixin):
             tab = self.observations.table
             if mode == "per_step":
                 extra += 48.0 * np.count_nonzero((tab[:, 1] != 0) | (tab[:, 2] != 0)) / self.n_steps
+        if mode == "per_step" and self.scenario_axis:
+            return w * (2 * SP + 4 + out) + w * (3 * G + 2) / self.n_scenarios + extra
         if mode == "per_step":
             return w * (2 * SP + 3 * G + 6 + out) + extra + ring
         if mode == "fused":

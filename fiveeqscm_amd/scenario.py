@@ -173,3 +173,72 @@ def write_observations_csv(path, years, T, sigma, comment=None):
         w.writerow(["YEAR", "T", "SIGMA"])
         for y, t, s in zip(years, T, sigma):
             w.writerow([repr(float(y)) if y != int(y) else str(int(y)), repr(float(t)), repr(float(s))])
+
+
+def read_emissions_csvs(paths, gases=("CO2", "CH4", "N2O")):
+    """Several scenario files (read_emissions_csv each) as one scenario set for an engine with the scenario axis:
+    (years [n], emissions [S, n, len(gases)]).  Every file must cover the same years and carry every requested gas;
+    ValueError names the first file that does not."""
+    paths = list(paths)
+    if not paths:
+        raise ValueError("read_emissions_csvs: no files")
+    years, E = read_emissions_csv(paths[0], gases)
+    out = [E]
+    for p in paths[1:]:
+        y, e = read_emissions_csv(p, gases)
+        if y.shape != years.shape or not np.array_equal(y, years):
+            raise ValueError(f"{p}: years {y[0]:g}..{y[-1]:g} ({y.size}) differ from {paths[0]} "
+                             f"({years[0]:g}..{years[-1]:g}, {years.size})")
+        out.append(e)
+    return years, np.stack(out)
+
+
+def write_scenario_summary_csv(path, names, years, summaries, percentiles=(5.0, 50.0, 95.0), quantity="T", unit="K"):
+    """Per-scenario end-of-run summaries in LONG format: one row per (scenario, year) — SCENARIO, YEAR, COUNT, MEAN, STD,
+    MIN, P05, P50, P95, MAX — `summaries[i]` being the root-rank dict of EnsembleEngine.gather_summary(..., scenario=i) of
+    scenario `names[i]` (the columns of write_summary_csv).  Floats are repr-exact: read_scenario_summary_csv returns them bit
+    for bit."""
+    names = [str(n) for n in names]
+    if len(names) != len(summaries):
+        raise ValueError(f"{len(names)} scenario names for {len(summaries)} summaries")
+    years = np.asarray(years, dtype=np.float64).reshape(-1)
+    pnames = ["P%s" % (("%02d" % p) if float(p).is_integer() else repr(float(p))) for p in percentiles]
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow([f"fiveeqscm_amd scenario summary of {quantity} ({unit})"])
+        w.writerow(["SCENARIO", "YEAR", "COUNT", "MEAN", "STD", "MIN"] + pnames + ["MAX"])
+        for name, summary in zip(names, summaries):
+            cols = {k: np.asarray(summary[k], dtype=np.float64).reshape(-1) for k in ("count", "mean", "var", "min", "max")}
+            if summary.get("percentiles") is None:
+                raise ValueError(f"scenario {name}: the summary holds no percentiles (they exist on the root rank only)")
+            pct = np.asarray(summary["percentiles"], dtype=np.float64).reshape(years.size, -1)
+            if pct.shape[1] != len(percentiles) or any(v.size != years.size for v in cols.values()):
+                raise ValueError(f"scenario {name}: summary of {cols['mean'].size} rows x {pct.shape[1]} percentiles does not "
+                                 f"match {years.size} years x {len(percentiles)} percentiles")
+            for k, y in enumerate(years):
+                w.writerow([name, int(y) if y == int(y) else repr(float(y)), int(cols["count"][k]),
+                            repr(float(cols["mean"][k])), repr(float(np.sqrt(cols["var"][k]))), repr(float(cols["min"][k]))]
+                           + [repr(float(v)) for v in pct[k]] + [repr(float(cols["max"][k]))])
+
+
+def read_scenario_summary_csv(path):
+    """{scenario name: (years [K], dict of columns)} of a file written by write_scenario_summary_csv (the columns as
+    read_summary_csv returns them), in file order."""
+    with open(path, newline="") as fh:
+        rows = [row for row in csv.reader(fh) if row]
+    header = next((r for r in rows if r and r[0] == "SCENARIO"), None)
+    if header is None:
+        raise ValueError(f"{path}: no SCENARIO header row")
+    out = {}
+    for r in rows[rows.index(header) + 1:]:
+        out.setdefault(r[0], []).append([float(c) for c in r[1:]])
+    cols = header[1:]
+    pcols = [i for i, name in enumerate(cols) if name.startswith("P")]
+    res = {}
+    for name, data in out.items():
+        data = np.array(data, dtype=np.float64).reshape(-1, len(cols))
+        d = {c.lower(): data[:, i] for i, c in enumerate(cols) if not c.startswith("P") and c != "YEAR"}
+        d["levels"] = [float(cols[i][1:]) for i in pcols]
+        d["percentiles"] = data[:, pcols]
+        res[name] = (data[:, 0], d)
+    return res

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define FIVEEQ_ABI_VERSION   12
+#define FIVEEQ_ABI_VERSION   13
 #define FIVEEQ_MAX_GAS       3
 #define FIVEEQ_MAX_POOLS     4
 #define FIVEEQ_N_BOX         2
@@ -249,6 +249,44 @@ int fiveeq_plan_create_obs_f32(const fiveeq_model *model, int64_t n_members, int
                                const double *obs, double *misfit, void **plan_out);
 /* new — 1 if the pool layout has the misfit forms above, else 0 */
 int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t *n_pools);
+
+/* SCENARIOS — one parameter ensemble under several emission scenarios at once (new, ABI v13).  Every parameter member m is
+ * advanced under each of n_scen scenarios s, and member-scenario (m, s) is bit for bit member m of fiveeq_run_* /
+ * fiveeq_run_ksteps_* run with scenario s's drive table: the kernels call the same model step.  Members and scenarios never
+ * interact.  Layouts (every scenario stride derives from ld, so a member sub-range [m0, m0 + n) is a pointer offset):
+ *   drive  dev [n_scen][n_steps][8]       one drive table per scenario (column 7, the row map, the same in each)
+ *   r, q   dev [3G][ld], [2][ld]          SHARED by the scenarios
+ *   R, S   dev [n_scen][SP][ld], [n_scen][2][ld]
+ *   C_traj dev [n_scen][n_rows][G][ld] or NULL;   T_traj dev [n_scen][n_rows][ld] or NULL
+ *   T_stats dev [n_scen][fiveeq_stats_waves(ld)][n_steps][4] or NULL
+ *   form FIVEEQ_FORM_PER_STEP: one launch per step; a lane loads its member's 3G + 2 parameter rows ONCE and advances the
+ *       member under all n_scen scenarios (the drive records are read as wave-uniform scalar loads), so a member-scenario-
+ *       step moves w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / n_scen bytes;
+ *   form FIVEEQ_FORM_FUSED: the time-fused kernel over spans of k_steps (0 = one launch for the range), one grid row of
+ *       workgroups per scenario (each stages its own scenario's drive chunk).
+ * Every pool layout.  FIVEEQ_E_INVALID for n_scen outside [1, fiveeq_max_scenarios()], a NULL drive or state pointer, an
+ * unknown form, k_steps < 0 or a step range outside [0, n_steps) — before anything is launched. */
+int fiveeq_run_scen_f64(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                        const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                        const double *r, const double *q, double *R, double *S,
+                        double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                        int32_t form, int32_t k_steps, void *stream);
+int fiveeq_run_scen_f32(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                        const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                        const float *r, const float *q, float *R, float *S,
+                        float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                        int32_t form, int32_t k_steps, void *stream);
+/* new — fiveeq_plan_create_* of the per-step form above: the launches of [t_begin, t_end) captured once */
+int fiveeq_plan_create_scen_f64(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                                const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                const double *r, const double *q, double *R, double *S,
+                                double *C_traj, double *T_traj, int32_t n_rows, double *T_stats, void **plan_out);
+int fiveeq_plan_create_scen_f32(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                                const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                const float *r, const float *q, float *R, float *S,
+                                float *C_traj, float *T_traj, int32_t n_rows, double *T_stats, void **plan_out);
+/* new — the largest n_scen the scenario forms take (64) */
+int32_t fiveeq_max_scenarios(void);
 
 /* SMALL ENSEMBLES (BASELINE configs[1], 10k CO2-only members): the time-fused step with ONE MEMBER
  * SPREAD OVER SEVERAL LANES.  An ensemble of fewer waves than the chip has SIMDs (1024) is bound by the number of
