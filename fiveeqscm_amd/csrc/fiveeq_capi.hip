@@ -137,6 +137,30 @@ KModel<T> make_kmodel(const fiveeq_model* m) {
 // >> 256 CUs); workgroup b owns the same members in every launch.
 int64_t member_blocks(int64_t n) { return (n + FIVEEQ_BLOCK - 1) / FIVEEQ_BLOCK; }
 
+// the workgroups of one launch over n members, per_block of them per workgroup
+int grid_blocks(int64_t n, int64_t per_block, unsigned& blocks) {
+    const int64_t b = (n + per_block - 1) / per_block;
+    if (b > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
+    blocks = (unsigned)b;
+    return FIVEEQ_OK;
+}
+
+// the bin-index ring of the streamed histograms (step_kernel / fused_kernel <..., BINS = true>)
+struct BinRing {
+    unsigned short* ring = nullptr;
+    int ring_rows = 0;
+    double lo = 0.0, inv_w = 0.0;
+    int n_bins = 0;
+};
+
+// the misfit accumulators of the constrained forms (step_kernel / fused_kernel <..., MISFIT = true>): obs [n_steps][4] and
+// misfit [3][ld], fp64 both
+struct MisfitRows {
+    const double* obs = nullptr;
+    double* misfit = nullptr;
+};
+
+// everything one C-ABI call hands its launches: filled by make_args() and the checker of each optional feature
 template <typename T>
 struct RunArgs {
     KModel<T> km;
@@ -148,17 +172,14 @@ struct RunArgs {
     T *R, *S, *C_traj, *T_traj;
     int n_rows;
     int n_steps;
+    int t_begin, t_end;
     double* stats;
     int packing;                 // the fp32 packing switch as this call found it
     bool stream_rows;            // the per-step launches of this call take the STREAMED (non-temporal) row form
-};
-
-// the bin-index ring of the streamed histograms (fused_kernel<..., BINS = true>)
-struct BinRing {
-    unsigned short* ring = nullptr;
-    int ring_rows = 0;
-    double lo = 0.0, inv_w = 0.0;
-    int n_bins = 0;
+    int n_scen;                  // scenarios (the scenario forms; 1 = no scenario axis)
+    T* cumE = nullptr;           // the inverse form's cumulative emissions
+    BinRing br;                  // the histogram forms' ring (else none)
+    MisfitRows mf;               // the constrained forms' accumulators (else none)
 };
 
 // ---- packed fp32 lanes: two members per lane (fiveeq_device.hpp, "Lane value types") ----------------------------
@@ -172,8 +193,9 @@ std::atomic<int> g_f32_packing{1};
 
 // ---- cache policy of the per-step kernel's state and parameter rows (fiveeq_device.hpp, step_kernel<..., NT>) --------------
 // STREAMED (non-temporal) pays exactly when the rows of this launch cannot be in the Infinity Cache at the next step:
-//   * the launch's own rows fill it: n members x (SP + 2 + 3G + 2) words >= the cache — false for the chunks of a chunk-major
-//     schedule (the engine sizes them to fit), true for an unchunked multi-million-member launch; and
+//   * the launch's own rows fill it: n members x (S (SP + 2) + 3G + 2) words >= the cache, for S scenarios (1 without the
+//     scenario axis: each scenario carries its own state rows, the parameter rows are shared) — false for the chunks of a
+//     chunk-major schedule (the engine sizes them to fit), true for an unchunked multi-million-member launch; and
 //   * the ensemble they are a part of (row length ld: the halves of a two-stream split share the cache) is at least twice
 //     the cache — between one and two cache sizes the default policy still hits often enough to win (2M fp64 members, 304 MB:
 //     +13 % streamed; 4M: -9 %; profiles/r05/step_row_policy_ab.txt).
@@ -182,9 +204,9 @@ std::atomic<int> g_f32_packing{1};
 constexpr int64_t INFINITY_CACHE_BYTES = (int64_t)256 << 20;       // MI355X (MI355X_MICROARCH.md)
 std::atomic<int> g_row_policy{FIVEEQ_ROWS_AUTO};
 
-bool rows_streamed(int policy, int n_gas, int sum_pools, int64_t n, int64_t ld, int word) {
+bool rows_streamed(int policy, int n_gas, int sum_pools, int n_scen, int64_t n, int64_t ld, int word) {
     if (policy != FIVEEQ_ROWS_AUTO) return policy == FIVEEQ_ROWS_STREAMED;
-    const int64_t per_member = (int64_t)word * (sum_pools + 2 + 3 * n_gas + 2);
+    const int64_t per_member = (int64_t)word * ((int64_t)n_scen * (sum_pools + 2) + 3 * n_gas + 2);
     return n * per_member >= INFINITY_CACHE_BYTES && ld * per_member >= 2 * INFINITY_CACHE_BYTES;
 }
 
@@ -204,12 +226,6 @@ struct LaneOf<float> {
     }
 };
 
-// the misfit accumulators of the constrained forms (step_kernel / fused_kernel <..., MISFIT = true>): obs [n_steps][4] and
-// misfit [3][ld], fp64 both
-struct MisfitRows {
-    const double* obs = nullptr;
-    double* misfit = nullptr;
-};
 // the layouts with MISFIT instantiations: a lone 4-pool gas (CO2-only) and 4 + 1 + 1 (CO2, CH4, N2O)
 constexpr bool misfit_layout(int p0, int p1, int p2) { return (p0 == 4 && p1 == 0 && p2 == 0) || (p0 == 4 && p1 == 1 && p2 == 1); }
 // ... and the PACKED fp32 fused kernel carries it for 4 + 1 + 1 only.  For {4} the two members' accumulators (12 KiB of LDS per
@@ -217,40 +233,44 @@ constexpr bool misfit_layout(int p0, int p1, int p2) { return (p0 == 4 && p1 == 
 // fp32 fused kernel, which keeps its plain counterpart's 7 waves (same bits either way: packed lanes mirror the scalar ones).
 constexpr bool misfit_packed_fused(int p0, int p1, int p2) { return p0 == 4 && p1 == 1 && p2 == 1; }
 
-template <typename T, bool BINS = false, bool MISFIT = false>
-int launch_step(const RunArgs<T>& a, int t, hipStream_t st, const BinRing& br = BinRing(), const MisfitRows& mf = MisfitRows()) {
+// ---- the two launchers: one step of the per-step kernel, one span [t_begin, t_end) of the time-fused kernel ----------------
+// The compile-time flags pick the kernel family; packing, the row policy and the pool layout are decided here per launch.
+// SCEN: the scenario axis (step_scen_kernel; the fused kernel with the scenario as blockIdx.y).
+template <typename T, bool BINS = false, bool MISFIT = false, bool SCEN = false>
+int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
-    static_assert(!(BINS && MISFIT), "no misfit in the histogram-ring form");
-    const bool packed = LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)br.ring) & 3) == 0);
-    const int64_t per_block = (int64_t)FIVEEQ_STEP_BLOCK * (packed ? 2 : 1);
-    const int64_t blocks = (a.n + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
-    const dim3 grid((unsigned)blocks), block(FIVEEQ_STEP_BLOCK);
+    static_assert(BINS + MISFIT + SCEN <= 1, "the histogram ring, the misfit and the scenario axis are separate forms");
+    const bool packed = LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0);
+    unsigned blocks;
+    if (int rc = grid_blocks(a.n, (int64_t)FIVEEQ_STEP_BLOCK * (packed ? 2 : 1), blocks)) return rc;
+    const dim3 grid(blocks), block(FIVEEQ_STEP_BLOCK);
     switch (a.code) {
-#define FIVEEQ_STEP_LAUNCH(V, p0, p1, p2, NT, MF)                                                                              \
-    hipLaunchKernelGGL((step_kernel<V, p0, p1, p2, BINS, NT, MF>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, \
-                       a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w,     \
-                       br.n_bins, mf.obs, mf.misfit)
+#define FIVEEQ_STEP_LAUNCH(V, p0, p1, p2, NT)                                                                                     \
+    do {                                                                                                                          \
+        if constexpr (SCEN)                                                                                                       \
+            hipLaunchKernelGGL((step_scen_kernel<V, p0, p1, p2, NT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, \
+                               a.n_scen, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats);                              \
+        else                                                                                                                      \
+            hipLaunchKernelGGL((step_kernel<V, p0, p1, p2, BINS, NT, MISFIT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t,   \
+                               a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.br.ring, a.br.ring_rows,   \
+                               a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit);                                          \
+    } while (0)
 #define X(p0, p1, p2)                                                                             \
     case (p0) * 100 + (p1) * 10 + (p2):                                                           \
-        if constexpr (MISFIT) {           /* default row policy only (the engine schedules such runs chunk-major) */ \
-            if constexpr (misfit_layout(p0, p1, p2)) {                                            \
-                if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, false, true);                       \
-                else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, false, true);                              \
-                break;                                                                            \
-            } else {                                                                              \
-                return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);     \
+        if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                     \
+            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);         \
+        } else {                                                                                  \
+            /* the streamed row form: plain and scenario launches only (the engine schedules misfit runs chunk-major) */ \
+            if constexpr (!BINS && !MISFIT) {                                                     \
+                if (a.stream_rows) {                                                              \
+                    if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, true);                          \
+                    else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, true);                                 \
+                    break;                                                                        \
+                }                                                                                 \
             }                                                                                     \
+            if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, false);                                 \
+            else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, false);                                        \
         }                                                                                         \
-        if constexpr (!BINS) {            /* the streamed row form: plain per-step launches only */ \
-            if (a.stream_rows) {                                                                  \
-                if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, true, false);                       \
-                else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, true, false);                              \
-                break;                                                                            \
-            }                                                                                     \
-        }                                                                                         \
-        if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, false, false);                              \
-        else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, false, false);                                     \
         break;
         FIVEEQ_LAYOUTS(X)
 #undef X
@@ -262,41 +282,41 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st, const BinRing& br = 
     return FIVEEQ_OK;
 }
 
-template <typename T, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false>
-int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, T* cumE, hipStream_t st, const BinRing& br = BinRing(),
-                 const MisfitRows& mf = MisfitRows()) {
+template <typename T, bool INV = false, bool BINS = false, bool COMP = false, bool MISFIT = false, bool SCEN = false>
+int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
     static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
+    static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
     constexpr bool HAS_PACKED = !INV && !std::is_same<P, T>::value;     // the inverse form has no packed instantiation
     // packed lanes store two 2-byte bin indices as one 4-byte word: the ring rows must be 4-byte aligned too; the misfit forms
     // have a packed instantiation for some layouts only (misfit_packed_fused) — decided HERE, before the grid is sized for it
     const bool packed = HAS_PACKED && (!MISFIT || misfit_packed_fused(a.code / 100, a.code / 10 % 10, a.code % 10)) &&
-                        LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)br.ring) & 3) == 0);
-    const int64_t blocks = member_blocks(packed ? (a.n + 1) / 2 : a.n);
-    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
-    const dim3 grid((unsigned)blocks), block(FIVEEQ_BLOCK);
+                        LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0);
+    unsigned blocks;
+    if (int rc = grid_blocks(a.n, (int64_t)FIVEEQ_BLOCK * (packed ? 2 : 1), blocks)) return rc;
+    const dim3 grid(blocks, (unsigned)a.n_scen), block(FIVEEQ_BLOCK);     // the scenarios are rows of the grid
     switch (a.code) {
+#define FIVEEQ_FUSED_LAUNCH(V, p0, p1, p2, I)                                                                                    \
+    hipLaunchKernelGGL((fused_kernel<V, p0, p1, p2, I, BINS, COMP, MISFIT, SCEN>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km,  \
+                       a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.cumE, a.C_traj, a.T_traj, a.n_rows,  \
+                       a.stats, a.br.ring, a.br.ring_rows, a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit)
 #define X(p0, p1, p2)                                                                                  \
     case (p0) * 100 + (p1) * 10 + (p2):                                                                \
         if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                          \
             return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);              \
         } else {                                                                                       \
-        if constexpr (HAS_PACKED && (!MISFIT || misfit_packed_fused(p0, p1, p2))) {                    \
-            if (packed) {                                                                              \
-                hipLaunchKernelGGL((fused_kernel<P, p0, p1, p2, false, BINS, COMP, MISFIT>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, \
-                                   a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, cumE, a.C_traj,  \
-                                   a.T_traj, a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w, br.n_bins, mf.obs,  \
-                                   mf.misfit);                                                         \
-                break;                                                                                 \
+            if constexpr (HAS_PACKED && (!MISFIT || misfit_packed_fused(p0, p1, p2))) {                \
+                if (packed) {                                                                          \
+                    FIVEEQ_FUSED_LAUNCH(P, p0, p1, p2, false);                                                   \
+                    break;                                                                             \
+                }                                                                                      \
             }                                                                                          \
-        }                                                                                              \
-        hipLaunchKernelGGL((fused_kernel<T, p0, p1, p2, INV, BINS, COMP, MISFIT>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km,   \
-                           a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, cumE, a.C_traj, a.T_traj,     \
-                           a.n_rows, a.stats, br.ring, br.ring_rows, br.lo, br.inv_w, br.n_bins, mf.obs, mf.misfit);    \
+            FIVEEQ_FUSED_LAUNCH(T, p0, p1, p2, INV);                                                           \
         }                                                                                              \
         break;
         FIVEEQ_LAYOUTS(X)
 #undef X
+#undef FIVEEQ_FUSED_LAUNCH
         default:
             return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
     }
@@ -304,9 +324,29 @@ int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, T* cumE, hipStream
     return FIVEEQ_OK;
 }
 
+// ---- the two drivers: every stepping entry point launches through one of them -------------------------------------------
+// per step: launch(t) for each timestep t of [t_begin, t_end)
+template <typename T, typename Launch>
+int each_step(const RunArgs<T>& a, Launch&& launch) {
+    for (int t = a.t_begin; t < a.t_end; ++t)
+        if (int rc = launch(t)) return rc;
+    return FIVEEQ_OK;
+}
+
+// per span: launch(t0, t1) over consecutive spans of k_steps steps (0, or more than the range: one span, the whole range)
+template <typename T, typename Launch>
+int each_span(const RunArgs<T>& a, int k_steps, Launch&& launch) {
+    if (k_steps == 0 || k_steps > a.t_end - a.t_begin) k_steps = a.t_end - a.t_begin;   // also keeps t + k_steps inside int32
+    for (int t = a.t_begin; t < a.t_end; t += k_steps)
+        if (int rc = launch(t, t + k_steps < a.t_end ? t + k_steps : a.t_end)) return rc;
+    return FIVEEQ_OK;
+}
+
+// ---- validation of one call: make_args() for what every stepping entry point takes, one checker per optional feature ------
 template <typename T>
-int make_args(RunArgs<T>& a, const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps,
-              int32_t t_begin, int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats) {
+int make_args(RunArgs<T>& a, const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
+              int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
+              int32_t n_scen = 1) {
     if (int rc = check_run(m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S)) return rc;
     if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
     a.km = make_kmodel<T>(m);
@@ -323,55 +363,98 @@ int make_args(RunArgs<T>& a, const fiveeq_model* m, int64_t n, int64_t ld, const
     a.T_traj = T_traj;
     a.n_rows = n_rows;
     a.n_steps = n_steps;
+    a.t_begin = t_begin;
+    a.t_end = t_end;
     a.stats = stats;
     a.packing = g_f32_packing.load(std::memory_order_relaxed);
     int sum_pools = 0;
     for (int g = 0; g < m->n_gas; ++g) sum_pools += m->gas[g].n_pools;
-    a.stream_rows = rows_streamed(g_row_policy.load(std::memory_order_relaxed), m->n_gas, sum_pools, n, ld, (int)sizeof(T));
+    a.stream_rows =
+        rows_streamed(g_row_policy.load(std::memory_order_relaxed), m->n_gas, sum_pools, n_scen, n, ld, (int)sizeof(T));
+    a.n_scen = n_scen;
     return FIVEEQ_OK;
 }
 
+// the bin-index ring (where the ring is optional, the caller leaves a NULL ring unchecked)
 template <typename T>
-int run_steps(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-              int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void* stream) {
-    RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    for (int t = t_begin; t < t_end; ++t)
-        if (int rc = launch_step(a, t, (hipStream_t)stream)) return rc;
+int check_ring(RunArgs<T>& a, double lo, double hi, int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows) {
+    if (n_bins < 1 || n_bins > HIST_MAX_BINS) return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, HIST_MAX_BINS);
+    if (!(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi)) return fail(FIVEEQ_E_INVALID, "need finite lo < hi");
+    if (!bin_ring) return fail(FIVEEQ_E_INVALID, "bin_ring is NULL");
+    if (ring_rows < 1) return fail(FIVEEQ_E_INVALID, "ring_rows=%d must be >= 1", ring_rows);
+    if (((uintptr_t)bin_ring) & 1) return fail(FIVEEQ_E_INVALID, "bin_ring must be 2-byte aligned");
+    a.br.ring = bin_ring;
+    a.br.ring_rows = ring_rows;
+    a.br.lo = lo;
+    a.br.inv_w = (double)n_bins / (hi - lo);
+    a.br.n_bins = n_bins;
     return FIVEEQ_OK;
 }
 
+// the misfit accumulators, and a pool layout that carries them
 template <typename T>
-int run_fused(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-              int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void* stream) {
-    RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    if (t_begin == t_end) return FIVEEQ_OK;
-    return launch_fused<T, false>(a, t_begin, t_end, nullptr, (hipStream_t)stream);
+int check_misfit(RunArgs<T>& a, const double* obs, double* misfit) {
+    if (!obs || !misfit) return fail(FIVEEQ_E_INVALID, "NULL misfit pointer (obs=%p misfit=%p)", (const void*)obs, (void*)misfit);
+    if ((((uintptr_t)obs) | ((uintptr_t)misfit)) & 7) return fail(FIVEEQ_E_INVALID, "obs and misfit must be 8-byte aligned");
+    if (!misfit_layout(a.code / 100, a.code / 10 % 10, a.code % 10))
+        return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form (pools {4} and 4+1+1 have)", a.code);
+    a.mf.obs = obs;
+    a.mf.misfit = misfit;
+    return FIVEEQ_OK;
 }
 
+// the scenario axis: one parameter ensemble under n_scen emission scenarios (step_scen_kernel, fused_kernel<.., SCEN>)
+constexpr int MAX_SCENARIOS = 64;
+int check_scen(int32_t n_scen) {
+    if (n_scen < 1 || n_scen > MAX_SCENARIOS) return fail(FIVEEQ_E_INVALID, "n_scen=%d outside 1..%d", n_scen, MAX_SCENARIOS);
+    return FIVEEQ_OK;
+}
+
+// the form of a run (FIVEEQ_FORM_*) and its span length: k_min is 1 where k_steps has no "whole range" value 0
+int check_form(int32_t form, int32_t k_steps, int32_t k_min) {
+    if (form != FIVEEQ_FORM_PER_STEP && form != FIVEEQ_FORM_FUSED)
+        return fail(FIVEEQ_E_INVALID, "form=%d: FIVEEQ_FORM_PER_STEP (0) or FIVEEQ_FORM_FUSED (1)", form);
+    if (k_steps < k_min) return fail(FIVEEQ_E_INVALID, "k_steps=%d must be >= %d", k_steps, k_min);
+    return FIVEEQ_OK;
+}
+
+// ---- the entry points (validated: nothing is launched before every check has passed) ---------------------------------------
+// the forward model, plain, constrained (MISFIT) or under several scenarios (SCEN): one launch per step, or the fused kernel
+// over spans of k_steps steps
+template <typename T, bool MISFIT = false, bool SCEN = false>
+int run_form(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
+    if (form == FIVEEQ_FORM_PER_STEP)
+        return each_step(a, [&](int t) { return launch_step<T, false, MISFIT, SCEN>(a, t, st); });
+    return each_span(a, k_steps, [&](int t0, int t1) { return launch_fused<T, false, false, false, MISFIT, SCEN>(a, t0, t1, st); });
+}
+
+// fiveeq_step/run/run_fused/run_ksteps (k_min 1), fiveeq_run_obs (MISFIT: obs, misfit) and fiveeq_run_scen (SCEN: n_scen,
+// checked first)
+template <typename T, bool MISFIT = false, bool SCEN = false>
+int run_forward(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
+                int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, int32_t form,
+                int32_t k_steps, int32_t k_min, void* stream, const double* obs = nullptr, double* misfit = nullptr,
+                int32_t n_scen = 1) {
+    if (int rc = SCEN ? check_scen(n_scen) : FIVEEQ_OK) return rc;
+    RunArgs<T> a;
+    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats, n_scen))
+        return rc;
+    if (int rc = MISFIT ? check_misfit(a, obs, misfit) : FIVEEQ_OK) return rc;
+    if (int rc = check_form(form, k_steps, k_min)) return rc;
+    return run_form<T, MISFIT, SCEN>(a, form, k_steps, (hipStream_t)stream);
+}
+
+// the streamed histograms: the per-step or the fused kernel <.., BINS = true> writing every member's bin into the ring
 template <typename T, bool FUSED>
 int run_bins(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
              int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
              double lo, double hi, int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
     RunArgs<T> a;
     if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    if (n_bins < 1 || n_bins > HIST_MAX_BINS) return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, HIST_MAX_BINS);
-    if (!(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi)) return fail(FIVEEQ_E_INVALID, "need finite lo < hi");
-    if (!bin_ring) return fail(FIVEEQ_E_INVALID, "bin_ring is NULL");
-    if (ring_rows < 1) return fail(FIVEEQ_E_INVALID, "ring_rows=%d must be >= 1", ring_rows);
-    if (((uintptr_t)bin_ring) & 1) return fail(FIVEEQ_E_INVALID, "bin_ring must be 2-byte aligned");
-    if (t_begin == t_end) return FIVEEQ_OK;
-    BinRing br;
-    br.ring = bin_ring;
-    br.ring_rows = ring_rows;
-    br.lo = lo;
-    br.inv_w = (double)n_bins / (hi - lo);
-    br.n_bins = n_bins;
-    if (FUSED) return launch_fused<T, false, true>(a, t_begin, t_end, nullptr, (hipStream_t)stream, br);
-    for (int t = t_begin; t < t_end; ++t)                 // the per-step form: one launch per timestep
-        if (int rc = launch_step<T, true>(a, t, (hipStream_t)stream, br)) return rc;
-    return FIVEEQ_OK;
+    if (int rc = check_ring(a, lo, hi, n_bins, bin_ring, ring_rows)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (FUSED) return each_span(a, 0, [&](int t0, int t1) { return launch_fused<T, false, true>(a, t0, t1, st); });
+    return each_step(a, [&](int t) { return launch_step<T, true>(a, t, st); });
 }
 
 template <typename T>
@@ -381,24 +464,9 @@ int run_inverse(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
     RunArgs<T> a;
     if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, stats)) return rc;
     if (!cumE) return fail(FIVEEQ_E_INVALID, "cumE is NULL");
-    if (t_begin == t_end) return FIVEEQ_OK;
-    return launch_fused<T, true>(a, t_begin, t_end, cumE, (hipStream_t)stream);
-}
-
-// ---- K steps per launch: the fused kernel over consecutive spans of k_steps ---------------------
-template <typename T>
-int run_ksteps(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-               int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
-               int32_t k_steps, void* stream) {
-    RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    if (k_steps < 1) return fail(FIVEEQ_E_INVALID, "k_steps=%d must be >= 1", k_steps);
-    if (t_begin == t_end) return FIVEEQ_OK;
-    if (k_steps > t_end - t_begin) k_steps = t_end - t_begin;      // also keeps t + k_steps inside int32
-    for (int t = t_begin; t < t_end; t += k_steps)
-        if (int rc = launch_fused<T, false>(a, t, t + k_steps < t_end ? t + k_steps : t_end, nullptr, (hipStream_t)stream))
-            return rc;
-    return FIVEEQ_OK;
+    a.cumE = cumE;
+    hipStream_t st = (hipStream_t)stream;
+    return each_span(a, 0, [&](int t0, int t1) { return launch_fused<T, true>(a, t0, t1, st); });
 }
 
 // ---- the compensated fp32 form: the fused kernel <.., COMP = true> over spans of k_steps, with or without the bin ring ----
@@ -408,28 +476,12 @@ int run_fused_comp(const fiveeq_model* m, int64_t n, int64_t ld, const float* dr
                    void* stream) {
     RunArgs<float> a;
     if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    if (k_steps < 1) return fail(FIVEEQ_E_INVALID, "k_steps=%d must be >= 1", k_steps);
-    BinRing br;
-    if (bin_ring) {
-        if (n_bins < 1 || n_bins > HIST_MAX_BINS) return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, HIST_MAX_BINS);
-        if (!(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi)) return fail(FIVEEQ_E_INVALID, "need finite lo < hi");
-        if (ring_rows < 1) return fail(FIVEEQ_E_INVALID, "ring_rows=%d must be >= 1", ring_rows);
-        if (((uintptr_t)bin_ring) & 1) return fail(FIVEEQ_E_INVALID, "bin_ring must be 2-byte aligned");
-        br.ring = bin_ring;
-        br.ring_rows = ring_rows;
-        br.lo = lo;
-        br.inv_w = (double)n_bins / (hi - lo);
-        br.n_bins = n_bins;
-    }
-    if (t_begin == t_end) return FIVEEQ_OK;
-    if (k_steps > t_end - t_begin) k_steps = t_end - t_begin;
-    for (int t = t_begin; t < t_end; t += k_steps) {
-        const int t1 = t + k_steps < t_end ? t + k_steps : t_end;
-        const int rc = bin_ring ? launch_fused<float, false, true, true>(a, t, t1, nullptr, (hipStream_t)stream, br)
-                                : launch_fused<float, false, false, true>(a, t, t1, nullptr, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return FIVEEQ_OK;
+    if (int rc = check_form(FIVEEQ_FORM_FUSED, k_steps, 1)) return rc;
+    if (int rc = bin_ring ? check_ring(a, lo, hi, n_bins, bin_ring, ring_rows) : FIVEEQ_OK) return rc;     // optional here
+    hipStream_t st = (hipStream_t)stream;
+    return each_span(a, k_steps, [&](int t0, int t1) {
+        return bin_ring ? launch_fused<float, false, true, true>(a, t0, t1, st) : launch_fused<float, false, false, true>(a, t0, t1, st);
+    });
 }
 
 // ---- small ensembles: one member per quad of lanes (small_kernel), several gases one per lane (small_multi_kernel) -----
@@ -437,10 +489,12 @@ int run_fused_comp(const fiveeq_model* m, int64_t n, int64_t ld, const float* dr
 // (an octet: small_octet_kernel), 1 for every other compiled layout, 0 = none
 int small_lanes(int code) { return code == 400 ? 4 : (code == 411 ? 8 : (layout_ok(code) ? 1 : 0)); }
 
-template <typename T>
+// COMP: the compensated fp32 form, small_multi_kernel<.., COMP = true> for every layout, one member per lane
+template <typename T, bool COMP = false>
 int run_small(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
               int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
               int32_t lanes, void* stream) {
+    static_assert(!COMP || std::is_same<T, float>::value, "the compensated form is fp32");
     RunArgs<T> a;
     if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
     const int widest = small_lanes(a.code);
@@ -451,27 +505,38 @@ int run_small(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int3
     if (lanes == 8 && a.stats != nullptr)
         return fail(FIVEEQ_E_INVALID, "lanes_per_member=8 writes no per-wave statistics (T_stats must be NULL): use 1");
     if (t_begin == t_end) return FIVEEQ_OK;
-    const int64_t per_block = FIVEEQ_SMALL_BLOCK / lanes;
-    const int64_t blocks = (a.n + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
-    const dim3 grid((unsigned)blocks), block(FIVEEQ_SMALL_BLOCK);
+    unsigned blocks;
+    if (int rc = grid_blocks(a.n, FIVEEQ_SMALL_BLOCK / lanes, blocks)) return rc;
+    const dim3 grid(blocks), block(FIVEEQ_SMALL_BLOCK);
     hipStream_t st = (hipStream_t)stream;
 #define FIVEEQ_SMALL_ARGS st, a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats
     const bool st_on = a.stats != nullptr;
+    if constexpr (COMP) {
+        switch (a.code) {
+#define X(p0, p1, p2)                                                                                                   \
+    case (p0) * 100 + (p1) * 10 + (p2):                                                                                 \
+        if (st_on) hipLaunchKernelGGL((small_multi_kernel<float, p0, p1, p2, true, true>), grid, block, 0, FIVEEQ_SMALL_ARGS); \
+        else hipLaunchKernelGGL((small_multi_kernel<float, p0, p1, p2, false, true>), grid, block, 0, FIVEEQ_SMALL_ARGS);      \
+        break;
+            FIVEEQ_LAYOUTS(X)
+#undef X
+            default: return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+        }
+    } else {
 #define FIVEEQ_SMALL1(p0, lpm)                                                                                     \
     if (st_on) hipLaunchKernelGGL((small_kernel<T, p0, lpm, true>), grid, block, 0, FIVEEQ_SMALL_ARGS);            \
     else hipLaunchKernelGGL((small_kernel<T, p0, lpm, false>), grid, block, 0, FIVEEQ_SMALL_ARGS);                 \
     break;
-    switch (a.code * 10 + lanes) {
-        case 1001: FIVEEQ_SMALL1(1, 1)
-        case 2001: FIVEEQ_SMALL1(2, 1)
-        case 3001: FIVEEQ_SMALL1(3, 1)
-        case 4001: FIVEEQ_SMALL1(4, 1)
-        case 4004: FIVEEQ_SMALL1(4, 4)
-        case 4118:
-            hipLaunchKernelGGL((small_octet_kernel<T>), grid, block, 0, st, a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q,
-                               a.R, a.S, a.C_traj, a.T_traj, a.n_rows);
-            break;
+        switch (a.code * 10 + lanes) {
+            case 1001: FIVEEQ_SMALL1(1, 1)
+            case 2001: FIVEEQ_SMALL1(2, 1)
+            case 3001: FIVEEQ_SMALL1(3, 1)
+            case 4001: FIVEEQ_SMALL1(4, 1)
+            case 4004: FIVEEQ_SMALL1(4, 4)
+            case 4118:
+                hipLaunchKernelGGL((small_octet_kernel<T>), grid, block, 0, st, a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld,
+                                   a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows);
+                break;
 #define X(p0, p1, p2)                                                                                              \
     case ((p0) * 100 + (p1) * 10 + (p2)) * 10 + 1:                                                                 \
         if constexpr ((p1) > 0) {                                                                                  \
@@ -479,207 +544,18 @@ int run_small(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int3
             else hipLaunchKernelGGL((small_multi_kernel<T, p0, p1, p2, false>), grid, block, 0, FIVEEQ_SMALL_ARGS);       \
         }                                                                                                          \
         break;
-        X(1, 1, 0) X(4, 1, 0) X(4, 4, 0) X(1, 1, 1) X(4, 1, 1) X(4, 4, 1) X(4, 4, 4)
+            X(1, 1, 0) X(4, 1, 0) X(4, 4, 0) X(1, 1, 1) X(4, 1, 1) X(4, 4, 1) X(4, 4, 4)
 #undef X
-        default: return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
-    }
+            default: return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+        }
 #undef FIVEEQ_SMALL1
+    }
 #undef FIVEEQ_SMALL_ARGS
     HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
 }
 
-// ---- the compensated fp32 form on the small-ensemble kernel: one member per lane, every layout ----
-int run_small_comp(const fiveeq_model* m, int64_t n, int64_t ld, const float* drive, int32_t n_steps, int32_t t_begin,
-                   int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj, float* T_traj, int n_rows,
-                   double* stats, void* stream) {
-    RunArgs<float> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    if (t_begin == t_end) return FIVEEQ_OK;
-    const int64_t blocks = (a.n + FIVEEQ_SMALL_BLOCK - 1) / FIVEEQ_SMALL_BLOCK;
-    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
-    const dim3 grid((unsigned)blocks), block(FIVEEQ_SMALL_BLOCK);
-    hipStream_t st = (hipStream_t)stream;
-    const bool st_on = a.stats != nullptr;
-    switch (a.code) {
-#define X(p0, p1, p2)                                                                                                          \
-    case (p0) * 100 + (p1) * 10 + (p2):                                                                                        \
-        if (st_on)                                                                                                             \
-            hipLaunchKernelGGL((small_multi_kernel<float, p0, p1, p2, true, true>), grid, block, 0, st, a.km, a.drive, a.n_steps,  \
-                               t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats);          \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((small_multi_kernel<float, p0, p1, p2, false, true>), grid, block, 0, st, a.km, a.drive, a.n_steps, \
-                               t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats);          \
-        break;
-        FIVEEQ_LAYOUTS(X)
-#undef X
-        default: return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
-    }
-    HIP_TRY(hipGetLastError());
-    return FIVEEQ_OK;
-}
-
-// ---- the constrained forms: the misfit accumulators carried through a per-step or a (K-step) fused run -------------------
-int misfit_check(const double* obs, double* misfit) {
-    if (!obs || !misfit) return fail(FIVEEQ_E_INVALID, "NULL misfit pointer (obs=%p misfit=%p)", (const void*)obs, (void*)misfit);
-    if ((((uintptr_t)obs) | ((uintptr_t)misfit)) & 7) return fail(FIVEEQ_E_INVALID, "obs and misfit must be 8-byte aligned");
-    return FIVEEQ_OK;
-}
-int misfit_layout_check(int code) {
-    if (!misfit_layout(code / 100, code / 10 % 10, code % 10))
-        return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form (pools {4} and 4+1+1 have)", code);
-    return FIVEEQ_OK;
-}
-
-template <typename T>
-int run_obs(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
-            const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, const double* obs,
-            double* misfit, int32_t form, int32_t k_steps, void* stream) {
-    RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    if (int rc = misfit_check(obs, misfit)) return rc;
-    if (form != FIVEEQ_FORM_PER_STEP && form != FIVEEQ_FORM_FUSED)
-        return fail(FIVEEQ_E_INVALID, "form=%d: FIVEEQ_FORM_PER_STEP (0) or FIVEEQ_FORM_FUSED (1)", form);
-    if (int rc = misfit_layout_check(a.code)) return rc;
-    if (k_steps < 0) return fail(FIVEEQ_E_INVALID, "k_steps=%d must be >= 0", k_steps);
-    if (t_begin == t_end) return FIVEEQ_OK;
-    MisfitRows mf;
-    mf.obs = obs;
-    mf.misfit = misfit;
-    hipStream_t st = (hipStream_t)stream;
-    if (form == FIVEEQ_FORM_PER_STEP) {
-        for (int t = t_begin; t < t_end; ++t)
-            if (int rc = launch_step<T, false, true>(a, t, st, BinRing(), mf)) return rc;
-        return FIVEEQ_OK;
-    }
-    if (k_steps == 0 || k_steps > t_end - t_begin) k_steps = t_end - t_begin;
-    for (int t = t_begin; t < t_end; t += k_steps)
-        if (int rc = launch_fused<T, false, false, false, true>(a, t, t + k_steps < t_end ? t + k_steps : t_end, nullptr, st,
-                                                               BinRing(), mf))
-            return rc;
-    return FIVEEQ_OK;
-}
-
-// ---- the scenario axis: one parameter ensemble under n_scen emission scenarios (step_scen_kernel, fused_kernel<.., SCEN>) ----
-constexpr int MAX_SCENARIOS = 64;
-
-// the row policy of kernel 1s: as rows_streamed(), with the S-fold state counted — n_scen (SP + 2) state rows beside the
-// 3G + 2 shared parameter rows per member
-bool rows_streamed_scen(int policy, int n_gas, int sum_pools, int n_scen, int64_t n, int64_t ld, int word) {
-    if (policy != FIVEEQ_ROWS_AUTO) return policy == FIVEEQ_ROWS_STREAMED;
-    const int64_t per_member = (int64_t)word * ((int64_t)n_scen * (sum_pools + 2) + 3 * n_gas + 2);
-    return n * per_member >= INFINITY_CACHE_BYTES && ld * per_member >= 2 * INFINITY_CACHE_BYTES;
-}
-
-template <typename T>
-int launch_step_scen(const RunArgs<T>& a, int t, int n_scen, bool nt, hipStream_t st) {
-    using P = typename LaneOf<T>::Packed;
-    const bool packed = LaneOf<T>::can_pack(a);
-    const int64_t per_block = (int64_t)FIVEEQ_STEP_BLOCK * (packed ? 2 : 1);
-    const int64_t blocks = (a.n + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
-    const dim3 grid((unsigned)blocks), block(FIVEEQ_STEP_BLOCK);
-    switch (a.code) {
-#define FIVEEQ_SCEN_LAUNCH(V, p0, p1, p2, NT)                                                                                   \
-    hipLaunchKernelGGL((step_scen_kernel<V, p0, p1, p2, NT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, n_scen, \
-                       a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats)
-#define X(p0, p1, p2)                                                                             \
-    case (p0) * 100 + (p1) * 10 + (p2):                                                           \
-        if (nt) {                                                                                 \
-            if (packed) FIVEEQ_SCEN_LAUNCH(P, p0, p1, p2, true);                                  \
-            else FIVEEQ_SCEN_LAUNCH(T, p0, p1, p2, true);                                         \
-        } else {                                                                                  \
-            if (packed) FIVEEQ_SCEN_LAUNCH(P, p0, p1, p2, false);                                 \
-            else FIVEEQ_SCEN_LAUNCH(T, p0, p1, p2, false);                                        \
-        }                                                                                         \
-        break;
-        FIVEEQ_LAYOUTS(X)
-#undef X
-#undef FIVEEQ_SCEN_LAUNCH
-        default:
-            return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
-    }
-    HIP_TRY(hipGetLastError());
-    return FIVEEQ_OK;
-}
-
-template <typename T>
-int launch_fused_scen(const RunArgs<T>& a, int t_begin, int t_end, int n_scen, hipStream_t st) {
-    using P = typename LaneOf<T>::Packed;
-    constexpr bool HAS_PACKED = !std::is_same<P, T>::value;
-    const bool packed = HAS_PACKED && LaneOf<T>::can_pack(a);
-    const int64_t blocks = member_blocks(packed ? (a.n + 1) / 2 : a.n);
-    if (blocks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large for one launch");
-    const dim3 grid((unsigned)blocks, (unsigned)n_scen), block(FIVEEQ_BLOCK);
-    switch (a.code) {
-#define FIVEEQ_SCEN_FUSED(V, p0, p1, p2)                                                                                        \
-    hipLaunchKernelGGL((fused_kernel<V, p0, p1, p2, false, false, false, false, true>), grid, block, FIVEEQ_FUSED_DYN_LDS, st,   \
-                       a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, nullptr, a.C_traj, a.T_traj,   \
-                       a.n_rows, a.stats, nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr)
-#define X(p0, p1, p2)                                                                             \
-    case (p0) * 100 + (p1) * 10 + (p2):                                                           \
-        if constexpr (HAS_PACKED) {                                                               \
-            if (packed) {                                                                         \
-                FIVEEQ_SCEN_FUSED(P, p0, p1, p2);                                                 \
-                break;                                                                            \
-            }                                                                                     \
-        }                                                                                         \
-        FIVEEQ_SCEN_FUSED(T, p0, p1, p2);                                                         \
-        break;
-        FIVEEQ_LAYOUTS(X)
-#undef X
-#undef FIVEEQ_SCEN_FUSED
-        default:
-            return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
-    }
-    HIP_TRY(hipGetLastError());
-    return FIVEEQ_OK;
-}
-
-int scen_check(int32_t n_scen) {
-    if (n_scen < 1 || n_scen > MAX_SCENARIOS) return fail(FIVEEQ_E_INVALID, "n_scen=%d outside 1..%d", n_scen, MAX_SCENARIOS);
-    return FIVEEQ_OK;
-}
-
-// make_args() for the scenario forms: the scenario count checked first, the row policy counted with the S-fold state
-template <typename T>
-int make_scen_args(RunArgs<T>& a, bool& nt, const fiveeq_model* m, int64_t n, int64_t ld, int32_t n_scen, const T* drive,
-                   int32_t n_steps, int32_t t_begin, int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj,
-                   int n_rows, double* stats) {
-    if (int rc = scen_check(n_scen)) return rc;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    int sum_pools = 0;
-    for (int g = 0; g < m->n_gas; ++g) sum_pools += m->gas[g].n_pools;
-    nt = rows_streamed_scen(g_row_policy.load(std::memory_order_relaxed), m->n_gas, sum_pools, n_scen, n, ld, (int)sizeof(T));
-    return FIVEEQ_OK;
-}
-
-template <typename T>
-int run_scen(const fiveeq_model* m, int64_t n, int64_t ld, int32_t n_scen, const T* drive, int32_t n_steps, int32_t t_begin,
-             int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, int32_t form,
-             int32_t k_steps, void* stream) {
-    RunArgs<T> a;
-    bool nt = false;
-    if (int rc = make_scen_args(a, nt, m, n, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                stats))
-        return rc;
-    if (form != FIVEEQ_FORM_PER_STEP && form != FIVEEQ_FORM_FUSED)
-        return fail(FIVEEQ_E_INVALID, "form=%d: FIVEEQ_FORM_PER_STEP (0) or FIVEEQ_FORM_FUSED (1)", form);
-    if (k_steps < 0) return fail(FIVEEQ_E_INVALID, "k_steps=%d must be >= 0", k_steps);
-    if (t_begin == t_end) return FIVEEQ_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (form == FIVEEQ_FORM_PER_STEP) {
-        for (int t = t_begin; t < t_end; ++t)
-            if (int rc = launch_step_scen(a, t, n_scen, nt, st)) return rc;
-        return FIVEEQ_OK;
-    }
-    if (k_steps == 0 || k_steps > t_end - t_begin) k_steps = t_end - t_begin;
-    for (int t = t_begin; t < t_end; t += k_steps)
-        if (int rc = launch_fused_scen(a, t, t + k_steps < t_end ? t + k_steps : t_end, n_scen, st)) return rc;
-    return FIVEEQ_OK;
-}
-
-// ---- plans: the per-step launch sequence captured into a hipGraph --------------------------
+// ---- plans: a per-step run captured into a hipGraph -----------------------------------------------------------------------
 struct Plan {
     uint32_t magic;
     hipGraph_t graph;
@@ -687,25 +563,21 @@ struct Plan {
 };
 constexpr uint32_t PLAN_MAGIC = 0x35455146u;  // "FQE5"
 
-template <typename T>
+// the plan of run_form<T, MISFIT, SCEN>(FIVEEQ_FORM_PER_STEP): that very run, enqueued on a capture stream
+template <typename T, bool MISFIT = false, bool SCEN = false>
 int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
                 int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void** plan_out,
-                const MisfitRows* mf = nullptr, int32_t n_scen = 0 /* > 0: the scenario form, step_scen_kernel */) {
+                const double* obs = nullptr, double* misfit = nullptr, int32_t n_scen = 1) {
+    if (SCEN) {
+        if (plan_out) *plan_out = nullptr;
+        if (int rc = check_scen(n_scen)) return rc;
+    }
     if (!plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
     *plan_out = nullptr;
     RunArgs<T> a;
-    bool scen_nt = false;
-    if (n_scen != 0) {
-        if (int rc = make_scen_args(a, scen_nt, m, n, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                    n_rows, stats))
-            return rc;
-    } else if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) {
+    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats, n_scen))
         return rc;
-    }
-    if (mf) {
-        if (int rc = misfit_check(mf->obs, mf->misfit)) return rc;
-        if (int rc = misfit_layout_check(a.code)) return rc;
-    }
+    if (int rc = MISFIT ? check_misfit(a, obs, misfit) : FIVEEQ_OK) return rc;
     if (t_begin == t_end) return fail(FIVEEQ_E_INVALID, "empty step range for a plan");
     hipStream_t cap = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
@@ -715,10 +587,7 @@ int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
         (void)hipStreamDestroy(cap);
         return fail(FIVEEQ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(e));
     }
-    int rc = FIVEEQ_OK;
-    for (int t = t_begin; t < t_end && rc == FIVEEQ_OK; ++t)
-        rc = n_scen ? launch_step_scen(a, t, n_scen, scen_nt, cap)
-                    : (mf ? launch_step<T, false, true>(a, t, cap, BinRing(), *mf) : launch_step(a, t, cap));
+    const int rc = run_form<T, MISFIT, SCEN>(a, FIVEEQ_FORM_PER_STEP, 0, cap);
     e = hipStreamEndCapture(cap, &graph);
     (void)hipStreamDestroy(cap);
     if (rc != FIVEEQ_OK) {
@@ -794,19 +663,20 @@ int fiveeq_step_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, co
                     int32_t t, const double* r, const double* q, double* R, double* S, double* C_traj, double* T_traj,
                     int32_t n_rows, double* T_stats, void* stream) {
     if (t < 0 || t >= n_steps) return fail(FIVEEQ_E_INVALID, "t=%d outside [0,%d)", t, n_steps);
-    return run_steps<double>(model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats, stream);
+    return run_forward<double>(model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                               FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                    int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
                    double* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_steps<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                        stream);
+    return run_forward<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                               T_stats, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_fused_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                          int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                          double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_fused<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                        stream);
+    return run_forward<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                               T_stats, FIVEEQ_FORM_FUSED, 0, 0, stream);
 }
 int fiveeq_plan_create_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                            int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
@@ -818,19 +688,20 @@ int fiveeq_step_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, co
                     int32_t t, const float* r, const float* q, float* R, float* S, float* C_traj, float* T_traj,
                     int32_t n_rows, double* T_stats, void* stream) {
     if (t < 0 || t >= n_steps) return fail(FIVEEQ_E_INVALID, "t=%d outside [0,%d)", t, n_steps);
-    return run_steps<float>(model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats, stream);
+    return run_forward<float>(model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                              FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                    int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                    float* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_steps<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                        stream);
+    return run_forward<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                              T_stats, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_fused_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                          int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                          float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_fused<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                        stream);
+    return run_forward<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                              T_stats, FIVEEQ_FORM_FUSED, 0, 0, stream);
 }
 int fiveeq_run_fused_bins_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                               int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
@@ -886,15 +757,15 @@ int fiveeq_run_ksteps_f64(const fiveeq_model* model, int64_t n_members, int64_t 
                           int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                           double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, int32_t k_steps,
                           void* stream) {
-    return run_ksteps<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                              T_stats, k_steps, stream);
+    return run_forward<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                               T_stats, FIVEEQ_FORM_FUSED, k_steps, 1, stream);
 }
 int fiveeq_run_ksteps_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                           int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                           float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, int32_t k_steps,
                           void* stream) {
-    return run_ksteps<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                             T_stats, k_steps, stream);
+    return run_forward<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                              T_stats, FIVEEQ_FORM_FUSED, k_steps, 1, stream);
 }
 int fiveeq_run_fused_comp_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                               int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
@@ -920,41 +791,36 @@ int fiveeq_run_small_f32(const fiveeq_model* model, int64_t n_members, int64_t l
 int fiveeq_run_small_comp_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                               int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                               float* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_small_comp(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats, stream);
+    return run_small<float, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                                  1, stream);
 }
 int fiveeq_run_obs_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                        int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
                        double* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit, int32_t form,
                        int32_t k_steps, void* stream) {
-    return run_obs<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats, obs,
-                           misfit, form, k_steps, stream);
+    return run_forward<double, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                     n_rows, T_stats, form, k_steps, 0, stream, obs, misfit);
 }
 int fiveeq_run_obs_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                        int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                        float* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit, int32_t form,
                        int32_t k_steps, void* stream) {
-    return run_obs<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats, obs,
-                          misfit, form, k_steps, stream);
+    return run_forward<float, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                    n_rows, T_stats, form, k_steps, 0, stream, obs, misfit);
 }
 int fiveeq_plan_create_obs_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                                int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
                                double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit,
                                void** plan_out) {
-    MisfitRows mf;
-    mf.obs = obs;
-    mf.misfit = misfit;
-    return plan_create<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                               plan_out, &mf);
+    return plan_create<double, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                                     T_stats, plan_out, obs, misfit);
 }
 int fiveeq_plan_create_obs_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                                int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
                                float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit,
                                void** plan_out) {
-    MisfitRows mf;
-    mf.obs = obs;
-    mf.misfit = misfit;
-    return plan_create<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                              plan_out, &mf);
+    return plan_create<float, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                                    T_stats, plan_out, obs, misfit);
 }
 int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;
@@ -967,31 +833,27 @@ int fiveeq_run_scen_f64(const fiveeq_model* model, int64_t n_members, int64_t ld
                         int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
                         double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, int32_t form, int32_t k_steps,
                         void* stream) {
-    return run_scen<double>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                            T_stats, form, k_steps, stream);
+    return run_forward<double, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj,
+                                            T_traj, n_rows, T_stats, form, k_steps, 0, stream, nullptr, nullptr, n_scen);
 }
 int fiveeq_run_scen_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
                         int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
                         float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, int32_t form, int32_t k_steps,
                         void* stream) {
-    return run_scen<float>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                           T_stats, form, k_steps, stream);
+    return run_forward<float, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj,
+                                           T_traj, n_rows, T_stats, form, k_steps, 0, stream, nullptr, nullptr, n_scen);
 }
 int fiveeq_plan_create_scen_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
                                 int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                                 double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
-    if (plan_out) *plan_out = nullptr;
-    if (int rc = scen_check(n_scen)) return rc;
-    return plan_create<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                               plan_out, nullptr, n_scen);
+    return plan_create<double, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                            n_rows, T_stats, plan_out, nullptr, nullptr, n_scen);
 }
 int fiveeq_plan_create_scen_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
                                 int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                                 float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
-    if (plan_out) *plan_out = nullptr;
-    if (int rc = scen_check(n_scen)) return rc;
-    return plan_create<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                              plan_out, nullptr, n_scen);
+    return plan_create<float, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                           n_rows, T_stats, plan_out, nullptr, nullptr, n_scen);
 }
 int32_t fiveeq_max_scenarios(void) { return MAX_SCENARIOS; }
 
@@ -1014,7 +876,7 @@ int fiveeq_rows_streamed(int32_t n_gas, const int32_t* n_pools, int64_t n_member
         return fail(FIVEEQ_E_INVALID, "fiveeq_rows_streamed: bad shape");
     int sum_pools = 0;
     for (int g = 0; g < n_gas; ++g) sum_pools += n_pools[g];
-    return rows_streamed(g_row_policy.load(std::memory_order_relaxed), n_gas, sum_pools, n_members, ld, word_bytes) ? 1 : 0;
+    return rows_streamed(g_row_policy.load(std::memory_order_relaxed), n_gas, sum_pools, 1, n_members, ld, word_bytes) ? 1 : 0;
 }
 
 static int lhs_check(int64_t n_total, int64_t m0, int64_t n_members, int32_t dim0, int32_t n_dim, int64_t ld) {

@@ -467,14 +467,44 @@ class EnsembleEngine(CheckpointMixin):
         """(obs, misfit) C-ABI pointers for members [m0, ...) of the misfit rows (ld = N)."""
         return self._ptr(self.obs), self._ptr(self.misfit, m0 * 8)
 
-    def _run_obs(self, t_begin, t_end, stream, form, k_steps=0, m0=0, n=None):
-        return self._fn("run_obs")(*self._run_args(t_begin, t_end, m0, n), *self._obs_args(m0), form, int(k_steps),
-                                   self._stream(stream))
+    def _forward_calls(self):
+        """The C calls of this engine's forward run, with the arguments of its feature bound: n_scen (the scenario axis, whose
+        strides derive from ld = N), (obs, misfit) (observations=) or none.  Returns
+          per_step(t_begin, t_end, m0, n, stream)  one launch per step for members [m0, m0 + n);
+          fused(t_begin, t_end, k, stream)         the fused kernel over spans of k steps, all members;
+          plan(t_begin, t_end, m0, n, plan_out)    the per-step launches of members [m0, m0 + n) captured into a plan."""
+        def args(t_begin, t_end, m0=0, n=None):
+            a = self._run_args(t_begin, t_end, m0, n)
+            if self.scenario_axis:
+                return (*a[:3], self.n_scenarios, *a[3:])
+            return a if self.observations is None else (*a, *self._obs_args(m0))
 
-    def _run_scen(self, t_begin, t_end, stream, form, k_steps=0, m0=0, n=None):
-        """fiveeq_run_scen_*: members [m0, m0 + n) under every scenario (the scenario strides derive from ld = N)."""
-        a = self._run_args(t_begin, t_end, m0, n)
-        return self._fn("run_scen")(*a[:3], self.n_scenarios, *a[3:], form, int(k_steps), self._stream(stream))
+        if self.scenario_axis or self.observations is not None:
+            sfx = "scen" if self.scenario_axis else "obs"
+            run, plan = self._fn("run_" + sfx), self._fn("plan_create_" + sfx)
+
+            def per_step(t, t1, m0, n, s):
+                return run(*args(t, t1, m0, n), _capi.FORM_PER_STEP, 0, self._stream(s))
+
+            def fused(t, t1, k, s):
+                return run(*args(t, t1), _capi.FORM_FUSED, int(k), self._stream(s))
+        else:
+            run, run_fused, ksteps, plan = self._fn("run"), self._fn("run_fused"), self._fn("run_ksteps"), self._fn("plan_create")
+
+            def per_step(t, t1, m0, n, s):
+                return run(*args(t, t1, m0, n), self._stream(s))
+
+            def fused(t, t1, k, s):                             # k < 1 (an empty range): run_ksteps would refuse it
+                return ksteps(*args(t, t1), int(k), self._stream(s)) if k >= 1 else run_fused(*args(t, t1), self._stream(s))
+
+        return per_step, fused, lambda t, t1, m0, n, out: plan(*args(t, t1, m0, n), out)
+
+    def _span_steps(self, mode, t_begin, t_end, k_steps):
+        """Steps per launch of the time-fused kernel in mode 'fused' (fused_span_steps) or 'ksteps' (k_steps, default
+        auto_k_steps())."""
+        if mode == "fused":
+            return self.fused_span_steps(t_end - t_begin)
+        return max(self.auto_k_steps() if k_steps is None else int(k_steps), 1)
 
     def _run_inverse(self, t_begin, t_end, stream):
         a = self._run_args(t_begin, t_end)
@@ -492,13 +522,8 @@ class EnsembleEngine(CheckpointMixin):
         with torch.cuda.device(self.device):
             if self.concentration_driven:
                 rc = self._run_inverse(t, t + 1, stream)
-            elif self.scenario_axis:
-                rc = self._run_scen(t, t + 1, stream, _capi.FORM_PER_STEP)
-            elif self.observations is not None:
-                rc = self._run_obs(t, t + 1, stream, _capi.FORM_PER_STEP)
             else:
-                a = self._run_args(t, t + 1)
-                rc = self._fn("step")(*a[:5], t, *a[7:], self._stream(stream))
+                rc = self._forward_calls()[0](t, t + 1, 0, None, stream)
         _capi.check(self.lib, rc)
         self.t_next = t + 1
 
@@ -550,32 +575,17 @@ class EnsembleEngine(CheckpointMixin):
                 rc = self._run_per_step(t_begin, t_end, stream, join)
             elif mode == "fused" and self.T_hist is not None:
                 rc = self._run_fused_bin_ring(t_begin, t_end, stream)
-            elif self.compensated and mode == "small":
+            elif mode == "small" and self.compensated:
                 rc = self.lib.fiveeq_run_small_comp_f32(*self._run_args(t_begin, t_end), self._stream(stream))
-            elif self.compensated:                                   # 'fused' / 'ksteps' without a ring: one C call
-                span = (self.fused_span_steps(t_end - t_begin) if mode == "fused" else
-                        max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
-                rc = self.lib.fiveeq_run_fused_comp_f32(*self._run_args(t_begin, t_end), span, 0.0, 1.0, 1, None, 0,
-                                                        self._stream(stream))
-            elif self.scenario_axis and mode in ("fused", "ksteps"):
-                k = (self.fused_span_steps(t_end - t_begin) if mode == "fused" else
-                     max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
-                rc = self._run_scen(t_begin, t_end, stream, _capi.FORM_FUSED, k)
-            elif self.observations is not None and mode in ("fused", "ksteps"):
-                k = (self.fused_span_steps(t_end - t_begin) if mode == "fused" else
-                     max(self.auto_k_steps() if k_steps is None else int(k_steps), 1))
-                rc = self._run_obs(t_begin, t_end, stream, _capi.FORM_FUSED, k)
-            elif mode == "fused":
-                span = self.fused_span_steps(t_end - t_begin)
-                if span < t_end - t_begin:                       # the same kernel, relaunched every `span` steps
-                    rc = self._fn("run_ksteps")(*self._run_args(t_begin, t_end), span, self._stream(stream))
-                else:
-                    rc = self._fn("run_fused")(*self._run_args(t_begin, t_end), self._stream(stream))
-            elif mode == "ksteps":
-                k = self.auto_k_steps() if k_steps is None else int(k_steps)
-                rc = self._fn("run_ksteps")(*self._run_args(t_begin, t_end), max(k, 1), self._stream(stream))
             elif mode == "small":
                 rc = self._fn("run_small")(*self._run_args(t_begin, t_end), self.small_form(), self._stream(stream))
+            elif mode in ("fused", "ksteps"):                    # without a ring: one C call, the kernel relaunched every span
+                span = self._span_steps(mode, t_begin, t_end, k_steps)
+                if self.compensated:
+                    rc = self.lib.fiveeq_run_fused_comp_f32(*self._run_args(t_begin, t_end), span, 0.0, 1.0, 1, None, 0,
+                                                            self._stream(stream))
+                else:
+                    rc = self._forward_calls()[1](t_begin, t_end, span, stream)
             else:                                                # 'graph': one captured plan per (chunk, part), the parts of a
                 plans = self.prepare_graph(t_begin, t_end)       # chunk replayed side by side on their own streams
                 rc = self._on_part_streams(stream, True, lambda streams: self._first_error(
@@ -691,20 +701,10 @@ class EnsembleEngine(CheckpointMixin):
         kernel also writes every member's histogram bin into a ring strip [S, N] of uint16 (row t mod S); after S steps each
         part counts its strip into T_hist (fiveeq_hist_bins) on its own stream — 2 bytes written + 2 read per member-step on
         top of the step's 124 / 248."""
-        if self.scenario_axis:
-            block = PER_STEP_BLOCK if self.per_step_streams > 1 else None
-            return self._per_step_schedule(t_begin, t_end, stream, join, block, lambda t, t1, m0, n, s: self._run_scen(
-                t, t1, s, _capi.FORM_PER_STEP, 0, m0, n))
-        if self.observations is not None:
-            block = PER_STEP_BLOCK if self.per_step_streams > 1 else None
-            return self._per_step_schedule(t_begin, t_end, stream, join, block, lambda t, t1, m0, n, s: self._run_obs(
-                t, t1, s, _capi.FORM_PER_STEP, 0, m0, n))
-        if self.T_hist is None:
+        if self.T_hist is None:                                  # (hist= is never combined with the scenario axis or observations=)
             # several streams: short blocks keep every stream's queue fed; one stream: one C call per chunk
             block = PER_STEP_BLOCK if self.per_step_streams > 1 else None
-            run = self._fn("run")
-            return self._per_step_schedule(t_begin, t_end, stream, join, block,
-                                           lambda t, t1, m0, n, s: run(*self._run_args(t, t1, m0, n), self._stream(s)))
+            return self._per_step_schedule(t_begin, t_end, stream, join, block, self._forward_calls()[0])
         N, (lo_h, hi_h, nb) = self.n_members, self.hist_spec
         ring = self._bin_ring(slots=1)
         S, buf, run = ring["S"], ring["buf"][0], self._fn("run_bins")
@@ -774,15 +774,11 @@ class EnsembleEngine(CheckpointMixin):
         if plans is None:
             plans = []
             self._wave_stats()
-            fn = self._fn("plan_create" if self.observations is None else "plan_create_obs")
-            if self.scenario_axis:
-                scen = self._fn("plan_create_scen")
-                fn = lambda *a: scen(*a[:3], self.n_scenarios, *a[3:])       # noqa: E731
+            create = self._forward_calls()[2]
             with torch.cuda.device(self.device):
                 for m0, n, _ in self.per_step_launches():
                     plan = ctypes.c_void_p()
-                    extra = () if self.observations is None else self._obs_args(m0)
-                    _capi.check(self.lib, fn(*self._run_args(t_begin, t_end, m0, n), *extra, ctypes.byref(plan)))
+                    _capi.check(self.lib, create(t_begin, t_end, m0, n, ctypes.byref(plan)))
                     plans.append(plan)
             self._plans[key] = plans
         return plans

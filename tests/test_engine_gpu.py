@@ -1543,7 +1543,7 @@ def test_percentile_selection_on_device_rows(gpu, dtype):
     np.testing.assert_allclose(one["percentiles"].cpu().numpy(), np.percentile(xs, pct, axis=1).T, rtol=1e-13, atol=0)
 
 
-def test_bin_index_ring_equals_the_histogram_of_stored_rows_and_keeps_stored_concentrations(gpu):
+def test_bin_index_ring_equals_the_histogram_of_stored_rows_and_leaves_the_stored_concentrations(gpu):
     """The streamed form writes 2-byte bin indices from inside the fused kernel: its T_hist must equal the histogram of stored
     rows bit for bit (same bin rule), the model results must not notice it, the moments come from the kernel's wave
     records, and it coexists with stored C rows.  Ragged sizes (the last packed
