@@ -855,6 +855,43 @@ __device__ __forceinline__ unsigned int hist_bin2(const HistRule<float> r, const
     const float2v pos = __builtin_elementwise_fma(v, (float2v)r.scale, (float2v)r.offset);
     return hist_bin_of_pos(r, pos.x, v.x) | (hist_bin_of_pos(r, pos.y, v.y) << 16);
 }
+// The histogram bin of T at o, the lane's slot in the ring row of its step (bin_ring [ring_rows][ld], row t mod ring_rows:
+// a scalar row offset), 2 bytes per member.  A packed lane stores both members' bins with one 4-byte store.
+template <typename T, typename V>
+__device__ __forceinline__ void store_bin(unsigned short* o, const HistRule<T> rule, const V Tn, const bool full) {
+    if constexpr (Lane<V>::W == 1) {
+        *o = (unsigned short)hist_bin(rule, Tn);
+    } else {
+        const unsigned int b01 = hist_bin2(rule, Tn);
+        if (full) *reinterpret_cast<unsigned int*>(o) = b01;
+        else *o = (unsigned short)(b01 & 0xffffu);
+    }
+}
+
+// One misfit step of the lane's member(s) (misfit_update()).  ob is the step's obs record: wave-uniform, read with scalar
+// loads, so the window test is a scalar branch; on a step outside the window (p_t == 0 && b_t == 0) the accumulators are
+// neither read nor written.  Word k of member j of the lane is acc[j * mem_stride + k * word_stride]: misfit [3][ld] in HBM
+// (strides 1, ld) or the fused kernel's lane-private LDS slots [3 W][FIVEEQ_BLOCK] (strides 3 FIVEEQ_BLOCK, FIVEEQ_BLOCK).
+// full = false skips a packed lane's missing second member; the LDS carrier passes true (there the missing member shadows
+// the first one and is never stored).
+template <typename V>
+__device__ __forceinline__ void misfit_step(const double* ob, const V Tn, double* acc, const int64_t mem_stride,
+                                            const int64_t word_stride, const bool full) {
+    const double o_t = ob[0], p_t = ob[1], b_t = ob[2];
+    if (p_t != 0.0 || b_t != 0.0) {
+#pragma unroll
+        for (int j = 0; j < Lane<V>::W; ++j) {
+            if (j == 0 || full) {
+                double* a = acc + j * mem_stride;
+                double A = a[0], U = a[word_stride], Vq = a[2 * word_stride];
+                misfit_update(o_t, p_t, b_t, lane_member(Tn, j), A, U, Vq);
+                a[0] = A;
+                a[word_stride] = U;
+                a[2 * word_stride] = Vq;
+            }
+        }
+    }
+}
 
 #ifdef FIVEEQ_STEP_WAVES
 #define FIVEEQ_STEP_ATTR __attribute__((amdgpu_waves_per_eu(FIVEEQ_STEP_WAVES, FIVEEQ_STEP_WAVES)))
@@ -915,9 +952,8 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
     __syncthreads();
 
     V Tn = (V)T(0);
-    {
-        member_step<V, L>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn);
-        if (active) {
+    member_step<V, L>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn);
+    if (active) {
 #pragma unroll
         for (int k = 0; k < L::SP; ++k) store_row<NT>(R + k * ld + m, Rv[k], full);
 #pragma unroll
@@ -931,34 +967,9 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
             }
             if (T_traj != nullptr) store_row<NTT>(T_traj + (int64_t)row * ld + m, Tn, full);
         }
-        if constexpr (MISFIT) {
-            const double o_t = obs[(int64_t)t * 4], p_t = obs[(int64_t)t * 4 + 1], b_t = obs[(int64_t)t * 4 + 2];   // scalar loads
-            if (p_t != 0.0 || b_t != 0.0) {
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    if (j == 0 || full) {
-                        double* mf = misfit + m + j;
-                        double A = mf[0], U = mf[ld], Vq = mf[2 * ld];
-                        misfit_update(o_t, p_t, b_t, lane_member(Tn, j), A, U, Vq);
-                        mf[0] = A;
-                        mf[ld] = U;
-                        mf[2 * ld] = Vq;
-                    }
-                }
-            }
-        }
-        if constexpr (BINS) {                                            // the histogram bin of T, 2 bytes per member
-            unsigned short* o = bin_ring + (int64_t)(t % ring_rows) * ld + m;
-            const HistRule<T> rule = make_rule(T(0), hist_lo, hist_inv_w, n_bins);
-            if constexpr (W == 1) {
-                *o = (unsigned short)hist_bin(rule, Tn);
-            } else {
-                const unsigned int b01 = hist_bin2(rule, Tn);
-                if (full) *reinterpret_cast<unsigned int*>(o) = b01;
-                else *o = (unsigned short)(b01 & 0xffffu);
-            }
-        }
-        }
+        if constexpr (MISFIT) misfit_step(obs + (int64_t)t * 4, Tn, misfit + m, 1, ld, full);
+        if constexpr (BINS)
+            store_bin(bin_ring + (int64_t)(t % ring_rows) * ld + m, make_rule(T(0), hist_lo, hist_inv_w, n_bins), Tn, full);
     }
     if (stats != nullptr) {
         const int64_t n_rec = (n + 63) >> 6;                             // one record per 64 members
@@ -1174,21 +1185,7 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
         for (int k = 0; k < nt; ++k) {
             const T* d = &drv[k * DRIVE_STRIDE];
             member_step<V, L, INV, COMP>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo);
-            if constexpr (MISFIT) {
-                const double* ob = obs + (int64_t)(tc + k) * 4;                 // wave-uniform: scalar loads, scalar branch
-                const double o_t = ob[0], p_t = ob[1], b_t = ob[2];
-                if (p_t != 0.0 || b_t != 0.0) {
-#pragma unroll
-                    for (int j = 0; j < W; ++j) {
-                        double* a = acc + 3 * j * FIVEEQ_BLOCK;
-                        double A = a[0], U = a[FIVEEQ_BLOCK], Vq = a[2 * FIVEEQ_BLOCK];
-                        misfit_update(o_t, p_t, b_t, lane_member(Tn, j), A, U, Vq);
-                        a[0] = A;
-                        a[FIVEEQ_BLOCK] = U;
-                        a[2 * FIVEEQ_BLOCK] = Vq;
-                    }
-                }
-            }
+            if constexpr (MISFIT) misfit_step(obs + (int64_t)(tc + k) * 4, Tn, acc, 3 * FIVEEQ_BLOCK, FIVEEQ_BLOCK, true);
             // the output row is wave-uniform: read it once into an SGPR so that the row test is a
             // scalar branch and the row offsets are scalar arithmetic, not 64-bit VALU per lane
             const int row = __builtin_amdgcn_readfirstlane((int)d[7]);
@@ -1203,16 +1200,7 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
                 }
             }
             if constexpr (BINS) {
-                if (active) {
-                    unsigned short* o = bin_ring + (int64_t)((tc + k) % ring_rows) * ld + m;     // scalar row offset
-                    if constexpr (W == 1) {
-                        *o = (unsigned short)hist_bin(rule, Tn);
-                    } else {
-                        const unsigned int b01 = hist_bin2(rule, Tn);
-                        if (full) *reinterpret_cast<unsigned int*>(o) = b01;                // both members: one 4-byte store
-                        else *o = (unsigned short)(b01 & 0xffffu);
-                    }
-                }
+                if (active) store_bin(bin_ring + (int64_t)((tc + k) % ring_rows) * ld + m, rule, Tn, full);
             }
             if (wave_live) {
                 tile[ks * STAT_ROW + (threadIdx.x & 63)] = Tn;

@@ -3,7 +3,14 @@
 instruction mix (VALU by type, SALU, LDS, global).  Runs in the CPU container (cross-compile).
 
     python tools/kernel_isa_stats.py [substring ...]      # default: the 4+1+1 instantiations
+    python tools/kernel_isa_stats.py --digest [FILE.s]    # every kernel: mangled name and sha256 of its assembly
+
+--digest hashes each kernel from its `<name>:` label through `.end_amdhsa_kernel` (code and kernel descriptor), with
+comments and blank lines dropped and the function-numbered labels (.LBB<n>_, .Lfunc_end<n>) made position-independent:
+two builds whose digests all match emit the same machine code for every kernel.  FILE.s is an assembly hipcc wrote with
+--save-temps (fiveeq_capi-hip-amdgcn-amd-amdhsa-gfx950.s); without it the tree is compiled first.
 """
+import hashlib
 import os
 import re
 import subprocess
@@ -13,16 +20,34 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def main():
-    want = sys.argv[1:] or ["Li4ELi1ELi1E"]
+KERNEL = re.compile(r"^(_Z\w+):\s*; @\1\n(.*?)\.end_amdhsa_kernel", re.S | re.M)
+
+
+def compile_asm():
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"), "--save-temps", "-o",
                os.path.join(tmp, "lib.so"), os.path.join(ROOT, "fiveeqscm_amd", "csrc", "fiveeq_capi.hip")]
         cmd += [f"-D{d}" for d in os.environ.get("FIVEEQ_DEFS", "").split() if d]
         subprocess.run(cmd, cwd=tmp, check=True, stderr=subprocess.DEVNULL)
-        asm = open(os.path.join(tmp, "fiveeq_capi-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-    for m in re.finditer(r"^(_Z\w+):\s*; @\1\n(.*?)\.end_amdhsa_kernel", asm, re.S | re.M):
+        return open(os.path.join(tmp, "fiveeq_capi-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+
+
+def digest(asm):
+    for m in KERNEL.finditer(asm):
+        lines = (line.split(";")[0].rstrip() for line in m.group(0).splitlines())
+        text = "\n".join(line for line in lines if line.strip())
+        text = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", re.sub(r"\.LBB\d+_", ".LBB_", text))
+        print(m.group(1), hashlib.sha256(text.encode()).hexdigest())
+
+
+def main():
+    if sys.argv[1:2] == ["--digest"]:
+        digest(open(sys.argv[2]).read() if len(sys.argv) > 2 else compile_asm())
+        return
+    want = sys.argv[1:] or ["Li4ELi1ELi1E"]
+    asm = compile_asm()
+    for m in KERNEL.finditer(asm):
         name, body = m.group(1), m.group(2)
         if not any(w in name for w in want):
             continue
