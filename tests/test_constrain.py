@@ -232,3 +232,51 @@ def test_constrained_summary_over_gloo_world2(empty_rank):
     assert all(p[0].tolist() == [float(keep.sum())] * 3 for p in parts)
     assert np.array_equal(parts[0][1], want) and parts[1][1] is None
     assert np.allclose(parts[0][2], full[:, keep].mean(1), rtol=1e-13)
+
+
+def test_exact_score_helper_and_its_bound_on_the_reference_arithmetic():
+    """oracle/misfit_exact.py, the exact-arithmetic reference R3 of tests/test_misfit_gpu.py, without a GPU: its integer
+    sums are plain Fraction arithmetic, and misfit_numpy + chi2_from_misfit (the fp64 arithmetic the kernels restate) stays
+    inside its derived bound (chi2_bound; the derivation is in tests/test_misfit_gpu.py::test_r3_score) on C-oracle T —
+    400 steps of 64 members of each misfit layout, on the observed fixture, a window from step 0, a one-step window, and a
+    table that forces cancellation: T and o_t shifted by a common 10 K, so that V >> chi2."""
+    from fractions import Fraction
+
+    from fiveeqscm_amd import emissions
+    from oracle import c_oracle
+    from oracle import misfit_exact as mx
+    n_steps, N = 400, 64
+    years = 1750.0 + np.arange(n_steps)
+    rng = np.random.default_rng(5)
+    y, To, s = scenario.read_observations_csv(FIXTURE)
+    for kind, G in (("co2", 1), ("multigas", 3)):
+        p = prm.sample_ensemble(prm.default_params(kind), N)
+        T = c_oracle.run(emissions.rcp_like_emissions(n_steps, G), p, N, keep=("T",))["T"]
+        oy = np.arange(1750.0, 2150.0, 3.0)
+        cases = {
+            "fixture": (T, Observations.from_years(years, y, To, s, baseline=(1900, 1950))),
+            "from_step_0": (T, Observations.from_years(years, oy, rng.normal(0.5, 0.5, oy.size), rng.uniform(0.05, 0.3, oy.size),
+                                                       baseline=(1750, 1760))),
+            "one_step": (T, Observations.from_years(years, [2000.0], [0.7], [0.1], baseline=(2000, 2000))),
+        }
+        Ts = T + 10.0                                              # a common 10 K offset on T ...
+        steps = np.arange(150, 320)
+        ref = Ts[150:201, 0].mean()
+        o = Ts[steps, 0] - ref + 10.0 + rng.normal(0.0, 0.01, steps.size)      # ... and on o_t: d = T - o ~ mean_ref T
+        cases["cancel"] = (Ts, Observations.from_years(years, years[steps], o - 10.0, 0.1, baseline=(1900, 1950)))
+        for name, (TT, obs) in cases.items():
+            mis = constrain.misfit_numpy(TT, obs.table)
+            chi2 = constrain.chi2_from_misfit(mis, obs.P)
+            if name == "cancel":
+                assert np.all(mis[2] > 100 * chi2), float((mis[2] / chi2).min())          # V >> chi2
+            for m in range(N):
+                exact, bound = mx.chi2_bound(TT[:, m], obs.table, mis[:, m], obs.P)
+                assert abs(Fraction(float(chi2[m])) - exact) <= bound, (kind, name, m)          # the derived bound
+        # the integer sums are Fraction arithmetic
+        tab = cases["fixture"][1].table
+        live = np.nonzero(tab[:, 1] + tab[:, 2])[0]
+        for m in (0, N - 1):
+            F = [Fraction(float(v)) for v in T[live, m]]
+            A = sum(Fraction(float(tab[t, 2])) * f for t, f in zip(live, F))
+            want = sum(Fraction(float(tab[t, 1])) * (f - A - Fraction(float(tab[t, 0]))) ** 2 for t, f in zip(live, F))
+            assert mx.chi2_exact(T[:, m], tab) == want
