@@ -4,7 +4,10 @@
 The record is the synthetic one committed for the tests (tests/golden/obs_synthetic.csv, made by
 tests/golden/make_obs_synthetic.py: one known member plus 0.1 K noise over 1900..2069).  Needs an MI355X.
 
-    python example/constrained_ensemble.py [--members N] [--dtype f64|f32]
+    python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing]
+
+--forcing adds forcing uncertainty (EnsembleEngine(forcing=), fiveeqscm_amd/forcing.py): an aerosol-like cooling scaled per
+member, and the accepted range of ECS with a shared and with a sampled scale.
 """
 import argparse
 import os
@@ -24,6 +27,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--members", type=int, default=100_000)
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--forcing", action="store_true",
+                    help="also sample an aerosol scale per member and print the accepted range of ECS with and without it")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -46,6 +51,29 @@ def main():
         q = s["percentiles"][0].tolist()
         print(f"  T({int(run_years[last])}) {label:13s} 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} K")
     eng.close()
+    if a.forcing:
+        forcing_uncertainty(p, N, n_steps, dtype, obs)
+
+
+def forcing_uncertainty(p, N, n_steps, dtype, obs):
+    """--forcing: the same design with an aerosol-like cooling that every member scales by its own factor in 0.3..2.0 (one more
+    dimension of the hypercube).  A member with high sensitivity and strong cooling fits the record as well as one with low
+    sensitivity and weak cooling, so the accepted range of ECS is wider than with a forcing every member shares."""
+    from fiveeqscm_amd.forcing import ExternalForcings
+    E = emissions.rcp_like_emissions(n_steps, 3)
+    aerosol = ExternalForcings(-0.9 * E[:, 0] / E[:, 0].max(), ("aerosol",))
+    scales = params.sample_forcing_scales(3, N, ranges=[(1.0, 1.0)] * 3 + [(0.3, 2.0)], device="cuda:0")
+    ecs = p["ECS"]
+    print("accepted range of ECS (5 / 95 % of the accepted members), aerosol scale shared (1.0) against sampled (0.3..2.0):")
+    for label, fx_scale in (("shared", np.ones(1)), ("sampled", scales[3:].to(dtype))):
+        eng = EnsembleEngine(dict(p, fx_scale=fx_scale), N, E, dtype=dtype, observations=obs, forcing=aerosol,
+                             store_trajectory=False, device="cuda:0")
+        eng.run(mode="auto")
+        keep = constrain.accept_rejection(eng.chi2(), constrain.ACCEPT_SEED, 0, N)
+        kept = ecs[keep]
+        lo, hi = (float(torch.quantile(kept, q)) for q in (0.05, 0.95)) if kept.numel() else (float("nan"),) * 2
+        print(f"  {label:8s} accepted {int(keep.sum()):7d}  ECS {lo:.2f} .. {hi:.2f} K")
+        eng.close()
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ MAX_POOLS = 4
 N_BOX = 2
 DRIVE_STRIDE = 8
 LHS_MAX_TOTAL = 1 << 28
+MAX_FEXT = 4
 
 OK = 0
 E_INVALID = -1
@@ -109,6 +110,12 @@ SIGNATURES = {
     "fiveeq_plan_create_scen_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [ctypes.POINTER(_p)]),
     "fiveeq_plan_create_scen_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [ctypes.POINTER(_p)]),
     "fiveeq_max_scenarios": (_i32, []),
+    "fiveeq_run_forc_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, _i32, _i32, _p]),
+    "fiveeq_run_forc_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, _i32, _i32, _p]),
+    "fiveeq_plan_create_forc_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, ctypes.POINTER(_p)]),
+    "fiveeq_plan_create_forc_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, ctypes.POINTER(_p)]),
+    "fiveeq_forcing_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32)]),
+    "fiveeq_max_fext": (_i32, []),
     "fiveeq_small_lanes": (_i32, [_i32, ctypes.POINTER(_i32)]),
     "fiveeq_set_f32_packing": (ctypes.c_int, [ctypes.c_int]),
     "fiveeq_set_row_policy": (ctypes.c_int, [_i32]),

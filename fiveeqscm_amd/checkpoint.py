@@ -29,6 +29,9 @@ class CheckpointMixin:
         if self.misfit is not None:                              # the misfit accumulators are state: always carried
             out["misfit"] = self.misfit.cpu().numpy()
             out["obs_sha256"] = self.observations.sha256
+        if self.forcing is not None:                             # which forcing set the state was run under
+            out["forcing_sha256"] = self.forcing.sha256
+            out["fscale_sha256"] = self.fscale_sha256()
         if self.scenario_axis:                                   # which scenario set the per-scenario state belongs to
             out["n_scenarios"] = int(self.n_scenarios)
             out["drive_sha256"] = self.drive_sha256
@@ -66,6 +69,10 @@ class CheckpointMixin:
         mine = None if self.observations is None else self.observations.sha256
         if state.get("obs_sha256") != mine:
             raise ValueError(f"checkpoint observation table {state.get('obs_sha256')!r} is not this engine's ({mine!r})")
+        mine = None if self.forcing is None else (self.forcing.sha256, self.fscale_sha256())
+        theirs = (state.get("forcing_sha256"), state.get("fscale_sha256")) if "forcing_sha256" in state else None
+        if theirs != mine:
+            raise ValueError(f"checkpoint forcing set (table sha256, scale rows sha256) {theirs!r} is not this engine's {mine!r}")
         mine = (self.n_scenarios, self.drive_sha256) if self.scenario_axis else None
         theirs = (int(state["n_scenarios"]), state.get("drive_sha256")) if "n_scenarios" in state else None
         if theirs != mine:

@@ -160,6 +160,15 @@ struct MisfitRows {
     double* misfit = nullptr;
 };
 
+// the per-member forcing scales (step_kernel / fused_kernel <..., FORC = true>): fscale [G + n_fext][ld] in kernel precision, gas
+// rows first, and the shared table fext [n_steps][MAX_FEXT]
+template <typename T>
+struct ForcRows {
+    const T* fscale = nullptr;
+    const T* fext = nullptr;
+    int n_fext = 0;
+};
+
 // everything one C-ABI call hands its launches: filled by make_args() and the checker of each optional feature
 template <typename T>
 struct RunArgs {
@@ -180,6 +189,7 @@ struct RunArgs {
     T* cumE = nullptr;           // the inverse form's cumulative emissions
     BinRing br;                  // the histogram forms' ring (else none)
     MisfitRows mf;               // the constrained forms' accumulators (else none)
+    ForcRows<T> fc;              // the forcing forms' scale rows and table (else none)
 };
 
 // ---- packed fp32 lanes: two members per lane (fiveeq_device.hpp, "Lane value types") ----------------------------
@@ -232,15 +242,20 @@ constexpr bool misfit_layout(int p0, int p1, int p2) { return (p0 == 4 && p1 == 
 // workgroup on top of 20 KiB) would cost the packed form two waves per SIMD (6 -> 4); those runs take the one-member-per-lane
 // fp32 fused kernel, which keeps its plain counterpart's 7 waves (same bits either way: packed lanes mirror the scalar ones).
 constexpr bool misfit_packed_fused(int p0, int p1, int p2) { return p0 == 4 && p1 == 1 && p2 == 1; }
+// the layouts with FORC instantiations: those that have the misfit form, with which it combines
+constexpr bool forcing_layout(int p0, int p1, int p2) { return misfit_layout(p0, p1, p2); }
 
 // ---- the two launchers: one step of the per-step kernel, one span [t_begin, t_end) of the time-fused kernel ----------------
 // The compile-time flags pick the kernel family; packing, the row policy and the pool layout are decided here per launch.
 // SCEN: the scenario axis (step_scen_kernel; the fused kernel with the scenario as blockIdx.y).
-template <typename T, bool BINS = false, bool MISFIT = false, bool SCEN = false>
+// FORC: the per-member forcing scales (with or without MISFIT).
+template <typename T, bool BINS = false, bool MISFIT = false, bool SCEN = false, bool FORC = false>
 int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
     static_assert(BINS + MISFIT + SCEN <= 1, "the histogram ring, the misfit and the scenario axis are separate forms");
-    const bool packed = LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0);
+    static_assert(!FORC || (!BINS && !SCEN), "the forcing scales combine with the misfit only");
+    const bool packed = LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0) &&
+                        (!FORC || (((uintptr_t)a.fc.fscale) & 7) == 0);
     unsigned blocks;
     if (int rc = grid_blocks(a.n, (int64_t)FIVEEQ_STEP_BLOCK * (packed ? 2 : 1), blocks)) return rc;
     const dim3 grid(blocks), block(FIVEEQ_STEP_BLOCK);
@@ -251,17 +266,20 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
             hipLaunchKernelGGL((step_scen_kernel<V, p0, p1, p2, NT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, \
                                a.n_scen, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats);                              \
         else                                                                                                                      \
-            hipLaunchKernelGGL((step_kernel<V, p0, p1, p2, BINS, NT, MISFIT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t,   \
-                               a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.br.ring, a.br.ring_rows,   \
-                               a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit);                                          \
+            hipLaunchKernelGGL((step_kernel<V, p0, p1, p2, BINS, NT, MISFIT, FORC>), grid, block, 0, st, a.km, a.drive,           \
+                               a.n_steps, t, a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.br.ring,     \
+                               a.br.ring_rows, a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit, a.fc.fscale, a.fc.fext,   \
+                               a.fc.n_fext);                                                                                      \
     } while (0)
 #define X(p0, p1, p2)                                                                             \
     case (p0) * 100 + (p1) * 10 + (p2):                                                           \
         if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                     \
             return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);         \
+        } else if constexpr (FORC && !forcing_layout(p0, p1, p2)) {                               \
+            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no forcing form", a.code);        \
         } else {                                                                                  \
             /* the streamed row form: plain and scenario launches only (the engine schedules misfit runs chunk-major) */ \
-            if constexpr (!BINS && !MISFIT) {                                                     \
+            if constexpr (!BINS && !MISFIT && !FORC) {                                                   \
                 if (a.stream_rows) {                                                              \
                     if (packed) FIVEEQ_STEP_LAUNCH(P, p0, p1, p2, true);                          \
                     else FIVEEQ_STEP_LAUNCH(T, p0, p1, p2, true);                                 \
@@ -282,28 +300,34 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
     return FIVEEQ_OK;
 }
 
-template <typename T, bool INV = false, bool BINS = false, bool COMP = false, bool MISFIT = false, bool SCEN = false>
+template <typename T, bool INV = false, bool BINS = false, bool COMP = false, bool MISFIT = false, bool SCEN = false,
+          bool FORC = false>
 int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
+    static_assert(!FORC || (!INV && !BINS && !COMP && !SCEN), "the forcing scales are carried by the plain forward form only");
     static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
     static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
     constexpr bool HAS_PACKED = !INV && !std::is_same<P, T>::value;     // the inverse form has no packed instantiation
     // packed lanes store two 2-byte bin indices as one 4-byte word: the ring rows must be 4-byte aligned too; the misfit forms
     // have a packed instantiation for some layouts only (misfit_packed_fused) — decided HERE, before the grid is sized for it
     const bool packed = HAS_PACKED && (!MISFIT || misfit_packed_fused(a.code / 100, a.code / 10 % 10, a.code % 10)) &&
-                        LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0);
+                        LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0) &&
+                        (!FORC || (((uintptr_t)a.fc.fscale) & 7) == 0);
     unsigned blocks;
     if (int rc = grid_blocks(a.n, (int64_t)FIVEEQ_BLOCK * (packed ? 2 : 1), blocks)) return rc;
     const dim3 grid(blocks, (unsigned)a.n_scen), block(FIVEEQ_BLOCK);     // the scenarios are rows of the grid
     switch (a.code) {
 #define FIVEEQ_FUSED_LAUNCH(V, p0, p1, p2, I)                                                                                    \
-    hipLaunchKernelGGL((fused_kernel<V, p0, p1, p2, I, BINS, COMP, MISFIT, SCEN>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km,  \
-                       a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.cumE, a.C_traj, a.T_traj, a.n_rows,  \
-                       a.stats, a.br.ring, a.br.ring_rows, a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit)
+    hipLaunchKernelGGL((fused_kernel<V, p0, p1, p2, I, BINS, COMP, MISFIT, SCEN, FORC>), grid, block, FIVEEQ_FUSED_DYN_LDS, st,  \
+                       a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.cumE, a.C_traj, a.T_traj,      \
+                       a.n_rows, a.stats, a.br.ring, a.br.ring_rows, a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit,    \
+                       a.fc.fscale, a.fc.fext, a.fc.n_fext)
 #define X(p0, p1, p2)                                                                                  \
     case (p0) * 100 + (p1) * 10 + (p2):                                                                \
         if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                          \
             return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);              \
+        } else if constexpr (FORC && !forcing_layout(p0, p1, p2)) {                                    \
+            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no forcing form", a.code);             \
         } else {                                                                                       \
             if constexpr (HAS_PACKED && (!MISFIT || misfit_packed_fused(p0, p1, p2))) {                \
                 if (packed) {                                                                          \
@@ -403,6 +427,22 @@ int check_misfit(RunArgs<T>& a, const double* obs, double* misfit) {
     return FIVEEQ_OK;
 }
 
+// the per-member forcing scales: the scale rows, the shared table of n_fext categories, and a pool layout that carries them
+template <typename T>
+int check_forcing(RunArgs<T>& a, const T* fscale, const T* fext, int32_t n_fext) {
+    if (n_fext < 0 || n_fext > MAX_FEXT) return fail(FIVEEQ_E_INVALID, "n_fext=%d outside 0..%d", n_fext, MAX_FEXT);
+    if (!fscale) return fail(FIVEEQ_E_INVALID, "fscale is NULL");
+    if (((uintptr_t)fscale) & (sizeof(T) - 1)) return fail(FIVEEQ_E_INVALID, "fscale must be %d-byte aligned", (int)sizeof(T));
+    if (n_fext > 0 && !fext) return fail(FIVEEQ_E_INVALID, "fext is NULL with n_fext=%d", n_fext);
+    if (((uintptr_t)fext) & (sizeof(T) - 1)) return fail(FIVEEQ_E_INVALID, "fext must be %d-byte aligned", (int)sizeof(T));
+    if (!forcing_layout(a.code / 100, a.code / 10 % 10, a.code % 10))
+        return fail(FIVEEQ_E_INVALID, "pool layout %03d has no forcing form (pools {4} and 4+1+1 have)", a.code);
+    a.fc.fscale = fscale;
+    a.fc.fext = n_fext > 0 ? fext : fscale;      // n_fext == 0: no kernel reads the table (no record, no staging); kept non-NULL
+    a.fc.n_fext = n_fext;
+    return FIVEEQ_OK;
+}
+
 // the scenario axis: one parameter ensemble under n_scen emission scenarios (step_scen_kernel, fused_kernel<.., SCEN>)
 constexpr int MAX_SCENARIOS = 64;
 int check_scen(int32_t n_scen) {
@@ -421,11 +461,38 @@ int check_form(int32_t form, int32_t k_steps, int32_t k_min) {
 // ---- the entry points (validated: nothing is launched before every check has passed) ---------------------------------------
 // the forward model, plain, constrained (MISFIT) or under several scenarios (SCEN): one launch per step, or the fused kernel
 // over spans of k_steps steps
-template <typename T, bool MISFIT = false, bool SCEN = false>
+template <typename T, bool MISFIT = false, bool SCEN = false, bool FORC = false>
 int run_form(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
     if (form == FIVEEQ_FORM_PER_STEP)
-        return each_step(a, [&](int t) { return launch_step<T, false, MISFIT, SCEN>(a, t, st); });
-    return each_span(a, k_steps, [&](int t0, int t1) { return launch_fused<T, false, false, false, MISFIT, SCEN>(a, t0, t1, st); });
+        return each_step(a, [&](int t) { return launch_step<T, false, MISFIT, SCEN, FORC>(a, t, st); });
+    return each_span(a, k_steps,
+                     [&](int t0, int t1) { return launch_fused<T, false, false, false, MISFIT, SCEN, FORC>(a, t0, t1, st); });
+}
+
+// the forcing forms carry the misfit or not by what the call hands them: obs and misfit both NULL, or both set
+template <typename T>
+int run_form_forc(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
+    return a.mf.misfit ? run_form<T, true, false, true>(a, form, k_steps, st) : run_form<T, false, false, true>(a, form, k_steps, st);
+}
+template <typename T>
+int check_forc_call(RunArgs<T>& a, const T* fscale, const T* fext, int32_t n_fext, const double* obs, double* misfit) {
+    if (int rc = check_forcing(a, fscale, fext, n_fext)) return rc;
+    if ((obs == nullptr) != (misfit == nullptr))
+        return fail(FIVEEQ_E_INVALID, "obs and misfit go together: both NULL (no misfit) or both set (obs=%p misfit=%p)",
+                    (const void*)obs, (void*)misfit);
+    return obs ? check_misfit(a, obs, misfit) : FIVEEQ_OK;
+}
+
+// fiveeq_run_forc: the forward model with per-member forcing scales
+template <typename T>
+int run_forc(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+             const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, const T* fscale, const T* fext,
+             int32_t n_fext, const double* obs, double* misfit, int32_t form, int32_t k_steps, void* stream) {
+    RunArgs<T> a;
+    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    if (int rc = check_forc_call(a, fscale, fext, n_fext, obs, misfit)) return rc;
+    if (int rc = check_form(form, k_steps, 0)) return rc;
+    return run_form_forc(a, form, k_steps, (hipStream_t)stream);
 }
 
 // fiveeq_step/run/run_fused/run_ksteps (k_min 1), fiveeq_run_obs (MISFIT: obs, misfit) and fiveeq_run_scen (SCEN: n_scen,
@@ -563,11 +630,13 @@ struct Plan {
 };
 constexpr uint32_t PLAN_MAGIC = 0x35455146u;  // "FQE5"
 
-// the plan of run_form<T, MISFIT, SCEN>(FIVEEQ_FORM_PER_STEP): that very run, enqueued on a capture stream
-template <typename T, bool MISFIT = false, bool SCEN = false>
+// the plan of run_form<T, MISFIT, SCEN>(FIVEEQ_FORM_PER_STEP): that very run, enqueued on a capture stream (FORC: of
+// run_form_forc, the misfit carried when obs and misfit are set)
+template <typename T, bool MISFIT = false, bool SCEN = false, bool FORC = false>
 int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
                 int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void** plan_out,
-                const double* obs = nullptr, double* misfit = nullptr, int32_t n_scen = 1) {
+                const double* obs = nullptr, double* misfit = nullptr, int32_t n_scen = 1, const T* fscale = nullptr,
+                const T* fext = nullptr, int32_t n_fext = 0) {
     if (SCEN) {
         if (plan_out) *plan_out = nullptr;
         if (int rc = check_scen(n_scen)) return rc;
@@ -578,6 +647,7 @@ int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
     if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats, n_scen))
         return rc;
     if (int rc = MISFIT ? check_misfit(a, obs, misfit) : FIVEEQ_OK) return rc;
+    if (int rc = FORC ? check_forc_call(a, fscale, fext, n_fext, obs, misfit) : FIVEEQ_OK) return rc;
     if (t_begin == t_end) return fail(FIVEEQ_E_INVALID, "empty step range for a plan");
     hipStream_t cap = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
@@ -587,7 +657,9 @@ int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
         (void)hipStreamDestroy(cap);
         return fail(FIVEEQ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(e));
     }
-    const int rc = run_form<T, MISFIT, SCEN>(a, FIVEEQ_FORM_PER_STEP, 0, cap);
+    int rc;
+    if constexpr (FORC) rc = run_form_forc(a, FIVEEQ_FORM_PER_STEP, 0, cap);
+    else rc = run_form<T, MISFIT, SCEN>(a, FIVEEQ_FORM_PER_STEP, 0, cap);
     e = hipStreamEndCapture(cap, &graph);
     (void)hipStreamDestroy(cap);
     if (rc != FIVEEQ_OK) {
@@ -856,6 +928,42 @@ int fiveeq_plan_create_scen_f32(const fiveeq_model* model, int64_t n_members, in
                                            n_rows, T_stats, plan_out, nullptr, nullptr, n_scen);
 }
 int32_t fiveeq_max_scenarios(void) { return MAX_SCENARIOS; }
+
+int fiveeq_run_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                        int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
+                        double* T_traj, int32_t n_rows, double* T_stats, const double* fscale, const double* fext, int32_t n_fext,
+                        const double* obs, double* misfit, int32_t form, int32_t k_steps, void* stream) {
+    return run_forc<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                         fscale, fext, n_fext, obs, misfit, form, k_steps, stream);
+}
+int fiveeq_plan_create_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                                int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
+                                double* T_traj, int32_t n_rows, double* T_stats, const double* fscale, const double* fext,
+                                int32_t n_fext, const double* obs, double* misfit, void** plan_out) {
+    return plan_create<double, false, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                                n_rows, T_stats, plan_out, obs, misfit, 1, fscale, fext, n_fext);
+}
+int fiveeq_run_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                        int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
+                        float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext, int32_t n_fext,
+                        const double* obs, double* misfit, int32_t form, int32_t k_steps, void* stream) {
+    return run_forc<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+                         fscale, fext, n_fext, obs, misfit, form, k_steps, stream);
+}
+int fiveeq_plan_create_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                                int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
+                                float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext,
+                                int32_t n_fext, const double* obs, double* misfit, void** plan_out) {
+    return plan_create<float, false, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                                n_rows, T_stats, plan_out, obs, misfit, 1, fscale, fext, n_fext);
+}
+int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t* n_pools) {
+    if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;
+    int p[3] = {0, 0, 0};
+    for (int g = 0; g < n_gas; ++g) p[g] = n_pools[g];
+    return forcing_layout(p[0], p[1], p[2]) ? 1 : 0;
+}
+int32_t fiveeq_max_fext(void) { return MAX_FEXT; }
 
 int32_t fiveeq_small_lanes(int32_t n_gas, const int32_t* n_pools) {
     if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;

@@ -444,25 +444,46 @@ __device__ __forceinline__ V gas_step(const KModel<typename Lane<V>::S>& km, con
     return Fg;
 }
 
-template <typename V, typename L, bool INV, bool COMP>
+// FORC = true (round 8) is the form with PER-MEMBER FORCING SCALES: the member carries G + K factors, sg_g per gas and sx_k per
+// external forcing category (0 <= K <= MAX_FEXT), and the run a shared table X [n_steps][MAX_FEXT] of category forcings:
+//     F = F_ext(t);   F = fma(sx_k, X[t][k], F), k = 0 .. K-1;   F = fma(sg_g, F_g, F), g = 0 .. G-1
+// with F_g exactly what gas_step() returns.  fma(1, F_g, F) is F + F_g with the same single rounding, so unit scales with
+// K = 0 (or an all-zero table) give the bits of the plain step.  Scale j of the lane is fs[j * fs_stride] (gas rows first:
+// registers with stride 1, or a lane-private LDS slot), xr the step's table record (wave-uniform), n_fext = K is
+// wave-uniform: the category loop is scalar branches.  Nothing else of the step differs; FORC = false is the code as it was.
+constexpr int MAX_FEXT = 4;
+template <typename V, typename L, bool INV, bool COMP, bool FORC = false>
 __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& km, const typename Lane<V>::S* __restrict__ drv,
                                             const V (&rr)[3 * L::G], const V (&qq)[2],
                                             V (&R)[L::SP], V (&S)[2], V (&out)[L::G], V& Tnew, V (&cum)[L::G],
-                                            V (&Rlo)[L::SP]) {
+                                            V (&Rlo)[L::SP], const V* fs = nullptr, const int fs_stride = 1,
+                                            const typename Lane<V>::S* xr = nullptr, const int n_fext = 0) {
+    static_assert(!FORC || (!INV && !COMP), "the forcing scales are carried by the plain forward form only");
     const V T_old = S[0] + S[1];
     V F = (V)drv[6];
+    if constexpr (FORC) {
+#pragma unroll
+        for (int k = 0; k < MAX_FEXT; ++k)
+            if (k < n_fext) F = fma3<V>(fs[(L::G + k) * fs_stride], xr[k], F);
+    }
     // compiler-only barriers: keep each gas's LDS constant reads inside that gas's code instead of all
     // ~45 being hoisted to the kernel top (VGPR pressure) or out of the fused time loop.  (Issuing gas
     // g+1's reads before gas g's arithmetic was tried: +-1 %, 133 VGPRs; not kept.)
     asm volatile("" ::: "memory");
-    F += gas_step<V, L, 0, INV, COMP>(km, km.gas[0], drv, rr, T_old, R, out, cum, Rlo);
+    const V F0 = gas_step<V, L, 0, INV, COMP>(km, km.gas[0], drv, rr, T_old, R, out, cum, Rlo);
+    if constexpr (FORC) F = fe_fma(fs[0 * fs_stride], F0, F);
+    else F += F0;
     if constexpr (L::G > 1) {
         asm volatile("" ::: "memory");
-        F += gas_step<V, L, 1, INV, COMP>(km, km.gas[1], drv, rr, T_old, R, out, cum, Rlo);
+        const V F1 = gas_step<V, L, 1, INV, COMP>(km, km.gas[1], drv, rr, T_old, R, out, cum, Rlo);
+        if constexpr (FORC) F = fe_fma(fs[1 * fs_stride], F1, F);
+        else F += F1;
     }
     if constexpr (L::G > 2) {
         asm volatile("" ::: "memory");
-        F += gas_step<V, L, 2, INV, COMP>(km, km.gas[2], drv, rr, T_old, R, out, cum, Rlo);
+        const V F2 = gas_step<V, L, 2, INV, COMP>(km, km.gas[2], drv, rr, T_old, R, out, cum, Rlo);
+        if constexpr (FORC) F = fe_fma(fs[2 * fs_stride], F2, F);
+        else F += F2;
     }
     // --- step_temp: S + em1_d (S - q F) ------------------------------------------------
 #pragma unroll
@@ -902,7 +923,11 @@ __device__ __forceinline__ void misfit_step(const double* ob, const V Tn, double
 // step's obs record is wave-uniform and read with scalar loads; on a step outside the window (p_t == 0 && b_t == 0) the
 // rows are neither read nor written, so such a step moves the bytes of the plain kernel.  Inside it: 24 B read + 24 B
 // written per member-step.  Instantiated for the {4} and 4 + 1 + 1 layouts, default row policy only.
-template <typename V, int P0, int P1, int P2, bool BINS = false, bool NT = false, bool MISFIT = false>
+// FORC = true (round 8): the step with per-member forcing scales (member_step<.., FORC>).  The lane also loads its G + n_fext
+// scale rows fscale [G + n_fext][ld] (gas rows first) — issued with the other row loads, before the staging barrier — and
+// the step's record fext [t][0 .. MAX_FEXT) is wave-uniform and read with scalar loads, like the obs record.  w (G + K) bytes
+// more per member-step; combines with MISFIT, not with BINS; default row policy; the {4} and 4 + 1 + 1 layouts.
+template <typename V, int P0, int P1, int P2, bool BINS = false, bool NT = false, bool MISFIT = false, bool FORC = false>
 __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kernel(
     const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
     const int64_t n, const int64_t ld,
@@ -913,11 +938,14 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
     const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
     unsigned short* __restrict__ bin_ring /* BINS: [ring_rows][ld], row t mod ring_rows */, const int ring_rows,
     const double hist_lo, const double hist_inv_w, const int n_bins,
-    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */) {
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */,
+    const typename Lane<V>::S* __restrict__ fscale /* FORC: [G + n_fext][ld] */,
+    const typename Lane<V>::S* __restrict__ fext /* FORC: [n_steps][MAX_FEXT] */, const int n_fext) {
     using L = Layout<P0, P1, P2>;
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     constexpr bool NTT = true;                    // the stored C / T rows: written once, never read by a stepping kernel
+    static_assert(!FORC || (!BINS && !NT), "the forcing scales: no histogram ring, default row policy");
     __shared__ T drv[DRIVE_STRIDE];
     const int64_t m = ((int64_t)blockIdx.x * FIVEEQ_STEP_BLOCK + threadIdx.x) * W;     // this lane's first member
     const bool active = m < n;
@@ -946,13 +974,24 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
     for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_row<V, NT>(r + k * ld + mm);
 #pragma unroll
     for (int k = 0; k < 2; ++k) qq[k] = load_row<V, NT>(q + k * ld + mm);
+    V fs[FORC ? L::G + MAX_FEXT : 1];             // FORC: the lane's scales, gas rows first (rows past n_fext are never read)
+    if constexpr (FORC) {
+#pragma unroll
+        for (int k = 0; k < L::G + MAX_FEXT; ++k) fs[k] = k < L::G + n_fext ? load_row<V, NT>(fscale + k * ld + mm) : (V)T(0);
+    }
 
     if (threadIdx.x < NW) reinterpret_cast<T*>(&km_s)[threadIdx.x] = stage_v;
     if (threadIdx.x < DRIVE_STRIDE) drv[threadIdx.x] = drv_v;
     __syncthreads();
 
     V Tn = (V)T(0);
-    member_step<V, L>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn);
+    if constexpr (FORC) {
+        V no_cum[L::G], no_Rlo[L::SP];            // never touched: INV = COMP = false
+        member_step<V, L, false, false, true>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, 1,
+                                              fext + (int64_t)t * MAX_FEXT, n_fext);
+    } else {
+        member_step<V, L>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn);
+    }
     if (active) {
 #pragma unroll
         for (int k = 0; k < L::SP; ++k) store_row<NT>(R + k * ld + m, Rv[k], full);
@@ -1072,6 +1111,26 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_scen_
     }
 }
 
+// Where the fused kernel keeps a lane's G + MAX_FEXT forcing scales (FORC), and how many steps it stages per refill.
+// Registers by default.  The fp64 4 + 1 + 1 form is the exception: its plain kernel sits at 117 VGPRs, 4 waves per SIMD, and
+// seven fp64 scales in registers took it to 129 (135 with the misfit): 3 waves.  There the scales live in a lane-private LDS
+// slot fs_s[G + MAX_FEXT][FIVEEQ_BLOCK], like the misfit accumulators (consecutive lanes, consecutive words: no bank
+// conflicts, no barrier), read back with one ds_read per fma; and so that four workgroups still fit a CU's 160 KB beside the
+// misfit slot (14 + 6 KB of slots on 17 KB of statistics tile and model), it stages 25 steps per refill instead of 125
+// (2.4 KB of drive and table records instead of 12): 39984 B per workgroup with the misfit, under the 40960 a static_assert in
+// the kernel holds it to.  profiles/r08/forcing_isa.txt has the counts.
+template <typename V, typename L, bool MISFIT, bool FORC>
+struct FusedForc {
+    static constexpr bool FS_LDS = false;
+    static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK;
+};
+template <bool MISFIT>
+struct FusedForc<double, Layout<4, 1, 1>, MISFIT, true> {
+    static constexpr bool FS_LDS = true;
+    static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK < 25 ? FIVEEQ_FUSED_CHUNK : 25;
+};
+constexpr int LDS_PER_CU = 160 * 1024;            // MI355X
+
 // ---------------------------------------------------------------------------------
 // Kernel 2 — TIME-FUSED: one launch advances [t_begin, t_end); a member's state and
 // parameters stay in registers for the whole span, the drive table is staged into LDS
@@ -1100,8 +1159,12 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_scen_
 // scenario-uniform: it stages its own scenario's drive chunk and offsets the state, row and statistics pointers by the
 // scenario strides of kernel 1s (all derived from ld, n_steps and n_rows, so no argument is added).  With SCEN false not
 // one instruction of the kernel changes.
+//
+// FORC = true (round 8; INV, BINS, COMP and SCEN false, with or without MISFIT): per-member forcing scales
+// (member_step<.., FORC>).  The G + n_fext scales are loaded once at launch start and stay on chip for the span; the table chunk
+// fext [tc .. tc + nt)[MAX_FEXT] is staged into LDS beside the drive chunk.  Where the scales live is FS_LDS, below.
 template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false,
-          bool SCEN = false>
+          bool SCEN = false, bool FORC = false>
 __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps,
     const int t_begin, const int t_end, const int64_t n, const int64_t ld,
@@ -1113,11 +1176,16 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
     unsigned short* __restrict__ bin_ring /* BINS: [ring_rows][ld] */, const int ring_rows, const double hist_lo,
     const double hist_inv_w, const int n_bins,
-    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */) {
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */,
+    const typename Lane<V>::S* __restrict__ fscale /* FORC: [G + n_fext][ld] */,
+    const typename Lane<V>::S* __restrict__ fext /* FORC: [n_steps][MAX_FEXT] */, const int n_fext) {
     using L = Layout<P0, P1, P2>;
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     static_assert(!(INV && BINS), "no streamed histograms in the concentration-driven form");
+    static_assert(!FORC || (!INV && !BINS && !COMP && !SCEN), "the forcing scales are carried by the plain forward form only");
+    constexpr int CHUNK = FusedForc<V, L, MISFIT, FORC>::CHUNK;       // steps staged per refill
+    constexpr bool FS_LDS = FusedForc<V, L, MISFIT, FORC>::FS_LDS;    // FORC: the scales in a lane-private LDS slot
     static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
     static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
     if constexpr (SCEN) {
@@ -1129,10 +1197,15 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
         if (T_traj != nullptr) T_traj += sc * n_rows * ld;
         if (stats != nullptr) stats += sc * ((ld + 63) >> 6) * n_steps * 4;
     }
-    __shared__ T drv[FIVEEQ_FUSED_CHUNK * DRIVE_STRIDE];
+    __shared__ T drv[CHUNK * DRIVE_STRIDE];
+    __shared__ T xs[FORC ? CHUNK * MAX_FEXT : 1];                     // FORC: the table chunk
+    __shared__ V fs_s[FS_LDS ? (L::G + MAX_FEXT) * FIVEEQ_BLOCK : 1];  // FS_LDS: [G + MAX_FEXT][FIVEEQ_BLOCK], lane-private
     __shared__ double acc_s[MISFIT ? 3 * W * FIVEEQ_BLOCK : 1];       // MISFIT: [3 W][FIVEEQ_BLOCK], lane-private
     __shared__ V stat_tile[FIVEEQ_BLOCK / 64][STAT_STEPS * STAT_ROW];
     __shared__ KModel<T> km_s;
+    // the LDS slot exists to keep four workgroups (4 waves per SIMD) on a CU: a change that outgrows the budget must not pass
+    static_assert(!FS_LDS || sizeof(drv) + sizeof(xs) + sizeof(fs_s) + sizeof(acc_s) + sizeof(stat_tile) + sizeof(km_s) <=
+                                 LDS_PER_CU / 4, "FS_LDS form: four workgroups no longer fit a CU's LDS");
     stage_model(&km_s);
     const KModel<T>& kmr = km_s;
 
@@ -1166,6 +1239,14 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_lane<V>(r + k * ld + mm);
 #pragma unroll
     for (int k = 0; k < 2; ++k) qq[k] = load_lane<V>(q + k * ld + mm);
+    V fs_r[FORC && !FS_LDS ? L::G + MAX_FEXT : 1];
+    V* const fs = FS_LDS ? &fs_s[threadIdx.x] : fs_r;    // FORC: scale j of this lane at fs[j * FS_STRIDE]
+    constexpr int FS_STRIDE = FS_LDS ? FIVEEQ_BLOCK : 1;
+    if constexpr (FORC) {
+#pragma unroll
+        for (int k = 0; k < L::G + MAX_FEXT; ++k)
+            fs[k * FS_STRIDE] = k < L::G + n_fext ? load_lane<V>(fscale + k * ld + mm) : (V)T(0);
+    }
     double* const acc = &acc_s[threadIdx.x];             // MISFIT: word k of member j of this lane at acc[(3 j + k) * FIVEEQ_BLOCK]
     if constexpr (MISFIT) {
 #pragma unroll
@@ -1176,15 +1257,24 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
         }
     }
 
-    for (int tc = t_begin; tc < t_end; tc += FIVEEQ_FUSED_CHUNK) {
-        const int nt = min(FIVEEQ_FUSED_CHUNK, t_end - tc);
+    for (int tc = t_begin; tc < t_end; tc += CHUNK) {
+        const int nt = min(CHUNK, t_end - tc);
         __syncthreads();                                  // previous chunk fully consumed
         for (int i = threadIdx.x; i < nt * DRIVE_STRIDE; i += FIVEEQ_BLOCK)
             drv[i] = drive[(int64_t)tc * DRIVE_STRIDE + i];
+        if constexpr (FORC) {
+            // n_fext == 0: member_step reads no record and fext may be NULL — nothing is staged (a wave-uniform test)
+            if (n_fext > 0)
+                for (int i = threadIdx.x; i < nt * MAX_FEXT; i += FIVEEQ_BLOCK) xs[i] = fext[(int64_t)tc * MAX_FEXT + i];
+        }
         __syncthreads();
         for (int k = 0; k < nt; ++k) {
             const T* d = &drv[k * DRIVE_STRIDE];
-            member_step<V, L, INV, COMP>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo);
+            if constexpr (FORC)
+                member_step<V, L, false, false, true>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo, fs, FS_STRIDE, &xs[k * MAX_FEXT],
+                                                      n_fext);
+            else
+                member_step<V, L, INV, COMP>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo);
             if constexpr (MISFIT) misfit_step(obs + (int64_t)(tc + k) * 4, Tn, acc, 3 * FIVEEQ_BLOCK, FIVEEQ_BLOCK, true);
             // the output row is wave-uniform: read it once into an SGPR so that the row test is a
             // scalar branch and the row offsets are scalar arithmetic, not 64-bit VALU per lane

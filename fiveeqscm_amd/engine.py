@@ -99,7 +99,7 @@ class EnsembleEngine(CheckpointMixin):
                  device=None, store_trajectory=True, output_steps=None, store_concentrations=True,
                  collect_stats=False, hist=None, hist_ring_steps="auto", concentration_driven=False,
                  chunk_members="auto", per_step_streams="auto", fused_span="auto", small_lanes="auto", compensated=False,
-                 R0=None, S0=None, lib_path=None, observations=None, scenario_names=None):
+                 R0=None, S0=None, lib_path=None, observations=None, scenario_names=None, forcing=None):
         """store_trajectory / output_steps: True stores C, T of every step; a list of step indices
         stores only those (rows in increasing step order, see `out_steps`); False stores nothing.
         store_concentrations=False keeps only the T rows (a 100M-member fp32 run then stores 4 B instead
@@ -154,7 +154,14 @@ class EnsembleEngine(CheckpointMixin):
         gather_summary() and T_histogram() then take scenario=).  F_ext: [n_steps] (shared) or [S, n_steps]; R0 / S0: one
         [SP, N] / [2, N] state for every scenario, or [S, ...].  scenario_names: S labels (default "0", "1", ...).  Modes
         'per_step', 'graph', 'fused', 'ksteps' and 'auto' (never 'small'); not with concentration_driven=True, hist=,
-        observations= or compensated=True.  `n_scenarios` is S (1 for an engine without the scenario axis)."""
+        observations= or compensated=True.  `n_scenarios` is S (1 for an engine without the scenario axis).
+        forcing: a forcing.ExternalForcings table [n_steps, K] (K <= 4 categories, K = 0 allowed).  Every member then scales
+        the forcing of gas g by params["f_scale"][g] and category k by params["fx_scale"][k] ([G] / [K] shared or [G, N] /
+        [K, N] per member, default 1; include/fiveeq.h "FORCING SCALES"): F = F_ext + sum_k sx_k X[t, k] + sum_g sg_g F_g, every
+        term one fma.  `fscale` [G + K, N] holds the rows, gas rows first.  Modes 'per_step', 'graph', 'fused', 'ksteps' and
+        'auto' (never 'small'), the same bits in each; works with observations=, chunk-major schedules, the two-stream
+        halves, step sub-ranges and R0 / S0; unit scales with K = 0 or a zero table are the plain run bit for bit.  Pool
+        layouts {4} and 4 + 1 + 1; not with hist=, concentration_driven=True, compensated=True or the scenario axis."""
         if dtype not in _DTYPES:
             raise ValueError("dtype must be torch.float64 or torch.float32")
         self.lib = _capi.load(lib_path)    # raises if the HIP library is not built
@@ -279,11 +286,38 @@ class EnsembleEngine(CheckpointMixin):
                 self.observations = observations
                 self.obs = torch.from_numpy(np.array(table, order="C")).to(dev)      # uploaded once
                 self.misfit = torch.zeros((3, N), dtype=torch.float64, device=dev)
+            self.forcing, self.fscale, self.fext = None, None, None
+            if forcing is not None:
+                for flag, why in ((hist is not None, "hist="), (self.concentration_driven, "concentration_driven=True"),
+                                  (self.compensated, "compensated=True"),
+                                  (self.scenario_axis, "emissions of several scenarios (the scenario axis)")):
+                    if flag:
+                        raise ValueError(f"forcing= cannot be combined with {why}: the forcing scales are carried by the plain "
+                                         "forward forms (with or without observations=) only")
+                if not self.lib.fiveeq_forcing_layout_supported(G, n_pools):
+                    raise ValueError(f"forcing=: pool layout {self.pools} has no forcing form (pools [4] and [4, 1, 1] have)")
+                if forcing.n_steps != self.n_steps:
+                    raise ValueError(f"forcing: table of {forcing.n_steps} steps for a run of {self.n_steps}")
+                Kx = forcing.n_categories
+                self.forcing = forcing
+                self.fext = torch.from_numpy(forcing.padded()).to(dev, dt_).contiguous()          # uploaded once
+                rows = [_rows(params.get("f_scale", np.ones(G)), G, N, "f_scale")]
+                if Kx:
+                    rows.append(_rows(params.get("fx_scale", np.ones(Kx)), Kx, N, "fx_scale"))
+                elif "fx_scale" in params and np.size(params["fx_scale"]):
+                    raise ValueError("fx_scale given, but the forcing table has no category")
+                as_t = lambda v: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v, order="C"))).to(dev, dt_)  # noqa: E731
+                self.fscale = torch.cat([as_t(v) for v in rows]).contiguous()                   # [G + K, N], gas rows first
+                if not bool(torch.isfinite(self.fscale).all()):
+                    raise ValueError("f_scale / fx_scale: non-finite scale factors")
+            elif "f_scale" in params or "fx_scale" in params:
+                raise ValueError("f_scale / fx_scale need forcing= (ExternalForcings; a table without categories will do)")
+        n_frows = 0 if self.fscale is None else int(self.fscale.shape[0])
         if chunk_members == "auto":
-            chunk_members = self.auto_chunk(N, SP, G, dtype, n_scenarios=Sc)
+            chunk_members = self.auto_chunk(N, SP, G, dtype, n_scenarios=Sc, extra_rows=n_frows)
         self.chunk_members = int(chunk_members or 0) // 256 * 256
         if per_step_streams == "auto":
-            t_step = (min(N, self.chunk_members or N) * self._w * (Sc * (2 * SP + G + 5) + 3 * G + 2)
+            t_step = (min(N, self.chunk_members or N) * self._w * (Sc * (2 * SP + G + 5) + 3 * G + 2 + n_frows)
                       / HBM_STREAM_BYTES_PER_S)
             per_step_streams = 2 if t_step >= PER_STEP_SPLIT_MIN_S else 1
         self.per_step_streams = max(1, int(per_step_streams))
@@ -332,12 +366,13 @@ class EnsembleEngine(CheckpointMixin):
         return s
 
     @staticmethod
-    def auto_chunk(n_members, sum_pools, n_gas, dtype, cache_bytes=INFINITY_CACHE_BYTES, n_scenarios=1):
+    def auto_chunk(n_members, sum_pools, n_gas, dtype, cache_bytes=INFINITY_CACHE_BYTES, n_scenarios=1, extra_rows=0):
         """Members per chunk of the chunk-major schedule: the fewest EVEN chunks whose state + parameter rows take at most
         CHUNK_CACHE_SHARE of the Infinity Cache each (a multiple of 256 members); 0 = do not chunk: the ensemble's rows fit the
-        cache by themselves.  With n_scenarios, every member carries that many copies of the state rows."""
+        cache by themselves.  With n_scenarios, every member carries that many copies of the state rows; extra_rows: further
+        parameter rows per member (the forcing scales)."""
         w = 8 if dtype == torch.float64 else 4
-        rows_bytes = n_members * w * (n_scenarios * (sum_pools + 2) + 3 * n_gas + 2)
+        rows_bytes = n_members * w * (n_scenarios * (sum_pools + 2) + 3 * n_gas + 2 + extra_rows)
         if rows_bytes <= cache_bytes:
             return 0
         k = -(-rows_bytes // int(CHUNK_CACHE_SHARE * cache_bytes))
@@ -370,7 +405,7 @@ class EnsembleEngine(CheckpointMixin):
         """Lanes per member mode='small' would run with now (4 or 1); 0 = the small-ensemble kernel does not apply: a run that
         wants in-loop histograms or the concentration-driven form."""
         if (not self.small_widest or self.T_hist is not None or self.concentration_driven or self.observations is not None
-                or self.scenario_axis):
+                or self.scenario_axis or self.forcing is not None):
             return 0
         if self.compensated:                                     # fiveeq_run_small_comp_f32: one member per lane, every layout
             return 1 if self.small_lanes in ("auto", 1) else 0
@@ -477,10 +512,13 @@ class EnsembleEngine(CheckpointMixin):
             a = self._run_args(t_begin, t_end, m0, n)
             if self.scenario_axis:
                 return (*a[:3], self.n_scenarios, *a[3:])
+            if self.forcing is not None:                        # (obs, misfit): both NULL without observations=
+                mis = self._obs_args(m0) if self.observations is not None else (None, None)
+                return (*a, self._ptr(self.fscale, m0 * self._w), self._ptr(self.fext), self.forcing.n_categories, *mis)
             return a if self.observations is None else (*a, *self._obs_args(m0))
 
-        if self.scenario_axis or self.observations is not None:
-            sfx = "scen" if self.scenario_axis else "obs"
+        if self.scenario_axis or self.observations is not None or self.forcing is not None:
+            sfx = "scen" if self.scenario_axis else ("forc" if self.forcing is not None else "obs")
             run, plan = self._fn("run_" + sfx), self._fn("plan_create_" + sfx)
 
             def per_step(t, t1, m0, n, s):
@@ -557,6 +595,9 @@ class EnsembleEngine(CheckpointMixin):
                              "time-fused kernel ('fused', 'ksteps') and the small-ensemble kernel ('small', one lane) carry them")
         if self.scenario_axis and mode == "small":
             raise ValueError("mode 'small' has no scenario form: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'")
+        if self.forcing is not None and mode == "small":
+            raise ValueError("mode 'small' does not carry the forcing scales of forcing=: use 'per_step', 'graph', 'fused', "
+                             "'ksteps' or 'auto'")
         if self.observations is not None and mode == "small":
             raise ValueError("mode 'small' does not carry the misfit of observations=: use 'per_step', 'graph', 'fused', "
                              "'ksteps' or 'auto'")
@@ -910,6 +951,14 @@ class EnsembleEngine(CheckpointMixin):
             self.join()
         return torch.stack([self.T_hist[:, 0], self.T_hist[:, -1]], dim=1)
 
+    def fscale_sha256(self):
+        """sha256 (hex) of the forcing scale rows as fp64 host bytes, [G + K, N] (None without forcing=): with
+        `forcing.sha256`, what a checkpoint names the engine's forcing set by."""
+        if self.fscale is None:
+            return None
+        import hashlib                                           # (not cached: `fscale` is the caller's to edit between runs)
+        return hashlib.sha256(self.fscale.double().cpu().numpy().tobytes()).hexdigest()
+
     # -- accounting ----------------------------------------------------------------------
     def bytes_per_member_step(self, mode="per_step", k_steps=None):
         """ALGORITHMIC HBM bytes per member-timestep:
@@ -921,8 +970,11 @@ class EnsembleEngine(CheckpointMixin):
         read per member-step.  With `observations=` the misfit accumulators add, per_step: 48 B (3 fp64 read + written) per
         member and step of the observation window, averaged over the run's steps; the fused forms: 48 B per member and launch.
         With the scenario axis the count is per MEMBER-SCENARIO-step: per_step reads the parameter rows once for all S
-        scenarios, w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / S."""
+        scenarios, w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / S.
+        With `forcing=` the G + K scale rows are parameter rows like r and q: per_step w (G + K) more per member-step, the
+        fused forms w (G + K) more per member and launch."""
         w, G, SP = self._w, self.n_gas, self.sum_pools
+        fr = 0 if self.fscale is None else int(self.fscale.shape[0])
         out = ((G if self.C is not None else 0) + 1) * self.n_rows / self.n_steps      # stored rows only
         extra = (32.0 / 64.0) if self.collect_stats else 0.0
         ring = 4.0 if (self.T_hist is not None and mode in ("fused", "per_step")) else 0.0
@@ -933,7 +985,7 @@ class EnsembleEngine(CheckpointMixin):
         if mode == "per_step" and self.scenario_axis:
             return w * (2 * SP + 4 + out) + w * (3 * G + 2) / self.n_scenarios + extra
         if mode == "per_step":
-            return w * (2 * SP + 3 * G + 6 + out) + extra + ring
+            return w * (2 * SP + 3 * G + 6 + fr + out) + extra + ring
         if mode == "fused":
             span = min(self.hist_ring_steps, self.n_steps) if self.T_hist is not None else self.fused_span_steps(self.n_steps)
         elif mode == "ksteps":
@@ -944,7 +996,7 @@ class EnsembleEngine(CheckpointMixin):
             raise ValueError(f"no byte count for mode {mode!r}")
         if self.observations is not None:
             extra += 48.0 / max(int(span), 1)
-        return w * (out + (2 * SP + 3 * G + 6) / max(int(span), 1)) + extra + ring
+        return w * (out + (2 * SP + 3 * G + 6 + fr) / max(int(span), 1)) + extra + ring
 
 
 def run_ensemble(emissions, params, n_members, *, F_ext=None, dt=1.0, dtype=torch.float64, device=None,

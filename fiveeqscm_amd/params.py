@@ -331,6 +331,30 @@ def sample_ensemble_shard(base, n_total, lo=0, hi=None, seed=LHS_SEED, device=No
     return out
 
 
+def sample_forcing_scales(base_or_G, n_total, lo=0, hi=None, ranges=(), seed=LHS_SEED, device=None):
+    """Forcing scale rows for members [lo, hi) of the n_total-member design: row j is uniform on ranges[j] = (a, b), drawn on
+    the shard-computable hypercube in dimension 3G + 2 + j — the dimensions AFTER those of `sample_ensemble_shard`, whose
+    draws for the same seed therefore stay as they are.  base_or_G: the parameter set, or its number of gases.  Returns
+    [len(ranges), hi - lo] fp64 — NumPy rows (device=None) or a tensor on `device`, bit-identical — independent of the
+    shard split.  By convention the first G rows are the gas scales (`f_scale`), the rest the category scales (`fx_scale`).
+    Uniform priors only."""
+    G = int(base_or_G) if np.isscalar(base_or_G) else n_gas_of(base_or_G)
+    hi = n_total if hi is None else hi
+    ranges = [(float(a), float(b)) for a, b in ranges]
+    if not ranges:
+        raise ValueError("sample_forcing_scales: no ranges")
+    for a, b in ranges:
+        if not (np.isfinite(a) and np.isfinite(b) and a <= b):
+            raise ValueError(f"range ({a}, {b}): want finite a <= b")
+    dims = list(range(3 * G + 2, 3 * G + 2 + len(ranges)))
+    if device is None:
+        u, stack = lhs_rows(n_total, dims, lo, hi, seed), np.stack
+    else:
+        import torch
+        u, stack = lhs_rows_device(n_total, dims, lo, hi, device, seed), torch.stack
+    return stack([(b - a) * u[j] + a for j, (a, b) in enumerate(ranges)])     # one rounding per operation on both back ends
+
+
 # ------------------------------------------------------------------------------------
 # pack the shared part into the C-ABI struct
 # ------------------------------------------------------------------------------------

@@ -24,12 +24,11 @@ def _is_number(cell):
         return False
 
 
-def read_emissions_csv(path, gases=("CO2", "CH4", "N2O")):
-    """Return (years [n] float64, emissions [n, len(gases)] float64) from an RCP-layout CSV.
-
-    The column-name row is the last non-numeric row before the data whose cells include every
-    requested species (CO2 may be given as FossilCO2 [+ OtherCO2] or as one CO2 column).  Rows
-    must be in increasing, evenly spaced years.  Raises ValueError on a malformed file."""
+def _read_year_table(path, is_header, expected):
+    """The row parsing shared by the CSV readers with a year column: free-text lines, a row of column names (the last
+    non-numeric row before the data for which is_header(names) holds), then one numeric row per year.  Returns (column
+    names, table [n, len(names)] with missing cells as NaN); the years (column 0) increase in equal steps.  ValueError on a
+    malformed file (`expected` words the missing-header message)."""
     with open(path, newline="") as fh:
         rows = [[c.strip() for c in row] for row in csv.reader(fh)]
     header, data = None, []
@@ -40,10 +39,10 @@ def read_emissions_csv(path, gases=("CO2", "CH4", "N2O")):
             data.append(row)
         elif not data:
             names = [c.replace(" ", "") for c in row]
-            if any(n in names for n in _CO2_PARTS + _ALIASES["CO2"] + ("CH4", "N2O")):
+            if is_header(names):
                 header = names
     if header is None:
-        raise ValueError(f"{path}: no column-name row found (expected species names such as FossilCO2, CH4, N2O)")
+        raise ValueError(f"{path}: no column-name row found (expected {expected})")
     if not data:
         raise ValueError(f"{path}: no numeric data rows")
     width = len(header)
@@ -53,6 +52,19 @@ def read_emissions_csv(path, gases=("CO2", "CH4", "N2O")):
         step = np.diff(years)
         if np.any(step <= 0) or not np.allclose(step, step[0]):
             raise ValueError(f"{path}: years must increase in equal steps")
+    return header, table
+
+
+def read_emissions_csv(path, gases=("CO2", "CH4", "N2O")):
+    """Return (years [n] float64, emissions [n, len(gases)] float64) from an RCP-layout CSV.
+
+    The column-name row is the last non-numeric row before the data whose cells include every
+    requested species (CO2 may be given as FossilCO2 [+ OtherCO2] or as one CO2 column).  Rows
+    must be in increasing, evenly spaced years.  Raises ValueError on a malformed file."""
+    header, table = _read_year_table(
+        path, lambda names: any(n in names for n in _CO2_PARTS + _ALIASES["CO2"] + ("CH4", "N2O")),
+        "species names such as FossilCO2, CH4, N2O")
+    years = table[:, 0]
 
     def col(name):
         return table[:, header.index(name)]

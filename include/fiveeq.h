@@ -288,6 +288,56 @@ int fiveeq_plan_create_scen_f32(const fiveeq_model *model, int64_t n_members, in
 /* new — the largest n_scen the scenario forms take (64) */
 int32_t fiveeq_max_scenarios(void);
 
+/* FORCING SCALES — per-member scale factors on the gas and external forcings (new; ADDITIVE: FIVEEQ_ABI_VERSION stays 13, no
+ * existing prototype or struct changes, sizeof(fiveeq_model) stays 448 — a caller built against the v13 header keeps working
+ * and finds the new symbols by name).  A member carries G + n_fext factors: sg_g per gas and sx_k per external forcing
+ * category, 0 <= n_fext <= fiveeq_max_fext() (4); the run carries a shared table of category forcings.  Layouts:
+ *   fscale dev [G + n_fext][ld]   kernel precision; gas rows first, then one row per category
+ *   fext   dev [n_steps][4]       kernel precision, shared: the forcing of category k during step t at [t][k]; columns
+ *                                 k >= n_fext are not read; may be NULL iff n_fext == 0
+ * The total forcing of step t becomes, every fma a single rounding,
+ *     F = drive[t][6];   F = fma(sx_k, fext[t][k], F), k = 0 .. n_fext-1;   F = fma(sg_g, F_g, F), g = 0 .. G-1
+ * with F_g the forcing of gas g exactly as the plain step computes it; nothing else of the step differs.  fma(1, F_g, F) is
+ * F + F_g with the same rounding, so unit scales with n_fext == 0, or with an all-zero table, give fiveeq_run_* bit for bit.
+ * obs / misfit: both NULL = no misfit; both set = the in-loop misfit of CONSTRAINED RUNS above, the same bits as there.
+ *   form FIVEEQ_FORM_PER_STEP: one launch per step; the lane loads its G + n_fext scale rows with its other rows (w (G + n_fext)
+ *       bytes more per member-step) and the step's table record is read with scalar loads;
+ *   form FIVEEQ_FORM_FUSED: the time-fused kernel over spans of k_steps (0 = one launch for the range): the scales stay on
+ *       chip for the span and the table chunk is staged through LDS beside the drive chunk.
+ * Every form gives the same bits, fp32 packed or not.  Pool layouts {4} and 4 + 1 + 1 (fiveeq_forcing_layout_supported); not
+ * in the scenario, small-ensemble, concentration-driven, compensated or histogram-ring forms.  FIVEEQ_E_INVALID for a NULL or
+ * misaligned fscale, n_fext outside 0..4, a NULL fext with n_fext > 0, exactly one of obs / misfit set, a layout without the
+ * form, an unknown form, k_steps < 0 or a step range outside [0, n_steps) — before anything is launched. */
+int fiveeq_run_forc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                        const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                        const double *r, const double *q, double *R, double *S,
+                        double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                        const double *fscale, const double *fext, int32_t n_fext,
+                        const double *obs, double *misfit, int32_t form, int32_t k_steps, void *stream);
+int fiveeq_run_forc_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                        const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                        const float *r, const float *q, float *R, float *S,
+                        float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                        const float *fscale, const float *fext, int32_t n_fext,
+                        const double *obs, double *misfit, int32_t form, int32_t k_steps, void *stream);
+/* fiveeq_plan_create_* of the per-step form above; the plan bakes in fscale, fext, obs and misfit too */
+int fiveeq_plan_create_forc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                const double *r, const double *q, double *R, double *S,
+                                double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                                const double *fscale, const double *fext, int32_t n_fext,
+                                const double *obs, double *misfit, void **plan_out);
+int fiveeq_plan_create_forc_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                const float *r, const float *q, float *R, float *S,
+                                float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                                const float *fscale, const float *fext, int32_t n_fext,
+                                const double *obs, double *misfit, void **plan_out);
+/* 1 if the pool layout has the forcing forms above, else 0 */
+int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t *n_pools);
+/* the largest n_fext the forcing forms take (4) */
+int32_t fiveeq_max_fext(void);
+
 /* SMALL ENSEMBLES (BASELINE configs[1], 10k CO2-only members): the time-fused step with ONE MEMBER
  * SPREAD OVER SEVERAL LANES.  An ensemble of fewer waves than the chip has SIMDs (1024) is bound by the number of
  * instructions one wave issues per step; with lanes_per_member = 4 (pool layouts {4}: a lone 4-pool gas) lane 4m + i carries

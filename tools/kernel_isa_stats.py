@@ -4,6 +4,12 @@ instruction mix (VALU by type, SALU, LDS, global).  Runs in the CPU container (c
 
     python tools/kernel_isa_stats.py [substring ...]      # default: the 4+1+1 instantiations
     python tools/kernel_isa_stats.py --digest [FILE.s]    # every kernel: mangled name and sha256 of its assembly
+    python tools/kernel_isa_stats.py --compare-forc PARENT.s [NEW.s]   # profiles/r08/forcing_isa.txt
+
+--compare-forc: PARENT.s is the assembly of the commit before the FORC template parameter (step_kernel / fused_kernel gained
+it as their last one, default false), NEW.s the tree's (compiled when not given).  Every kernel of PARENT.s is looked up in
+NEW.s by its demangled name — with ", false" appended for the two templates — and compared on VGPR, SGPR, LDS, scratch,
+occupancy and instruction count; then every FORC = true instantiation is listed beside its FORC = false counterpart.
 
 --digest hashes each kernel from its `<name>:` label through `.end_amdhsa_kernel` (code and kernel descriptor), with
 comments and blank lines dropped and the function-numbered labels (.LBB<n>_, .Lfunc_end<n>) made position-independent:
@@ -41,9 +47,47 @@ def digest(asm):
         print(m.group(1), hashlib.sha256(text.encode()).hexdigest())
 
 
+def facts(asm):
+    """{demangled kernel name without its parameter list: (vgpr, sgpr, lds, scratch, occupancy, instructions)}"""
+    found = [(m.group(1), m.group(2), asm[m.end():m.end() + 4000]) for m in KERNEL.finditer(asm)]
+    names = subprocess.run(["c++filt"], input="\n".join(f[0] for f in found), capture_output=True, text=True).stdout.split("\n")
+    out = {}
+    for (_, body, tail), dem in zip(found, names):
+        get = lambda k: int(re.search(r"\.amdhsa_%s (\d+)" % k, body)[1])   # noqa: E731
+        after = lambda k: int(re.search(r"; %s: (\d+)" % k, tail)[1])   # noqa: E731
+        code = body.split(".section")[0]
+        key = dem.replace("float __vector(2)", "float2v").split("(")[0].replace("void fiveeq::", "")
+        out[key] = (get("next_free_vgpr"), get("next_free_sgpr"), after("LDSByteSize"), after("ScratchSize"), after("Occupancy"),
+                    len(re.findall(r"^\s+[a-z]\w+ ", code, re.M)))
+    return out
+
+
+def compare_forc(parent_asm, new_asm):
+    old, new = facts(parent_asm), facts(new_asm)
+    changed = missing = 0
+    for name, f in old.items():
+        key = name[:-1] + ", false>" if name.startswith(("step_kernel<", "fused_kernel<")) else name
+        if key not in new:
+            missing += 1
+            print("MISSING", key)
+        elif new[key] != f:
+            changed += 1
+            print("CHANGED", key, f, "->", new[key])
+    print(f"pre-existing instantiations compared: {len(old)}; missing: {missing}; changed: {changed}\n")
+    line = "   %-7s vgpr %3d sgpr %3d lds %5d scratch %d waves/SIMD %d instr %d"
+    for name in sorted(new):
+        if name.startswith(("step_kernel<", "fused_kernel<")) and name.endswith(", true>"):
+            print(name)
+            print(line % (("forc",) + new[name]))
+            print(line % (("without",) + new[name[:-len("true>")] + "false>"]))
+
+
 def main():
     if sys.argv[1:2] == ["--digest"]:
         digest(open(sys.argv[2]).read() if len(sys.argv) > 2 else compile_asm())
+        return
+    if sys.argv[1:2] == ["--compare-forc"]:
+        compare_forc(open(sys.argv[2]).read(), open(sys.argv[3]).read() if len(sys.argv) > 3 else compile_asm())
         return
     want = sys.argv[1:] or ["Li4ELi1ELi1E"]
     asm = compile_asm()
