@@ -12,7 +12,12 @@ scenarios at once, and write per-scenario 5/50/95 % of warming as CSV.
 The scenarios are synthetic: rcp_like_emissions with future CO2 scaled low / mid / high after the branch year.  Needs an
 MI355X.
 
-    python example/scenario_projections.py [--members N] [--out FILE]
+--forcing adds forcing uncertainty: every member scales the gas forcings and two external categories (an aerosol forcing
+proportional to the CO2 emissions, volcanic spikes) by its own factors.  The history runs with forcing= + observations=, so the
+misfit constrains the aerosol scale; the projection is a scenario engine with forcing=ScenarioForcings — one aerosol table per
+scenario, following that scenario's emissions — and the SAME scale rows.
+
+    python example/scenario_projections.py [--members N] [--out FILE] [--forcing]
 """
 import argparse
 import os
@@ -26,6 +31,7 @@ sys.path.insert(0, ROOT)
 
 from fiveeqscm_amd import constrain, emissions, params, scenario  # noqa: E402
 from fiveeqscm_amd.engine import EnsembleEngine  # noqa: E402
+from fiveeqscm_amd.forcing import ScenarioForcings  # noqa: E402
 
 SCENARIOS = {"low": 0.3, "mid": 1.0, "high": 1.6}          # future CO2 emissions as a multiple of the baseline path
 
@@ -34,6 +40,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--members", type=int, default=100_000)
     ap.add_argument("--out", default="scenario_projections.csv")
+    ap.add_argument("--forcing", action="store_true", help="per-member forcing scales, per-scenario aerosol tables")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -42,22 +49,34 @@ def main():
     p = params.sample_ensemble_shard(params.default_params("multigas"), N, 0, N, device="cuda:0")
     E = emissions.rcp_like_emissions(n_steps, 3)
     t_branch = int(obs.window[1])                             # the first step after the last observed year
-
-    hist = EnsembleEngine(p, N, E, observations=obs, store_trajectory=False, device="cuda:0")
-    hist.run(0, t_branch, mode="auto")
-    keep = constrain.accept_rejection(hist.chi2(), constrain.ACCEPT_SEED, 0, N)
-
     E_s = np.repeat(E[None], len(SCENARIOS), axis=0)
     for s, f in enumerate(SCENARIOS.values()):
         E_s[s, t_branch:, 0] *= f
+    sf = None
+    if a.forcing:                                             # the scenarios share the tables of the history, like its emissions
+        sc = params.sample_forcing_scales(3, N, 0, N, [(0.9, 1.1)] * 3 + [(0.3, 2.0), (0.5, 1.5)], device="cuda:0")
+        p["f_scale"], p["fx_scale"] = sc[:3], sc[3:]
+        volcanic = np.where(np.arange(n_steps) % 37 == 5, -2.5, 0.0) * (np.arange(n_steps) < t_branch)
+        sf = ScenarioForcings([np.stack([-0.9 * E_s[s, :, 0] / E[:, 0].max(), volcanic], 1) for s in range(len(SCENARIOS))],
+                              ("aerosol", "volcanic"))
+
+    hist = EnsembleEngine(p, N, E, observations=obs, forcing=sf.scenario(0) if sf else None, store_trajectory=False,
+                          device="cuda:0")
+    hist.run(0, t_branch, mode="auto")
+    keep = constrain.accept_rejection(hist.chi2(), constrain.ACCEPT_SEED, 0, N)
+
     out_steps = [t for t in range(t_branch, n_steps, 10)] + [n_steps - 1]
     torch.cuda.synchronize()
     proj = EnsembleEngine(p, N, E_s, R0=hist.R, S0=hist.S, output_steps=out_steps, store_concentrations=False,
-                          scenario_names=list(SCENARIOS), device="cuda:0")
+                          scenario_names=list(SCENARIOS), forcing=sf, device="cuda:0")
     proj.run(t_branch, n_steps, mode="auto")
     pct = (5.0, 50.0, 95.0)
     sums = [proj.gather_summary(out_steps, percentiles=pct, scenario=s, accepted=keep) for s in range(proj.n_scenarios)]
     scenario.write_scenario_summary_csv(a.out, proj.scenario_names, run_years[out_steps], sums, pct)
+    if sf is not None:
+        aer = p["fx_scale"][0][keep]
+        print(f"aerosol scale: prior 0.3 .. 2.0, accepted members {float(aer.min()):.2f} .. {float(aer.max()):.2f} "
+              f"(mean {float(aer.mean()):.2f})")
     print(f"{N} members, {int(keep.sum())} accepted on {obs.n_obs} observed years; branch at {int(run_years[t_branch])}; "
           f"projection mode {proj.last_mode}; summary -> {a.out}")
     for name, sm in zip(proj.scenario_names, sums):

@@ -114,6 +114,10 @@ SIGNATURES = {
     "fiveeq_run_forc_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, _i32, _i32, _p]),
     "fiveeq_plan_create_forc_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, ctypes.POINTER(_p)]),
     "fiveeq_plan_create_forc_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, ctypes.POINTER(_p)]),
+    "fiveeq_run_scen_forc_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, _i32, _i32, _p]),
+    "fiveeq_run_scen_forc_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, _i32, _i32, _p]),
+    "fiveeq_plan_create_scen_forc_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, ctypes.POINTER(_p)]),
+    "fiveeq_plan_create_scen_forc_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, ctypes.POINTER(_p)]),
     "fiveeq_forcing_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32)]),
     "fiveeq_max_fext": (_i32, []),
     "fiveeq_small_lanes": (_i32, [_i32, ctypes.POINTER(_i32)]),

@@ -160,8 +160,9 @@ struct MisfitRows {
     double* misfit = nullptr;
 };
 
-// the per-member forcing scales (step_kernel / fused_kernel <..., FORC = true>): fscale [G + n_fext][ld] in kernel precision, gas
-// rows first, and the shared table fext [n_steps][MAX_FEXT]
+// the per-member forcing scales (step_kernel / step_scen_kernel / fused_kernel <..., FORC = true>): fscale [G + n_fext][ld] in
+// kernel precision, gas rows first, and the shared table fext [n_steps][MAX_FEXT] (the scenario forms: one table per scenario,
+// [n_scen][n_steps][MAX_FEXT])
 template <typename T>
 struct ForcRows {
     const T* fscale = nullptr;
@@ -248,12 +249,13 @@ constexpr bool forcing_layout(int p0, int p1, int p2) { return misfit_layout(p0,
 // ---- the two launchers: one step of the per-step kernel, one span [t_begin, t_end) of the time-fused kernel ----------------
 // The compile-time flags pick the kernel family; packing, the row policy and the pool layout are decided here per launch.
 // SCEN: the scenario axis (step_scen_kernel; the fused kernel with the scenario as blockIdx.y).
-// FORC: the per-member forcing scales (with or without MISFIT).
+// FORC: the per-member forcing scales (with or without MISFIT, or with SCEN: the scale rows shared by the scenarios, a table
+// per scenario).
 template <typename T, bool BINS = false, bool MISFIT = false, bool SCEN = false, bool FORC = false>
 int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
     static_assert(BINS + MISFIT + SCEN <= 1, "the histogram ring, the misfit and the scenario axis are separate forms");
-    static_assert(!FORC || (!BINS && !SCEN), "the forcing scales combine with the misfit only");
+    static_assert(!FORC || !BINS, "the forcing scales combine with the misfit or the scenario axis only");
     const bool packed = LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0) &&
                         (!FORC || (((uintptr_t)a.fc.fscale) & 7) == 0);
     unsigned blocks;
@@ -263,8 +265,9 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
 #define FIVEEQ_STEP_LAUNCH(V, p0, p1, p2, NT)                                                                                     \
     do {                                                                                                                          \
         if constexpr (SCEN)                                                                                                       \
-            hipLaunchKernelGGL((step_scen_kernel<V, p0, p1, p2, NT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld, \
-                               a.n_scen, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats);                              \
+            hipLaunchKernelGGL((step_scen_kernel<V, p0, p1, p2, NT, FORC>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, \
+                               a.ld, a.n_scen, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.fc.fscale, a.fc.fext, \
+                               a.fc.n_fext);                                                                                      \
         else                                                                                                                      \
             hipLaunchKernelGGL((step_kernel<V, p0, p1, p2, BINS, NT, MISFIT, FORC>), grid, block, 0, st, a.km, a.drive,           \
                                a.n_steps, t, a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.br.ring,     \
@@ -304,7 +307,7 @@ template <typename T, bool INV = false, bool BINS = false, bool COMP = false, bo
           bool FORC = false>
 int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
-    static_assert(!FORC || (!INV && !BINS && !COMP && !SCEN), "the forcing scales are carried by the plain forward form only");
+    static_assert(!FORC || (!INV && !BINS && !COMP), "the forcing scales are carried by the plain forward form only");
     static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
     static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
     constexpr bool HAS_PACKED = !INV && !std::is_same<P, T>::value;     // the inverse form has no packed instantiation
@@ -495,6 +498,21 @@ int run_forc(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32
     return run_form_forc(a, form, k_steps, (hipStream_t)stream);
 }
 
+// fiveeq_run_scen_forc: the scenario axis with per-member forcing scales — the scale rows shared by the scenarios, one category
+// table per scenario
+template <typename T>
+int run_scen_forc(const fiveeq_model* m, int64_t n, int64_t ld, int32_t n_scen, const T* drive, int32_t n_steps, int32_t t_begin,
+                  int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
+                  const T* fscale, const T* fext, int32_t n_fext, int32_t form, int32_t k_steps, void* stream) {
+    if (int rc = check_scen(n_scen)) return rc;
+    RunArgs<T> a;
+    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats, n_scen))
+        return rc;
+    if (int rc = check_forcing(a, fscale, fext, n_fext)) return rc;
+    if (int rc = check_form(form, k_steps, 0)) return rc;
+    return run_form<T, false, true, true>(a, form, k_steps, (hipStream_t)stream);
+}
+
 // fiveeq_step/run/run_fused/run_ksteps (k_min 1), fiveeq_run_obs (MISFIT: obs, misfit) and fiveeq_run_scen (SCEN: n_scen,
 // checked first)
 template <typename T, bool MISFIT = false, bool SCEN = false>
@@ -631,7 +649,7 @@ struct Plan {
 constexpr uint32_t PLAN_MAGIC = 0x35455146u;  // "FQE5"
 
 // the plan of run_form<T, MISFIT, SCEN>(FIVEEQ_FORM_PER_STEP): that very run, enqueued on a capture stream (FORC: of
-// run_form_forc, the misfit carried when obs and misfit are set)
+// run_form_forc, the misfit carried when obs and misfit are set; SCEN and FORC: of run_form<T, false, true, true>)
 template <typename T, bool MISFIT = false, bool SCEN = false, bool FORC = false>
 int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
                 int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void** plan_out,
@@ -658,7 +676,8 @@ int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
         return fail(FIVEEQ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(e));
     }
     int rc;
-    if constexpr (FORC) rc = run_form_forc(a, FIVEEQ_FORM_PER_STEP, 0, cap);
+    if constexpr (FORC && SCEN) rc = run_form<T, false, true, true>(a, FIVEEQ_FORM_PER_STEP, 0, cap);
+    else if constexpr (FORC) rc = run_form_forc(a, FIVEEQ_FORM_PER_STEP, 0, cap);
     else rc = run_form<T, MISFIT, SCEN>(a, FIVEEQ_FORM_PER_STEP, 0, cap);
     e = hipStreamEndCapture(cap, &graph);
     (void)hipStreamDestroy(cap);
@@ -928,6 +947,34 @@ int fiveeq_plan_create_scen_f32(const fiveeq_model* model, int64_t n_members, in
                                            n_rows, T_stats, plan_out, nullptr, nullptr, n_scen);
 }
 int32_t fiveeq_max_scenarios(void) { return MAX_SCENARIOS; }
+int fiveeq_run_scen_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
+                             int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
+                             double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, const double* fscale,
+                             const double* fext, int32_t n_fext, int32_t form, int32_t k_steps, void* stream) {
+    return run_scen_forc<double>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                                 T_stats, fscale, fext, n_fext, form, k_steps, stream);
+}
+int fiveeq_run_scen_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
+                             int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
+                             float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext,
+                             int32_t n_fext, int32_t form, int32_t k_steps, void* stream) {
+    return run_scen_forc<float>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
+                                T_stats, fscale, fext, n_fext, form, k_steps, stream);
+}
+int fiveeq_plan_create_scen_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
+                                     int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
+                                     double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats,
+                                     const double* fscale, const double* fext, int32_t n_fext, void** plan_out) {
+    return plan_create<double, false, true, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                                  n_rows, T_stats, plan_out, nullptr, nullptr, n_scen, fscale, fext, n_fext);
+}
+int fiveeq_plan_create_scen_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
+                                     int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
+                                     float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, const float* fscale,
+                                     const float* fext, int32_t n_fext, void** plan_out) {
+    return plan_create<float, false, true, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
+                                                 n_rows, T_stats, plan_out, nullptr, nullptr, n_scen, fscale, fext, n_fext);
+}
 
 int fiveeq_run_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                         int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,

@@ -1034,19 +1034,44 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
 //   R [n_scen][SP][ld], S [n_scen][2][ld], C_traj [n_scen][n_rows][G][ld], T_traj [n_scen][n_rows][ld],
 //   stats [n_scen][ceil(ld/64)][n_steps][4]
 // so a member sub-range [m0, m0 + n) is a plain pointer offset, as for step_kernel.
+//
+// FORC = true (round 9): the scenarios with per-member forcing scales (member_step<.., FORC>).  The lane loads its G + n_fext
+// scale rows fscale [G + n_fext][ld] ONCE, beside the parameter rows, for all scenarios — w (G + K) / S bytes per
+// member-scenario-step — and scenario sc's table record fext [sc][t][0 .. MAX_FEXT) is wave-uniform and read with scalar
+// loads, like its drive record (n_fext == 0: no record is read).  Member-scenario (m, s) is bit for bit member m of
+// step_kernel<.., FORC> on scenario s's drive table and category table.  Default row policy; the {4} and 4 + 1 + 1 layouts.
+// Where the scales live across the scenario loop is ScenForc::FS_LDS.
 // ---------------------------------------------------------------------------------
-template <typename V, int P0, int P1, int P2, bool NT = false>
+// The plain fp64 4 + 1 + 1 scenario kernel sits at 120 VGPRs, 4 waves per SIMD: seven fp64 scales live across the scenario
+// loop would take it past 128 and cost a wave.  Such an instantiation parks the scales in a lane-private LDS slot
+// fs_s[G + MAX_FEXT][FIVEEQ_STEP_BLOCK] like fused_kernel's FS_LDS form (consecutive lanes, consecutive words: no bank
+// conflicts; a lane reads only what it wrote, and a wave's LDS operations complete in program order: no barrier beyond the
+// model's staging barrier), read back with one ds_read per fma.  Everything else keeps them in registers.
+// profiles/r09/scenario_forcing_isa.txt has the counts both ways.
+template <typename V, typename L>
+struct ScenForc {
+    static constexpr bool FS_LDS = false;
+};
+template <>
+struct ScenForc<double, Layout<4, 1, 1>> {
+    static constexpr bool FS_LDS = true;
+};
+template <typename V, int P0, int P1, int P2, bool NT = false, bool FORC = false>
 __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_scen_kernel(
     const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
     const int64_t n, const int64_t ld, const int n_scen,
     const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
     typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
     typename Lane<V>::S* __restrict__ C_traj, typename Lane<V>::S* __restrict__ T_traj,
-    const int n_rows, double* __restrict__ stats) {
+    const int n_rows, double* __restrict__ stats,
+    const typename Lane<V>::S* __restrict__ fscale /* FORC: [G + n_fext][ld] */,
+    const typename Lane<V>::S* __restrict__ fext /* FORC: [n_scen][n_steps][MAX_FEXT] */, const int n_fext) {
     using L = Layout<P0, P1, P2>;
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     constexpr bool NTT = true;                    // the stored C / T rows: written once, never read by a stepping kernel
+    static_assert(!FORC || !NT, "the forcing scales: default row policy");
+    constexpr bool FS_LDS = FORC && ScenForc<V, L>::FS_LDS;           // FORC: the scales in a lane-private LDS slot
     const int64_t m = ((int64_t)blockIdx.x * FIVEEQ_STEP_BLOCK + threadIdx.x) * W;
     const bool active = m < n;
     const bool full = m + (W - 1) < n;
@@ -1064,6 +1089,16 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_scen_
     for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_row<V, NT>(r + k * ld + mm);
 #pragma unroll
     for (int k = 0; k < 2; ++k) qq[k] = load_row<V, NT>(q + k * ld + mm);
+    // FORC: the lane's scales, gas rows first (rows past n_fext are never read): scale j at fs[j * FS_STRIDE]
+    __shared__ V fs_s[FS_LDS ? (L::G + MAX_FEXT) * FIVEEQ_STEP_BLOCK : 1];
+    V fs_r[FORC && !FS_LDS ? L::G + MAX_FEXT : 1];
+    V* const fs = FS_LDS ? &fs_s[threadIdx.x] : fs_r;
+    constexpr int FS_STRIDE = FS_LDS ? FIVEEQ_STEP_BLOCK : 1;
+    if constexpr (FORC) {
+#pragma unroll
+        for (int k = 0; k < L::G + MAX_FEXT; ++k)
+            fs[k * FS_STRIDE] = k < L::G + n_fext ? load_row<V, NT>(fscale + k * ld + mm) : (V)T(0);
+    }
     if (threadIdx.x < NW) reinterpret_cast<T*>(&km_s)[threadIdx.x] = stage_v;
     __syncthreads();
 
@@ -1082,7 +1117,13 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_scen_
         for (int k = 0; k < 2; ++k) Sv[k] = load_row<V, NT>(Sl + k * ld);
         const T* d = drive + ((int64_t)sc * n_steps + t) * DRIVE_STRIDE;    // wave-uniform: scalar loads
         V Tn = (V)T(0);
-        member_step<V, L>(kmr, d, rr, qq, Rv, Sv, Cv, Tn);
+        if constexpr (FORC) {
+            V no_cum[L::G], no_Rlo[L::SP];        // never touched: INV = COMP = false
+            member_step<V, L, false, false, true>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, FS_STRIDE,
+                                                  fext + ((int64_t)sc * n_steps + t) * MAX_FEXT, n_fext);
+        } else {
+            member_step<V, L>(kmr, d, rr, qq, Rv, Sv, Cv, Tn);
+        }
         if (active) {
 #pragma unroll
             for (int k = 0; k < L::SP; ++k) store_row<NT>(Rl + k * ld, Rv[k], full);
@@ -1119,15 +1160,28 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_scen_
 // misfit slot (14 + 6 KB of slots on 17 KB of statistics tile and model), it stages 25 steps per refill instead of 125
 // (2.4 KB of drive and table records instead of 12): 39984 B per workgroup with the misfit, under the 40960 a static_assert in
 // the kernel holds it to.  profiles/r08/forcing_isa.txt has the counts.
-template <typename V, typename L, bool MISFIT, bool FORC>
+// With SCEN (round 9) the fp32 {4} form takes the slot too: its plain scenario kernel sits at 65 VGPRs, 7 waves per SIMD, and five
+// fp32 scales in registers took it to 74: 6 waves; with the slot it is at 66 and keeps 7 (seven workgroups of 14.5 KB fit a CU).
+// The fp64 {4} and the packed fp32 {4} scenario forms lose a wave either way (slot: 103 and 85 VGPRs where 96 and 80 would be
+// needed, and six packed workgroups of 27.6 KB would not fit a CU), exactly as their single-scenario forms do: they keep
+// the registers.  profiles/r09/scenario_forcing_isa.txt.  WGS: the workgroups per CU the slot has to leave room for.
+template <typename V, typename L, bool MISFIT, bool FORC, bool SCEN = false>
 struct FusedForc {
     static constexpr bool FS_LDS = false;
     static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK;
+    static constexpr int WGS = 4;
 };
-template <bool MISFIT>
-struct FusedForc<double, Layout<4, 1, 1>, MISFIT, true> {
+template <bool MISFIT, bool SCEN>
+struct FusedForc<double, Layout<4, 1, 1>, MISFIT, true, SCEN> {
     static constexpr bool FS_LDS = true;
     static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK < 25 ? FIVEEQ_FUSED_CHUNK : 25;
+    static constexpr int WGS = 4;
+};
+template <>
+struct FusedForc<float, Layout<4, 0, 0>, false, true, true> {
+    static constexpr bool FS_LDS = true;
+    static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK < 25 ? FIVEEQ_FUSED_CHUNK : 25;
+    static constexpr int WGS = 7;
 };
 constexpr int LDS_PER_CU = 160 * 1024;            // MI355X
 
@@ -1160,9 +1214,11 @@ constexpr int LDS_PER_CU = 160 * 1024;            // MI355X
 // scenario strides of kernel 1s (all derived from ld, n_steps and n_rows, so no argument is added).  With SCEN false not
 // one instruction of the kernel changes.
 //
-// FORC = true (round 8; INV, BINS, COMP and SCEN false, with or without MISFIT): per-member forcing scales
+// FORC = true (round 8; INV, BINS and COMP false, with or without MISFIT): per-member forcing scales
 // (member_step<.., FORC>).  The G + n_fext scales are loaded once at launch start and stay on chip for the span; the table chunk
 // fext [tc .. tc + nt)[MAX_FEXT] is staged into LDS beside the drive chunk.  Where the scales live is FS_LDS, below.
+// With SCEN (round 9; MISFIT false) the table is fext [n_scen][n_steps][MAX_FEXT], one per scenario: the workgroup offsets it
+// by its scenario like the drive table; the scale rows are shared by the scenarios.
 template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false,
           bool SCEN = false, bool FORC = false>
 __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
@@ -1183,9 +1239,9 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     static_assert(!(INV && BINS), "no streamed histograms in the concentration-driven form");
-    static_assert(!FORC || (!INV && !BINS && !COMP && !SCEN), "the forcing scales are carried by the plain forward form only");
-    constexpr int CHUNK = FusedForc<V, L, MISFIT, FORC>::CHUNK;       // steps staged per refill
-    constexpr bool FS_LDS = FusedForc<V, L, MISFIT, FORC>::FS_LDS;    // FORC: the scales in a lane-private LDS slot
+    static_assert(!FORC || (!INV && !BINS && !COMP), "the forcing scales are carried by the plain forward form only");
+    constexpr int CHUNK = FusedForc<V, L, MISFIT, FORC, SCEN>::CHUNK;       // steps staged per refill
+    constexpr bool FS_LDS = FusedForc<V, L, MISFIT, FORC, SCEN>::FS_LDS;    // FORC: the scales in a lane-private LDS slot
     static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
     static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
     if constexpr (SCEN) {
@@ -1196,6 +1252,7 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
         if (C_traj != nullptr) C_traj += sc * n_rows * L::G * ld;
         if (T_traj != nullptr) T_traj += sc * n_rows * ld;
         if (stats != nullptr) stats += sc * ((ld + 63) >> 6) * n_steps * 4;
+        if constexpr (FORC) fext += sc * n_steps * MAX_FEXT;         // a table per scenario; fscale is shared: not offset
     }
     __shared__ T drv[CHUNK * DRIVE_STRIDE];
     __shared__ T xs[FORC ? CHUNK * MAX_FEXT : 1];                     // FORC: the table chunk
@@ -1203,9 +1260,10 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     __shared__ double acc_s[MISFIT ? 3 * W * FIVEEQ_BLOCK : 1];       // MISFIT: [3 W][FIVEEQ_BLOCK], lane-private
     __shared__ V stat_tile[FIVEEQ_BLOCK / 64][STAT_STEPS * STAT_ROW];
     __shared__ KModel<T> km_s;
-    // the LDS slot exists to keep four workgroups (4 waves per SIMD) on a CU: a change that outgrows the budget must not pass
+    // the LDS slot exists to keep WGS workgroups (four: 4 waves per SIMD) on a CU: a change that outgrows the budget must not pass
     static_assert(!FS_LDS || sizeof(drv) + sizeof(xs) + sizeof(fs_s) + sizeof(acc_s) + sizeof(stat_tile) + sizeof(km_s) <=
-                                 LDS_PER_CU / 4, "FS_LDS form: four workgroups no longer fit a CU's LDS");
+                                 LDS_PER_CU / FusedForc<V, L, MISFIT, FORC, SCEN>::WGS,
+                  "FS_LDS form: the workgroups it is there to keep no longer fit a CU's LDS");
     stage_model(&km_s);
     const KModel<T>& kmr = km_s;
 

@@ -27,6 +27,7 @@ import torch
 from . import _capi
 from .checkpoint import CheckpointMixin
 from .emissions import emissions_sha256, make_drive, make_scenario_drive
+from .forcing import ScenarioForcings
 from .params import make_model, n_gas_of, pools_of
 from .tuning import (_env_choice, _env_positive, calibrate, concurrent_side_streams,  # noqa: F401  (calibrate: part of this
                      side_stream_report)                                               # module's interface)
@@ -154,14 +155,19 @@ class EnsembleEngine(CheckpointMixin):
         gather_summary() and T_histogram() then take scenario=).  F_ext: [n_steps] (shared) or [S, n_steps]; R0 / S0: one
         [SP, N] / [2, N] state for every scenario, or [S, ...].  scenario_names: S labels (default "0", "1", ...).  Modes
         'per_step', 'graph', 'fused', 'ksteps' and 'auto' (never 'small'); not with concentration_driven=True, hist=,
-        observations= or compensated=True.  `n_scenarios` is S (1 for an engine without the scenario axis).
+        observations= or compensated=True.  `n_scenarios` is S (1 for an engine without the scenario axis).  With
+        forcing=ScenarioForcings (below) every member-scenario also carries its member's forcing scales.
         forcing: a forcing.ExternalForcings table [n_steps, K] (K <= 4 categories, K = 0 allowed).  Every member then scales
         the forcing of gas g by params["f_scale"][g] and category k by params["fx_scale"][k] ([G] / [K] shared or [G, N] /
         [K, N] per member, default 1; include/fiveeq.h "FORCING SCALES"): F = F_ext + sum_k sx_k X[t, k] + sum_g sg_g F_g, every
         term one fma.  `fscale` [G + K, N] holds the rows, gas rows first.  Modes 'per_step', 'graph', 'fused', 'ksteps' and
         'auto' (never 'small'), the same bits in each; works with observations=, chunk-major schedules, the two-stream
         halves, step sub-ranges and R0 / S0; unit scales with K = 0 or a zero table are the plain run bit for bit.  Pool
-        layouts {4} and 4 + 1 + 1; not with hist=, concentration_driven=True, compensated=True or the scenario axis."""
+        layouts {4} and 4 + 1 + 1; not with hist=, concentration_driven=True or compensated=True.
+        WITH THE SCENARIO AXIS forcing= is a forcing.ScenarioForcings — one table per scenario, [S, n_steps, K], its
+        n_scenarios the emissions' S — and the f_scale / fx_scale rows are shared by the scenarios: member-scenario (m, s) is bit
+        for bit member m of a single-scenario forcing= engine on scenario s's emissions, F_ext and table, in every mode.  (One
+        ExternalForcings table with several scenarios is refused: say ScenarioForcings.shared(fx, S) if that is what is meant.)"""
         if dtype not in _DTYPES:
             raise ValueError("dtype must be torch.float64 or torch.float32")
         self.lib = _capi.load(lib_path)    # raises if the HIP library is not built
@@ -289,11 +295,20 @@ class EnsembleEngine(CheckpointMixin):
             self.forcing, self.fscale, self.fext = None, None, None
             if forcing is not None:
                 for flag, why in ((hist is not None, "hist="), (self.concentration_driven, "concentration_driven=True"),
-                                  (self.compensated, "compensated=True"),
-                                  (self.scenario_axis, "emissions of several scenarios (the scenario axis)")):
+                                  (self.compensated, "compensated=True")):
                     if flag:
                         raise ValueError(f"forcing= cannot be combined with {why}: the forcing scales are carried by the plain "
-                                         "forward forms (with or without observations=) only")
+                                         "forward forms (with or without observations=, or with the scenario axis) only")
+                per_scenario = isinstance(forcing, ScenarioForcings)
+                if self.scenario_axis and not per_scenario:
+                    raise ValueError("forcing= with emissions of several scenarios (the scenario axis) takes one table per "
+                                     "scenario: pass a forcing.ScenarioForcings (ScenarioForcings.shared(fx, S) for one table "
+                                     "under every scenario), not an ExternalForcings")
+                if per_scenario and not self.scenario_axis:
+                    raise ValueError("forcing=ScenarioForcings needs emissions of several scenarios ([S, n_steps, G]); a run of "
+                                     "one scenario takes an ExternalForcings (ScenarioForcings.scenario(s))")
+                if per_scenario and forcing.n_scenarios != Sc:
+                    raise ValueError(f"forcing: tables of {forcing.n_scenarios} scenarios for emissions of {Sc}")
                 if not self.lib.fiveeq_forcing_layout_supported(G, n_pools):
                     raise ValueError(f"forcing=: pool layout {self.pools} has no forcing form (pools [4] and [4, 1, 1] have)")
                 if forcing.n_steps != self.n_steps:
@@ -504,21 +519,25 @@ class EnsembleEngine(CheckpointMixin):
 
     def _forward_calls(self):
         """The C calls of this engine's forward run, with the arguments of its feature bound: n_scen (the scenario axis, whose
-        strides derive from ld = N), (obs, misfit) (observations=) or none.  Returns
+        strides derive from ld = N), (obs, misfit) (observations=), (fscale, fext, n_fext) (forcing=, after n_scen's or before
+        the misfit's) or none.  Returns
           per_step(t_begin, t_end, m0, n, stream)  one launch per step for members [m0, m0 + n);
           fused(t_begin, t_end, k, stream)         the fused kernel over spans of k steps, all members;
           plan(t_begin, t_end, m0, n, plan_out)    the per-step launches of members [m0, m0 + n) captured into a plan."""
         def args(t_begin, t_end, m0=0, n=None):
             a = self._run_args(t_begin, t_end, m0, n)
-            if self.scenario_axis:
-                return (*a[:3], self.n_scenarios, *a[3:])
+            if self.scenario_axis:                              # the scale rows are shared, the tables [S, n_steps, 4]
+                fc = (() if self.forcing is None else
+                      (self._ptr(self.fscale, m0 * self._w), self._ptr(self.fext), self.forcing.n_categories))
+                return (*a[:3], self.n_scenarios, *a[3:], *fc)
             if self.forcing is not None:                        # (obs, misfit): both NULL without observations=
                 mis = self._obs_args(m0) if self.observations is not None else (None, None)
                 return (*a, self._ptr(self.fscale, m0 * self._w), self._ptr(self.fext), self.forcing.n_categories, *mis)
             return a if self.observations is None else (*a, *self._obs_args(m0))
 
         if self.scenario_axis or self.observations is not None or self.forcing is not None:
-            sfx = "scen" if self.scenario_axis else ("forc" if self.forcing is not None else "obs")
+            sfx = (("scen_forc" if self.forcing is not None else "scen") if self.scenario_axis
+                   else ("forc" if self.forcing is not None else "obs"))
             run, plan = self._fn("run_" + sfx), self._fn("plan_create_" + sfx)
 
             def per_step(t, t1, m0, n, s):
@@ -970,7 +989,8 @@ class EnsembleEngine(CheckpointMixin):
         read per member-step.  With `observations=` the misfit accumulators add, per_step: 48 B (3 fp64 read + written) per
         member and step of the observation window, averaged over the run's steps; the fused forms: 48 B per member and launch.
         With the scenario axis the count is per MEMBER-SCENARIO-step: per_step reads the parameter rows once for all S
-        scenarios, w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / S.
+        scenarios, w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / S (with `forcing=`: w (3G + 2 + G + K) / S, the scale rows
+        too are read once per member).
         With `forcing=` the G + K scale rows are parameter rows like r and q: per_step w (G + K) more per member-step, the
         fused forms w (G + K) more per member and launch."""
         w, G, SP = self._w, self.n_gas, self.sum_pools
@@ -983,7 +1003,7 @@ class EnsembleEngine(CheckpointMixin):
             if mode == "per_step":
                 extra += 48.0 * np.count_nonzero((tab[:, 1] != 0) | (tab[:, 2] != 0)) / self.n_steps
         if mode == "per_step" and self.scenario_axis:
-            return w * (2 * SP + 4 + out) + w * (3 * G + 2) / self.n_scenarios + extra
+            return w * (2 * SP + 4 + out) + w * (3 * G + 2 + fr) / self.n_scenarios + extra
         if mode == "per_step":
             return w * (2 * SP + 3 * G + 6 + fr + out) + extra + ring
         if mode == "fused":

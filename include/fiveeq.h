@@ -265,7 +265,9 @@ int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t *n_pools);
  *   form FIVEEQ_FORM_FUSED: the time-fused kernel over spans of k_steps (0 = one launch for the range), one grid row of
  *       workgroups per scenario (each stages its own scenario's drive chunk).
  * Every pool layout.  FIVEEQ_E_INVALID for n_scen outside [1, fiveeq_max_scenarios()], a NULL drive or state pointer, an
- * unknown form, k_steps < 0 or a step range outside [0, n_steps) — before anything is launched. */
+ * unknown form, k_steps < 0 or a step range outside [0, n_steps) — before anything is launched.
+ * The scenario axis combines with the per-member forcing scales (fiveeq_run_scen_forc_*, under FORCING SCALES below); not
+ * with the misfit, the histogram ring, the concentration-driven, the compensated or the small-ensemble forms. */
 int fiveeq_run_scen_f64(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
                         const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
                         const double *r, const double *q, double *R, double *S,
@@ -305,7 +307,8 @@ int32_t fiveeq_max_scenarios(void);
  *   form FIVEEQ_FORM_FUSED: the time-fused kernel over spans of k_steps (0 = one launch for the range): the scales stay on
  *       chip for the span and the table chunk is staged through LDS beside the drive chunk.
  * Every form gives the same bits, fp32 packed or not.  Pool layouts {4} and 4 + 1 + 1 (fiveeq_forcing_layout_supported); not
- * in the scenario, small-ensemble, concentration-driven, compensated or histogram-ring forms.  FIVEEQ_E_INVALID for a NULL or
+ * in the small-ensemble, concentration-driven, compensated or histogram-ring forms; under the scenario axis through
+ * fiveeq_run_scen_forc_* below (without the misfit).  FIVEEQ_E_INVALID for a NULL or
  * misaligned fscale, n_fext outside 0..4, a NULL fext with n_fext > 0, exactly one of obs / misfit set, a layout without the
  * form, an unknown form, k_steps < 0 or a step range outside [0, n_steps) — before anything is launched. */
 int fiveeq_run_forc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
@@ -333,6 +336,42 @@ int fiveeq_plan_create_forc_f32(const fiveeq_model *model, int64_t n_members, in
                                 float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
                                 const float *fscale, const float *fext, int32_t n_fext,
                                 const double *obs, double *misfit, void **plan_out);
+/* FORCING SCALES UNDER THE SCENARIO AXIS (new; additive, FIVEEQ_ABI_VERSION stays 13): fiveeq_run_scen_* / fiveeq_plan_create_scen_*
+ * with the forcing scales of fiveeq_run_forc_*.  The arguments of the scenario calls, then
+ *   fscale dev [G + n_fext][ld]          SHARED by the scenarios, like r and q
+ *   fext   dev [n_scen][n_steps][4]      one category table per scenario (aerosol and other external forcings differ from one
+ *                                        scenario to the next); may be NULL iff n_fext == 0
+ * then form, k_steps, stream (or plan_out).  Member-scenario (m, s) is bit for bit member m of fiveeq_run_forc_* (obs = misfit =
+ * NULL) run with scenario s's drive table and category table, in both forms, fp32 packed or not.
+ *   form FIVEEQ_FORM_PER_STEP: the lane loads its G + n_fext scale rows ONCE beside its parameter rows for all scenarios —
+ *       w (G + n_fext) / n_scen bytes more per member-scenario-step — and reads scenario s's table record with scalar loads;
+ *   form FIVEEQ_FORM_FUSED: a grid row of workgroups per scenario, each staging its own scenario's table chunk.
+ * Pool layouts {4} and 4 + 1 + 1; no misfit.  FIVEEQ_E_INVALID for a NULL or misaligned fscale, n_fext outside
+ * 0..fiveeq_max_fext(), a NULL fext with n_fext > 0, n_scen outside 1..fiveeq_max_scenarios(), a layout without the forcing
+ * form, an unknown form, k_steps < 0 or a step range outside [0, n_steps) — before anything is launched. */
+int fiveeq_run_scen_forc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                             const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                             const double *r, const double *q, double *R, double *S,
+                             double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                             const double *fscale, const double *fext, int32_t n_fext,
+                             int32_t form, int32_t k_steps, void *stream);
+int fiveeq_run_scen_forc_f32(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                             const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                             const float *r, const float *q, float *R, float *S,
+                             float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                             const float *fscale, const float *fext, int32_t n_fext,
+                             int32_t form, int32_t k_steps, void *stream);
+/* fiveeq_plan_create_* of the per-step form above; the plan bakes in fscale and fext too */
+int fiveeq_plan_create_scen_forc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                                     const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                     const double *r, const double *q, double *R, double *S,
+                                     double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                                     const double *fscale, const double *fext, int32_t n_fext, void **plan_out);
+int fiveeq_plan_create_scen_forc_f32(const fiveeq_model *model, int64_t n_members, int64_t ld, int32_t n_scen,
+                                     const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                     const float *r, const float *q, float *R, float *S,
+                                     float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                                     const float *fscale, const float *fext, int32_t n_fext, void **plan_out);
 /* 1 if the pool layout has the forcing forms above, else 0 */
 int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t *n_pools);
 /* the largest n_fext the forcing forms take (4) */

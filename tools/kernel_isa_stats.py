@@ -5,11 +5,16 @@ instruction mix (VALU by type, SALU, LDS, global).  Runs in the CPU container (c
     python tools/kernel_isa_stats.py [substring ...]      # default: the 4+1+1 instantiations
     python tools/kernel_isa_stats.py --digest [FILE.s]    # every kernel: mangled name and sha256 of its assembly
     python tools/kernel_isa_stats.py --compare-forc PARENT.s [NEW.s]   # profiles/r08/forcing_isa.txt
+    python tools/kernel_isa_stats.py --compare-scen-forc PARENT.s [NEW.s]   # profiles/r09/scenario_forcing_isa.txt
 
 --compare-forc: PARENT.s is the assembly of the commit before the FORC template parameter (step_kernel / fused_kernel gained
 it as their last one, default false), NEW.s the tree's (compiled when not given).  Every kernel of PARENT.s is looked up in
 NEW.s by its demangled name — with ", false" appended for the two templates — and compared on VGPR, SGPR, LDS, scratch,
 occupancy and instruction count; then every FORC = true instantiation is listed beside its FORC = false counterpart.
+
+--compare-scen-forc: the same for the commit before step_scen_kernel gained FORC as its last template parameter (default
+false; fused_kernel's parameter list did not change, it gained the SCEN + FORC instantiations): every kernel of PARENT.s
+against NEW.s, then every new instantiation beside its SCEN, FORC = false counterpart.
 
 --digest hashes each kernel from its `<name>:` label through `.end_amdhsa_kernel` (code and kernel descriptor), with
 comments and blank lines dropped and the function-numbered labels (.LBB<n>_, .Lfunc_end<n>) made position-independent:
@@ -82,7 +87,38 @@ def compare_forc(parent_asm, new_asm):
             print(line % (("without",) + new[name[:-len("true>")] + "false>"]))
 
 
+def compare_scen_forc(parent_asm, new_asm):
+    old, new = facts(parent_asm), facts(new_asm)
+    changed = missing = 0
+    for name, f in old.items():
+        key = name[:-1] + ", false>" if name.startswith("step_scen_kernel<") else name
+        if key not in new:
+            missing += 1
+            print("MISSING", key)
+        elif new[key] != f:
+            changed += 1
+            print("CHANGED", key, f, "->", new[key])
+    renamed = {(n[:-1] + ", false>" if n.startswith("step_scen_kernel<") else n) for n in old}
+    added = sorted(n for n in new if n not in renamed)
+    print(f"pre-existing instantiations compared: {len(old)}; missing: {missing}; changed: {changed}; new: {len(added)}\n")
+    line = "   %-7s vgpr %3d sgpr %3d lds %5d scratch %d waves/SIMD %d instr %d"
+    worse = 0
+    for name in added:
+        assert name.endswith("true>"), name                    # step_scen_kernel<.., FORC>, fused_kernel<.., SCEN, FORC>
+        plain = name[:-len("true>")] + "false>"
+        print(name)
+        print(line % (("forc",) + new[name]))
+        print(line % (("without",) + new[plain]))
+        if new[name][3] != 0 or new[name][4] < new[plain][4]:
+            worse += 1
+            print("   ^^^ scratch, or fewer waves per SIMD than the counterpart")
+    print(f"\nnew instantiations with scratch or fewer waves per SIMD than their counterpart: {worse}")
+
+
 def main():
+    if sys.argv[1:2] == ["--compare-scen-forc"]:
+        compare_scen_forc(open(sys.argv[2]).read(), open(sys.argv[3]).read() if len(sys.argv) > 3 else compile_asm())
+        return
     if sys.argv[1:2] == ["--digest"]:
         digest(open(sys.argv[2]).read() if len(sys.argv) > 2 else compile_asm())
         return
