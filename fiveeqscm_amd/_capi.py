@@ -149,12 +149,15 @@ SIGNATURES = {
 }
 
 _lib = None
-SOURCES = (os.path.join(_HERE, "csrc", "fiveeq_capi.hip"), os.path.join(_HERE, "csrc", "fiveeq_device.hpp"),
-           os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"))
+# every source of the library, in the order csrc/Makefile (SRCS) hashes them
+SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
+    "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
+    "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_diag.hpp")) + (
+    os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 
 def source_hash():
-    """sha256 (hex) of the library's three sources as they lie in this tree, concatenated in SOURCES order — what
+    """sha256 (hex) of the library's sources as they lie in this tree, concatenated in SOURCES order — what
     csrc/Makefile stamps into the library; None when the tree carries no sources (an installed binary)."""
     import hashlib
     if not all(os.path.exists(p) for p in SOURCES):

@@ -46,11 +46,22 @@ int fail(int code, const char* fmt, ...) {
     X(1, 1, 0) X(4, 1, 0) X(4, 4, 0)            \
     X(1, 1, 1) X(4, 1, 1) X(4, 4, 1) X(4, 4, 4)
 
-int layout_code(const fiveeq_model* m) {
+// the layout code of n_gas <= 3 pool counts: P0 P1 P2 as decimal digits (0 = gas absent)
+int layout_code(int n_gas, const int32_t* n_pools) {
     int p[3] = {0, 0, 0};
-    for (int g = 0; g < m->n_gas; ++g) p[g] = m->gas[g].n_pools;
+    for (int g = 0; g < n_gas; ++g) p[g] = n_pools[g];
     return p[0] * 100 + p[1] * 10 + p[2];
 }
+int layout_code(const fiveeq_model* m) {
+    int32_t p[3] = {0, 0, 0};
+    for (int g = 0; g < m->n_gas; ++g) p[g] = m->gas[g].n_pools;
+    return layout_code(3, p);
+}
+
+// the refusals of a layout, one text each
+int no_kernel(int code) { return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", code); }
+int no_misfit_form(int code) { return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", code); }
+int no_forcing_form(int code) { return fail(FIVEEQ_E_INVALID, "pool layout %03d has no forcing form", code); }
 
 bool layout_ok(int code) {
     switch (code) {
@@ -86,8 +97,7 @@ int check_model(const fiveeq_model* m) {
         if (!(gs.emis2conc > 0.0) || !std::isfinite(gs.emis2conc))
             return fail(FIVEEQ_E_INVALID, "gas %d: emis2conc=%g must be > 0", g, gs.emis2conc);
     }
-    if (!layout_ok(layout_code(m)))
-        return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", layout_code(m));
+    if (!layout_ok(layout_code(m))) return no_kernel(layout_code(m));
     return FIVEEQ_OK;
 }
 
@@ -193,7 +203,7 @@ struct RunArgs {
     ForcRows<T> fc;              // the forcing forms' scale rows and table (else none)
 };
 
-// ---- packed fp32 lanes: two members per lane (fiveeq_device.hpp, "Lane value types") ----------------------------
+// ---- packed fp32 lanes: two members per lane (fiveeq_math.hpp, "Lane value types") ----------------------------
 // The fp32 entry points run the packed kernels whenever the rows allow 8-byte accesses: even row stride, every row
 // pointer 8-byte aligned, at least two members.  Otherwise (odd ld, a sub-range starting at an odd member) the
 // one-member-per-lane kernels run; both give the same bits.  fiveeq_set_f32_packing(0) forces the scalar kernels (A/B
@@ -202,7 +212,7 @@ struct RunArgs {
 // every launch of one call takes the same kernel shape.
 std::atomic<int> g_f32_packing{1};
 
-// ---- cache policy of the per-step kernel's state and parameter rows (fiveeq_device.hpp, step_kernel<..., NT>) --------------
+// ---- cache policy of the per-step kernel's state and parameter rows (fiveeq_step.hpp, step_kernel<..., NT>) --------------
 // STREAMED (non-temporal) pays exactly when the rows of this launch cannot be in the Infinity Cache at the next step:
 //   * the launch's own rows fill it: n members x (S (SP + 2) + 3G + 2) words >= the cache, for S scenarios (1 without the
 //     scenario axis: each scenario carries its own state rows, the parameter rows are shared) — false for the chunks of a
@@ -239,12 +249,14 @@ struct LaneOf<float> {
 
 // the layouts with MISFIT instantiations: a lone 4-pool gas (CO2-only) and 4 + 1 + 1 (CO2, CH4, N2O)
 constexpr bool misfit_layout(int p0, int p1, int p2) { return (p0 == 4 && p1 == 0 && p2 == 0) || (p0 == 4 && p1 == 1 && p2 == 1); }
+constexpr bool misfit_layout(int code) { return misfit_layout(code / 100, code / 10 % 10, code % 10); }
 // ... and the PACKED fp32 fused kernel carries it for 4 + 1 + 1 only.  For {4} the two members' accumulators (12 KiB of LDS per
 // workgroup on top of 20 KiB) would cost the packed form two waves per SIMD (6 -> 4); those runs take the one-member-per-lane
 // fp32 fused kernel, which keeps its plain counterpart's 7 waves (same bits either way: packed lanes mirror the scalar ones).
 constexpr bool misfit_packed_fused(int p0, int p1, int p2) { return p0 == 4 && p1 == 1 && p2 == 1; }
 // the layouts with FORC instantiations: those that have the misfit form, with which it combines
 constexpr bool forcing_layout(int p0, int p1, int p2) { return misfit_layout(p0, p1, p2); }
+constexpr bool forcing_layout(int code) { return misfit_layout(code); }
 
 // ---- the two launchers: one step of the per-step kernel, one span [t_begin, t_end) of the time-fused kernel ----------------
 // The compile-time flags pick the kernel family; packing, the row policy and the pool layout are decided here per launch.
@@ -277,9 +289,9 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
 #define X(p0, p1, p2)                                                                             \
     case (p0) * 100 + (p1) * 10 + (p2):                                                           \
         if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                     \
-            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);         \
+            return no_misfit_form(a.code);                                                        \
         } else if constexpr (FORC && !forcing_layout(p0, p1, p2)) {                               \
-            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no forcing form", a.code);        \
+            return no_forcing_form(a.code);                                                       \
         } else {                                                                                  \
             /* the streamed row form: plain and scenario launches only (the engine schedules misfit runs chunk-major) */ \
             if constexpr (!BINS && !MISFIT && !FORC) {                                                   \
@@ -297,7 +309,7 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
 #undef X
 #undef FIVEEQ_STEP_LAUNCH
         default:
-            return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+            return no_kernel(a.code);
     }
     HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
@@ -328,9 +340,9 @@ int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
 #define X(p0, p1, p2)                                                                                  \
     case (p0) * 100 + (p1) * 10 + (p2):                                                                \
         if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                          \
-            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form", a.code);              \
+            return no_misfit_form(a.code);                                                             \
         } else if constexpr (FORC && !forcing_layout(p0, p1, p2)) {                                    \
-            return fail(FIVEEQ_E_INVALID, "pool layout %03d has no forcing form", a.code);             \
+            return no_forcing_form(a.code);                                                            \
         } else {                                                                                       \
             if constexpr (HAS_PACKED && (!MISFIT || misfit_packed_fused(p0, p1, p2))) {                \
                 if (packed) {                                                                          \
@@ -345,7 +357,7 @@ int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
 #undef X
 #undef FIVEEQ_FUSED_LAUNCH
         default:
-            return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+            return no_kernel(a.code);
     }
     HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
@@ -423,7 +435,7 @@ template <typename T>
 int check_misfit(RunArgs<T>& a, const double* obs, double* misfit) {
     if (!obs || !misfit) return fail(FIVEEQ_E_INVALID, "NULL misfit pointer (obs=%p misfit=%p)", (const void*)obs, (void*)misfit);
     if ((((uintptr_t)obs) | ((uintptr_t)misfit)) & 7) return fail(FIVEEQ_E_INVALID, "obs and misfit must be 8-byte aligned");
-    if (!misfit_layout(a.code / 100, a.code / 10 % 10, a.code % 10))
+    if (!misfit_layout(a.code))
         return fail(FIVEEQ_E_INVALID, "pool layout %03d has no misfit form (pools {4} and 4+1+1 have)", a.code);
     a.mf.obs = obs;
     a.mf.misfit = misfit;
@@ -438,7 +450,7 @@ int check_forcing(RunArgs<T>& a, const T* fscale, const T* fext, int32_t n_fext)
     if (((uintptr_t)fscale) & (sizeof(T) - 1)) return fail(FIVEEQ_E_INVALID, "fscale must be %d-byte aligned", (int)sizeof(T));
     if (n_fext > 0 && !fext) return fail(FIVEEQ_E_INVALID, "fext is NULL with n_fext=%d", n_fext);
     if (((uintptr_t)fext) & (sizeof(T) - 1)) return fail(FIVEEQ_E_INVALID, "fext must be %d-byte aligned", (int)sizeof(T));
-    if (!forcing_layout(a.code / 100, a.code / 10 % 10, a.code % 10))
+    if (!forcing_layout(a.code))
         return fail(FIVEEQ_E_INVALID, "pool layout %03d has no forcing form (pools {4} and 4+1+1 have)", a.code);
     a.fc.fscale = fscale;
     a.fc.fext = n_fext > 0 ? fext : fscale;      // n_fext == 0: no kernel reads the table (no record, no staging); kept non-NULL
@@ -605,7 +617,7 @@ int run_small(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int3
         break;
             FIVEEQ_LAYOUTS(X)
 #undef X
-            default: return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+            default: return no_kernel(a.code);
         }
     } else {
 #define FIVEEQ_SMALL1(p0, lpm)                                                                                     \
@@ -631,7 +643,7 @@ int run_small(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int3
         break;
             X(1, 1, 0) X(4, 1, 0) X(4, 4, 0) X(1, 1, 1) X(4, 1, 1) X(4, 4, 1) X(4, 4, 4)
 #undef X
-            default: return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no compiled kernel", a.code);
+            default: return no_kernel(a.code);
         }
 #undef FIVEEQ_SMALL1
     }
@@ -742,12 +754,9 @@ int64_t fiveeq_stats_waves(int64_t n_members) { return n_members < 1 ? 0 : (n_me
 
 int fiveeq_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     if (!n_pools || n_gas < 1 || n_gas > FIVEEQ_MAX_GAS) return 0;
-    int p[3] = {0, 0, 0};
-    for (int g = 0; g < n_gas; ++g) {
+    for (int g = 0; g < n_gas; ++g)
         if (n_pools[g] < 1 || n_pools[g] > FIVEEQ_MAX_POOLS) return 0;
-        p[g] = n_pools[g];
-    }
-    return layout_ok(p[0] * 100 + p[1] * 10 + p[2]) ? 1 : 0;
+    return layout_ok(layout_code(n_gas, n_pools)) ? 1 : 0;
 }
 
 int fiveeq_step_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
@@ -914,10 +923,7 @@ int fiveeq_plan_create_obs_f32(const fiveeq_model* model, int64_t n_members, int
                                     T_stats, plan_out, obs, misfit);
 }
 int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t* n_pools) {
-    if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;
-    int p[3] = {0, 0, 0};
-    for (int g = 0; g < n_gas; ++g) p[g] = n_pools[g];
-    return misfit_layout(p[0], p[1], p[2]) ? 1 : 0;
+    return fiveeq_layout_supported(n_gas, n_pools) && misfit_layout(layout_code(n_gas, n_pools)) ? 1 : 0;
 }
 
 int fiveeq_run_scen_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
@@ -1005,18 +1011,12 @@ int fiveeq_plan_create_forc_f32(const fiveeq_model* model, int64_t n_members, in
                                                 n_rows, T_stats, plan_out, obs, misfit, 1, fscale, fext, n_fext);
 }
 int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t* n_pools) {
-    if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;
-    int p[3] = {0, 0, 0};
-    for (int g = 0; g < n_gas; ++g) p[g] = n_pools[g];
-    return forcing_layout(p[0], p[1], p[2]) ? 1 : 0;
+    return fiveeq_layout_supported(n_gas, n_pools) && forcing_layout(layout_code(n_gas, n_pools)) ? 1 : 0;
 }
 int32_t fiveeq_max_fext(void) { return MAX_FEXT; }
 
 int32_t fiveeq_small_lanes(int32_t n_gas, const int32_t* n_pools) {
-    if (!fiveeq_layout_supported(n_gas, n_pools)) return 0;
-    int p[3] = {0, 0, 0};
-    for (int g = 0; g < n_gas; ++g) p[g] = n_pools[g];
-    return small_lanes(p[0] * 100 + p[1] * 10 + p[2]);
+    return fiveeq_layout_supported(n_gas, n_pools) ? small_lanes(layout_code(n_gas, n_pools)) : 0;
 }
 int fiveeq_set_f32_packing(int on) { return g_f32_packing.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 

@@ -1,0 +1,238 @@
+// fiveeq_fused.hpp — kernel 2: the time-fused step (fused_kernel).
+// Part of fiveeq_device.hpp, which includes it after the shared constants: include that header, not this one.
+#pragma once
+
+namespace fiveeq {
+
+// Where the fused kernel keeps a lane's G + MAX_FEXT forcing scales (FORC), and how many steps it stages per refill.
+// Registers by default.  The fp64 4 + 1 + 1 form is the exception: its plain kernel sits at 117 VGPRs, 4 waves per SIMD, and
+// seven fp64 scales in registers took it to 129 (135 with the misfit): 3 waves.  There the scales live in a lane-private LDS
+// slot fs_s[G + MAX_FEXT][FIVEEQ_BLOCK], like the misfit accumulators (consecutive lanes, consecutive words: no bank
+// conflicts, no barrier), read back with one ds_read per fma; and so that four workgroups still fit a CU's 160 KB beside the
+// misfit slot (14 + 6 KB of slots on 17 KB of statistics tile and model), it stages 25 steps per refill instead of 125
+// (2.4 KB of drive and table records instead of 12): 39984 B per workgroup with the misfit, under the 40960 a static_assert in
+// the kernel holds it to.  profiles/r08/forcing_isa.txt has the counts.
+// With SCEN (round 9) the fp32 {4} form takes the slot too: its plain scenario kernel sits at 65 VGPRs, 7 waves per SIMD, and five
+// fp32 scales in registers took it to 74: 6 waves; with the slot it is at 66 and keeps 7 (seven workgroups of 14.5 KB fit a CU).
+// The fp64 {4} and the packed fp32 {4} scenario forms lose a wave either way (slot: 103 and 85 VGPRs where 96 and 80 would be
+// needed, and six packed workgroups of 27.6 KB would not fit a CU), exactly as their single-scenario forms do: they keep
+// the registers.  profiles/r09/scenario_forcing_isa.txt.  WGS: the workgroups per CU the slot has to leave room for.
+template <typename V, typename L, bool MISFIT, bool FORC, bool SCEN = false>
+struct FusedForc {
+    static constexpr bool FS_LDS = false;
+    static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK;
+    static constexpr int WGS = 4;
+};
+template <bool MISFIT, bool SCEN>
+struct FusedForc<double, Layout<4, 1, 1>, MISFIT, true, SCEN> {
+    static constexpr bool FS_LDS = true;
+    static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK < 25 ? FIVEEQ_FUSED_CHUNK : 25;
+    static constexpr int WGS = 4;
+};
+template <>
+struct FusedForc<float, Layout<4, 0, 0>, false, true, true> {
+    static constexpr bool FS_LDS = true;
+    static constexpr int CHUNK = FIVEEQ_FUSED_CHUNK < 25 ? FIVEEQ_FUSED_CHUNK : 25;
+    static constexpr int WGS = 7;
+};
+constexpr int LDS_PER_CU = 160 * 1024;            // MI355X
+
+// ---------------------------------------------------------------------------------
+// Kernel 2 — TIME-FUSED: one launch advances [t_begin, t_end); a member's state and
+// parameters stay in registers for the whole span, the drive table is staged into LDS
+// FIVEEQ_FUSED_CHUNK steps at a time, and only the C/T rows of stored steps go to HBM.
+// Per member-step traffic: w (G + 1) + w (2 SP + 3 G + 6) / n_steps.
+// Same member_step() as kernel 1: results are bit-identical.
+// ---------------------------------------------------------------------------------
+//
+// INV = true: concentration-driven form.  drive[t][0..2] are target concentrations, cumE [G][ld] is
+// per-member cumulative-emission state (in/out), and C_traj receives the DIAGNOSED EMISSIONS.
+// (112 VGPRs at fp64 4+1+1 = 4 waves/SIMD; launch-bounds hints for 5 or 6 waves spill: -3 % / -16 %.)
+//
+// MISFIT = true (round 7; INV, BINS and COMP false): the member's misfit accumulators (misfit_update()) are loaded from
+// misfit [3][ld] fp64 once at launch start, carried on chip and stored once at the end — 48 B per member and launch.
+// THE CARRIER IS LDS, NOT REGISTERS: three fp64 per member are 6 VGPRs (12 on a packed lane), and in registers they cost the
+// fp64 {4} form a wave per SIMD (93 -> 105 VGPRs: 5 -> 4 waves) and the fp32 {4} form one too (66 -> 74: 7 -> 6).  Each lane
+// keeps its own words in a lane-private LDS slot (acc_s[3 W][FIVEEQ_BLOCK]: consecutive lanes, consecutive 8-byte words,
+// no bank conflicts, no barrier — a wave's LDS operations complete in program order); a window step adds 3 ds_read_b64 +
+// 3 ds_write_b64 per member beside the step's VALU.  The step's obs record is wave-uniform and read with SCALAR loads
+// straight from obs [n_steps][4] (no LDS staging: the 3 KB a chunk of records would take is what keeps the fp64 {4} form at
+// five workgroups per CU, 5 x 31 KB of 160 KB), so the window test is a scalar branch.  Every MISFIT instantiation keeps
+// its plain counterpart's waves per SIMD with no scratch (tools/kernel_isa_stats.py); the packed fp32 form is instantiated
+// for 4 + 1 + 1 only (fiveeq_capi.hip, misfit_packed_fused).
+//
+// SCEN = true (ABI v13; INV, BINS, COMP and MISFIT false): the grid's y dimension is the emission scenario.  A workgroup is
+// scenario-uniform: it stages its own scenario's drive chunk and offsets the state, row and statistics pointers by the
+// scenario strides of kernel 1s (all derived from ld, n_steps and n_rows, so no argument is added).  With SCEN false not
+// one instruction of the kernel changes.
+//
+// FORC = true (round 8; INV, BINS and COMP false, with or without MISFIT): per-member forcing scales
+// (member_step<.., FORC>).  The G + n_fext scales are loaded once at launch start and stay on chip for the span; the table chunk
+// fext [tc .. tc + nt)[MAX_FEXT] is staged into LDS beside the drive chunk.  Where the scales live is FS_LDS, below.
+// With SCEN (round 9; MISFIT false) the table is fext [n_scen][n_steps][MAX_FEXT], one per scenario: the workgroup offsets it
+// by its scenario like the drive table; the scale rows are shared by the scenarios.
+template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false,
+          bool SCEN = false, bool FORC = false>
+__global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
+    const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps,
+    const int t_begin, const int t_end, const int64_t n, const int64_t ld,
+    const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
+    typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
+    typename Lane<V>::S* __restrict__ cumE /* [G][ld], INV only */,
+    typename Lane<V>::S* __restrict__ C_traj /* [n_rows][G][ld] or nullptr */,
+    typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
+    const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
+    unsigned short* __restrict__ bin_ring /* BINS: [ring_rows][ld] */, const int ring_rows, const double hist_lo,
+    const double hist_inv_w, const int n_bins,
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */,
+    const typename Lane<V>::S* __restrict__ fscale /* FORC: [G + n_fext][ld] */,
+    const typename Lane<V>::S* __restrict__ fext /* FORC: [n_steps][MAX_FEXT] */, const int n_fext) {
+    using L = Layout<P0, P1, P2>;
+    using T = typename Lane<V>::S;
+    constexpr int W = Lane<V>::W;                 // members per lane
+    static_assert(!(INV && BINS), "no streamed histograms in the concentration-driven form");
+    static_assert(!FORC || (!INV && !BINS && !COMP), "the forcing scales are carried by the plain forward form only");
+    constexpr int CHUNK = FusedForc<V, L, MISFIT, FORC, SCEN>::CHUNK;       // steps staged per refill
+    constexpr bool FS_LDS = FusedForc<V, L, MISFIT, FORC, SCEN>::FS_LDS;    // FORC: the scales in a lane-private LDS slot
+    static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
+    static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
+    if constexpr (SCEN) {
+        const int64_t sc = blockIdx.y;
+        drive += sc * n_steps * DRIVE_STRIDE;
+        R += sc * L::SP * ld;
+        S += sc * 2 * ld;
+        if (C_traj != nullptr) C_traj += sc * n_rows * L::G * ld;
+        if (T_traj != nullptr) T_traj += sc * n_rows * ld;
+        if (stats != nullptr) stats += sc * ((ld + 63) >> 6) * n_steps * 4;
+        if constexpr (FORC) fext += sc * n_steps * MAX_FEXT;         // a table per scenario; fscale is shared: not offset
+    }
+    __shared__ T drv[CHUNK * DRIVE_STRIDE];
+    __shared__ T xs[FORC ? CHUNK * MAX_FEXT : 1];                     // FORC: the table chunk
+    __shared__ V fs_s[FS_LDS ? (L::G + MAX_FEXT) * FIVEEQ_BLOCK : 1];  // FS_LDS: [G + MAX_FEXT][FIVEEQ_BLOCK], lane-private
+    __shared__ double acc_s[MISFIT ? 3 * W * FIVEEQ_BLOCK : 1];       // MISFIT: [3 W][FIVEEQ_BLOCK], lane-private
+    __shared__ V stat_tile[FIVEEQ_BLOCK / 64][STAT_STEPS * STAT_ROW];
+    __shared__ KModel<T> km_s;
+    // the LDS slot exists to keep WGS workgroups (four: 4 waves per SIMD) on a CU: a change that outgrows the budget must not pass
+    static_assert(!FS_LDS || sizeof(drv) + sizeof(xs) + sizeof(fs_s) + sizeof(acc_s) + sizeof(stat_tile) + sizeof(km_s) <=
+                                 LDS_PER_CU / FusedForc<V, L, MISFIT, FORC, SCEN>::WGS,
+                  "FS_LDS form: the workgroups it is there to keep no longer fit a CU's LDS");
+    stage_model(&km_s);
+    const KModel<T>& kmr = km_s;
+
+    const auto [m, active, full, mm] = lane_span<W, FIVEEQ_BLOCK, PARK_FIRST>(n);    // idle tail lanes shadow member 0 and store nothing
+    const int64_t n_rec = (n + 63) >> 6;                                             // statistics records: one per 64 members
+    const int64_t wave = (int64_t)blockIdx.x * (FIVEEQ_BLOCK / 64) + (threadIdx.x >> 6);
+    const bool wave_live = stats != nullptr && wave * W < n_rec;
+    V* const tile = stat_tile[threadIdx.x >> 6];
+    const int n_valid = (int)min((int64_t)64 * W, n - wave * 64 * W);               // members of this wave (<= 0: none)
+    int ks = 0;                                                                      // steps parked in the tile
+    const HistRule<T> rule = make_rule(T(0), hist_lo, hist_inv_w, n_bins);           // (BINS only)
+
+    V rr[3 * L::G], qq[2], Rv[L::SP], Sv[2], Cv[L::G], Tn, cum[L::G];
+    V Rlo[L::SP];                                         // COMP: the compensation words (zero at launch: they do not cross HBM)
+    if constexpr (COMP) {
+#pragma unroll
+        for (int k = 0; k < L::SP; ++k) Rlo[k] = (V)T(0);
+    }
+    if constexpr (INV) {
+#pragma unroll
+        for (int g = 0; g < L::G; ++g) cum[g] = cumE[g * ld + mm];
+    }
+#pragma unroll
+    for (int k = 0; k < L::SP; ++k) Rv[k] = load_lane<V>(R + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) Sv[k] = load_lane<V>(S + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_lane<V>(r + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) qq[k] = load_lane<V>(q + k * ld + mm);
+    V fs_r[FORC && !FS_LDS ? L::G + MAX_FEXT : 1];
+    V* const fs = FS_LDS ? &fs_s[threadIdx.x] : fs_r;    // FORC: scale j of this lane at fs[j * FS_STRIDE]
+    constexpr int FS_STRIDE = FS_LDS ? FIVEEQ_BLOCK : 1;
+    if constexpr (FORC) {
+#pragma unroll
+        for (int k = 0; k < L::G + MAX_FEXT; ++k)
+            fs[k * FS_STRIDE] = k < L::G + n_fext ? load_lane<V>(fscale + k * ld + mm) : (V)T(0);
+    }
+    double* const acc = &acc_s[threadIdx.x];             // MISFIT: word k of member j of this lane at acc[(3 j + k) * FIVEEQ_BLOCK]
+    if constexpr (MISFIT) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const int64_t mj = (j == 0 || full) ? mm + j : mm;    // a packed lane's missing second member shadows the first
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc[(3 * j + k) * FIVEEQ_BLOCK] = misfit[k * ld + mj];
+        }
+    }
+
+    for (int tc = t_begin; tc < t_end; tc += CHUNK) {
+        const int nt = min(CHUNK, t_end - tc);
+        __syncthreads();                                  // previous chunk fully consumed
+        for (int i = threadIdx.x; i < nt * DRIVE_STRIDE; i += FIVEEQ_BLOCK)
+            drv[i] = drive[(int64_t)tc * DRIVE_STRIDE + i];
+        if constexpr (FORC) {
+            // n_fext == 0: member_step reads no record and fext may be NULL — nothing is staged (a wave-uniform test)
+            if (n_fext > 0)
+                for (int i = threadIdx.x; i < nt * MAX_FEXT; i += FIVEEQ_BLOCK) xs[i] = fext[(int64_t)tc * MAX_FEXT + i];
+        }
+        __syncthreads();
+        for (int k = 0; k < nt; ++k) {
+            const T* d = &drv[k * DRIVE_STRIDE];
+            if constexpr (FORC)
+                member_step<V, L, false, false, true>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo, fs, FS_STRIDE, &xs[k * MAX_FEXT],
+                                                      n_fext);
+            else
+                member_step<V, L, INV, COMP>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo);
+            if constexpr (MISFIT) misfit_step(obs + (int64_t)(tc + k) * 4, Tn, acc, 3 * FIVEEQ_BLOCK, FIVEEQ_BLOCK, true);
+            // the output row is wave-uniform: read it once into an SGPR so that the row test is a
+            // scalar branch and the row offsets are scalar arithmetic, not 64-bit VALU per lane
+            const int row = __builtin_amdgcn_readfirstlane((int)d[7]);
+            if (row >= 0 && row < n_rows) {
+                if (active) {
+                    if (C_traj != nullptr) {
+                        T* c = C_traj + (int64_t)row * L::G * ld + m;
+#pragma unroll
+                        for (int g = 0; g < L::G; ++g) store_lane(c + g * ld, Cv[g], full);
+                    }
+                    if (T_traj != nullptr) store_lane(T_traj + (int64_t)row * ld + m, Tn, full);
+                }
+            }
+            if constexpr (BINS) {
+                if (active) store_bin(bin_ring + (int64_t)((tc + k) % ring_rows) * ld + m, rule, Tn, full);
+            }
+            if (wave_live) {
+                tile[ks * STAT_ROW + (threadIdx.x & 63)] = Tn;
+                if (++ks == STAT_STEPS || tc + k + 1 == t_end) {
+                    const int64_t t_first = (int64_t)(tc + k + 1 - ks);
+                    if constexpr (W == 1) {
+                        wave_stats_flush(tile, ks, n_valid, stats + (wave * n_steps + t_first) * 4, 4);
+                    } else {
+                        wave_stats_flush(tile, ks, n_valid, stats + (2 * wave * n_steps + t_first) * 4,
+                                         2 * wave + 1 < n_rec ? stats + ((2 * wave + 1) * n_steps + t_first) * 4 : nullptr, 4);
+                    }
+                    ks = 0;
+                }
+            }
+        }
+    }
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < L::SP; ++k) store_lane(R + k * ld + m, Rv[k], full);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) store_lane(S + k * ld + m, Sv[k], full);
+        if constexpr (INV) {
+#pragma unroll
+            for (int g = 0; g < L::G; ++g) cumE[g * ld + m] = cum[g];
+        }
+        if constexpr (MISFIT) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                if (j == 0 || full) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) misfit[k * ld + m + j] = acc[(3 * j + k) * FIVEEQ_BLOCK];
+                }
+            }
+        }
+    }
+}
+
+}  // namespace fiveeq

@@ -122,8 +122,8 @@ typedef struct fiveeq_model {
 /* new — library identification */
 int         fiveeq_abi_version(void);
 const char *fiveeq_last_error(void);
-/* new — sha256 (hex) of the three sources this library was compiled from, concatenated in this order:
- * fiveeq_capi.hip, fiveeq_device.hpp, include/fiveeq.h — stamped by csrc/Makefile ("unstamped" otherwise).  A binding that
+/* new — sha256 (hex) of the sources this library was compiled from, concatenated in the order of csrc/Makefile's SRCS:
+ * fiveeq_capi.hip, fiveeq_device.hpp and the headers it includes, include/fiveeq.h — stamped by csrc/Makefile ("unstamped" otherwise).  A binding that
  * sits next to those sources recomputes it and refuses a library built from other text (fiveeqscm_amd/_capi.py). */
 const char *fiveeq_source_hash(void);
 /* new — the experiment knobs this library was compiled with (-DFIVEEQ_STEP_WAVES=..., -DFIVEEQ_FUSED_CHUNK=..., non-default

@@ -31,14 +31,17 @@ def test_library_loads_and_exports_every_declared_symbol():
 
 
 def test_shipped_library_is_stamped_with_its_sources_and_has_no_experiment_knobs():
-    """csrc/Makefile stamps the sha256 of (fiveeq_capi.hip, fiveeq_device.hpp, fiveeq.h) into the library; the binding
-    recomputes it from the tree.  The product build carries no experiment flag (timing hooks, occupancy caps, block shapes)."""
+    """csrc/Makefile stamps the sha256 of the library's sources (_capi.SOURCES: fiveeq_capi.hip, fiveeq_device.hpp and the
+    headers it includes, fiveeq.h) into the library; the binding recomputes it from the tree.  The product build carries no
+    experiment flag (timing hooks, occupancy caps, block shapes), and none of its sources carries experiment code."""
     lib = _capi.load()
     assert lib.fiveeq_source_hash().decode() == _capi.source_hash() and len(_capi.source_hash()) == 64
     assert _capi.build_flags(lib) == ""
-    with open(os.path.join(ROOT, "fiveeqscm_amd", "csrc", "fiveeq_device.hpp")) as fh:
-        text = fh.read()
-    assert "wall_clock64" not in text and "s_getreg" not in text, "experiment code belongs in tools/variants/"
+    assert len(_capi.SOURCES) == len(set(_capi.SOURCES)) and any(p.endswith("fiveeq_device.hpp") for p in _capi.SOURCES)
+    for path in _capi.SOURCES:
+        with open(path) as fh:
+            text = fh.read()
+        assert "wall_clock64" not in text and "s_getreg" not in text, f"{path}: experiment code belongs in tools/variants/"
 
 
 def test_a_library_built_from_other_sources_is_refused(tmp_path, monkeypatch):

@@ -109,7 +109,7 @@ def test_observations_change_no_bit_of_the_model(obs, ens, dtype):
 
 
 def test_fp32_chi2_against_the_fp64_oracle(obs, ens):
-    """fp32 T carries at most ~1.7e-5 relative error over the run (fiveeq_device.hpp, the compensated form's note: the default
+    """fp32 T carries at most ~1.7e-5 relative error over the run (fiveeq_member.hpp, the compensated form's note: the default
     fp32 form's worst T error against 50-digit arithmetic); take 4x that of max |T| as the per-step bound dT.  A residual
     r_t = T_t - mean_ref T - o_t then errs by at most 2 dT, so |d chi2| <= sum_t p_t (2 |r_t| 2 dT + (2 dT)^2)."""
     from oracle import c_oracle

@@ -55,7 +55,7 @@ def _ulp_err(got, want):
 
 
 def test_device_math_primitives_within_two_ulp(gpu):
-    """Hand-written expm1 / exp / log / sqrt / reciprocal (fiveeq_device.hpp) against NumPy (glibc /
+    """Hand-written expm1 / exp / log / sqrt / reciprocal (fiveeq_math.hpp) against NumPy (glibc /
     SVML, <= 1 ulp themselves) over the argument ranges the model can produce."""
     from fiveeqscm_amd import _capi
     lib = _capi.load()
