@@ -67,10 +67,39 @@ _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 _mp = ctypes.POINTER(Model)
 
-# name -> (restype, argtypes); every symbol include/fiveeq.h declares
-# (model, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats, stream|plan_out)
-_RUN_ARGS = [_mp, _i64, _i64, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p]
 _STEP_ARGS = [_mp, _i64, _i64, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p]
+
+
+def _run_args(tail, scen=False, cumE=False):
+    """argtypes of a stepping entry point: (model, n, ld, [n_scen,] drive, n_steps, t_begin, t_end, r, q, R, S, [cumE,] C_traj,
+    T_traj, n_rows, T_stats), then its own tail."""
+    return ([_mp, _i64, _i64] + [_i32] * scen + [_p, _i32, _i32, _i32, _p, _p, _p, _p] + [_p] * cumE + [_p, _p, _i32, _p]
+            + list(tail))
+
+
+# the tails: stream; plan_out; (form, k_steps, stream); (obs, misfit); (fscale, fext, n_fext); (lo, hi, n_bins, bin_ring, ring_rows)
+_ST, _PLAN, _FORM, _OBS, _FORC = [_p], [ctypes.POINTER(_p)], [_i32, _i32, _p], [_p, _p], [_p, _p, _i32]
+_RING = [ctypes.c_double, ctypes.c_double, _i32, _p, _i32]
+# the stepping entry points that come as _f64 and _f32: name -> _run_args(...)
+_RUNS = {
+    "run": _run_args(_ST),
+    "run_fused": _run_args(_ST),
+    "run_ksteps": _run_args([_i32] + _ST),
+    "run_small": _run_args([_i32] + _ST),
+    "run_bins": _run_args(_RING + _ST),
+    "run_fused_bins": _run_args(_RING + _ST),
+    "run_inverse": _run_args(_ST, cumE=True),
+    "plan_create": _run_args(_PLAN),
+    "run_obs": _run_args(_OBS + _FORM),
+    "plan_create_obs": _run_args(_OBS + _PLAN),
+    "run_scen": _run_args(_FORM, scen=True),
+    "plan_create_scen": _run_args(_PLAN, scen=True),
+    "run_forc": _run_args(_FORC + _OBS + _FORM),
+    "plan_create_forc": _run_args(_FORC + _OBS + _PLAN),
+    "run_scen_forc": _run_args(_FORC + _FORM, scen=True),
+    "plan_create_scen_forc": _run_args(_FORC + _PLAN, scen=True),
+}
+# name -> (restype, argtypes); every symbol include/fiveeq.h declares
 SIGNATURES = {
     "fiveeq_abi_version": (ctypes.c_int, []),
     "fiveeq_last_error": (ctypes.c_char_p, []),
@@ -81,43 +110,12 @@ SIGNATURES = {
     "fiveeq_stats_waves": (ctypes.c_int64, [_i64]),
     "fiveeq_step_f64": (ctypes.c_int, _STEP_ARGS),
     "fiveeq_step_f32": (ctypes.c_int, _STEP_ARGS),
-    "fiveeq_run_f64": (ctypes.c_int, _RUN_ARGS),
-    "fiveeq_run_f32": (ctypes.c_int, _RUN_ARGS),
-    "fiveeq_run_fused_f64": (ctypes.c_int, _RUN_ARGS),
-    "fiveeq_run_fused_f32": (ctypes.c_int, _RUN_ARGS),
-    "fiveeq_run_fused_bins_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [ctypes.c_double, ctypes.c_double, _i32, _p, _i32, _p]),
-    "fiveeq_run_fused_bins_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [ctypes.c_double, ctypes.c_double, _i32, _p, _i32, _p]),
+    **{f"fiveeq_{name}_{sfx}": (ctypes.c_int, args) for name, args in _RUNS.items() for sfx in ("f64", "f32")},
+    "fiveeq_run_fused_comp_f32": (ctypes.c_int, _run_args([_i32] + _RING + _ST)),
+    "fiveeq_run_small_comp_f32": (ctypes.c_int, _run_args(_ST)),
     "fiveeq_hist_bins": (ctypes.c_int, [_i32, _i64, _i64, _p, _i32, _p, _p]),
-    "fiveeq_run_bins_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [ctypes.c_double, ctypes.c_double, _i32, _p, _i32, _p]),
-    "fiveeq_run_bins_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [ctypes.c_double, ctypes.c_double, _i32, _p, _i32, _p]),
-    "fiveeq_plan_create_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [ctypes.POINTER(_p)]),
-    "fiveeq_plan_create_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [ctypes.POINTER(_p)]),
-    "fiveeq_run_inverse_f64": (ctypes.c_int, _RUN_ARGS[:11] + [_p] + _RUN_ARGS[11:]),
-    "fiveeq_run_inverse_f32": (ctypes.c_int, _RUN_ARGS[:11] + [_p] + _RUN_ARGS[11:]),
-    "fiveeq_run_ksteps_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_i32, _p]),
-    "fiveeq_run_ksteps_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_i32, _p]),
-    "fiveeq_run_small_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_i32, _p]),
-    "fiveeq_run_small_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_i32, _p]),
-    "fiveeq_run_fused_comp_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_i32, ctypes.c_double, ctypes.c_double, _i32, _p, _i32, _p]),
-    "fiveeq_run_small_comp_f32": (ctypes.c_int, _RUN_ARGS),
-    "fiveeq_run_obs_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _i32, _p]),
-    "fiveeq_run_obs_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _i32, _p]),
-    "fiveeq_plan_create_obs_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, ctypes.POINTER(_p)]),
-    "fiveeq_plan_create_obs_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, ctypes.POINTER(_p)]),
     "fiveeq_misfit_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32)]),
-    "fiveeq_run_scen_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_i32, _i32, _p]),
-    "fiveeq_run_scen_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_i32, _i32, _p]),
-    "fiveeq_plan_create_scen_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [ctypes.POINTER(_p)]),
-    "fiveeq_plan_create_scen_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [ctypes.POINTER(_p)]),
     "fiveeq_max_scenarios": (_i32, []),
-    "fiveeq_run_forc_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, _i32, _i32, _p]),
-    "fiveeq_run_forc_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, _i32, _i32, _p]),
-    "fiveeq_plan_create_forc_f64": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, ctypes.POINTER(_p)]),
-    "fiveeq_plan_create_forc_f32": (ctypes.c_int, _RUN_ARGS[:-1] + [_p, _p, _i32, _p, _p, ctypes.POINTER(_p)]),
-    "fiveeq_run_scen_forc_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, _i32, _i32, _p]),
-    "fiveeq_run_scen_forc_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, _i32, _i32, _p]),
-    "fiveeq_plan_create_scen_forc_f64": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, ctypes.POINTER(_p)]),
-    "fiveeq_plan_create_scen_forc_f32": (ctypes.c_int, _RUN_ARGS[:3] + [_i32] + _RUN_ARGS[3:-1] + [_p, _p, _i32, ctypes.POINTER(_p)]),
     "fiveeq_forcing_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32)]),
     "fiveeq_max_fext": (_i32, []),
     "fiveeq_small_lanes": (_i32, [_i32, ctypes.POINTER(_i32)]),

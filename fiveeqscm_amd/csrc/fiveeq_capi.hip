@@ -180,23 +180,30 @@ struct ForcRows {
     int n_fext = 0;
 };
 
+// the fifteen arguments every stepping entry point takes (model ... T_stats), in the order of the C ABI: each extern "C"
+// wrapper brace-initialises one
+template <typename T>
+struct BaseArgs {
+    const fiveeq_model* m;
+    int64_t n, ld;
+    const T* drive;
+    int32_t n_steps, t_begin, t_end;
+    const T *r, *q;
+    T *R, *S, *C_traj, *T_traj;
+    int32_t n_rows;
+    double* stats;
+};
+
 // everything one C-ABI call hands its launches: filled by make_args() and the checker of each optional feature
 template <typename T>
-struct RunArgs {
+struct RunArgs : BaseArgs<T> {
     KModel<T> km;
     int code;
     int n_gas;
-    int64_t n, ld;
-    const T* drive;
-    const T *r, *q;
-    T *R, *S, *C_traj, *T_traj;
-    int n_rows;
-    int n_steps;
-    int t_begin, t_end;
-    double* stats;
     int packing;                 // the fp32 packing switch as this call found it
     bool stream_rows;            // the per-step launches of this call take the STREAMED (non-temporal) row form
-    int n_scen;                  // scenarios (the scenario forms; 1 = no scenario axis)
+    bool scen = false;           // the call is of a scenario family (step_scen_kernel, fused_kernel<.., SCEN>), whatever n_scen
+    int n_scen;                  // scenarios (the scenario forms; 1 without the scenario axis)
     T* cumE = nullptr;           // the inverse form's cumulative emissions
     BinRing br;                  // the histogram forms' ring (else none)
     MisfitRows mf;               // the constrained forms' accumulators (else none)
@@ -383,33 +390,18 @@ int each_span(const RunArgs<T>& a, int k_steps, Launch&& launch) {
 
 // ---- validation of one call: make_args() for what every stepping entry point takes, one checker per optional feature ------
 template <typename T>
-int make_args(RunArgs<T>& a, const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-              int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
-              int32_t n_scen = 1) {
-    if (int rc = check_run(m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S)) return rc;
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
-    a.km = make_kmodel<T>(m);
-    a.code = layout_code(m);
-    a.n_gas = m->n_gas;
-    a.n = n;
-    a.ld = ld;
-    a.drive = drive;
-    a.r = r;
-    a.q = q;
-    a.R = R;
-    a.S = S;
-    a.C_traj = C_traj;
-    a.T_traj = T_traj;
-    a.n_rows = n_rows;
-    a.n_steps = n_steps;
-    a.t_begin = t_begin;
-    a.t_end = t_end;
-    a.stats = stats;
+int make_args(RunArgs<T>& a, const BaseArgs<T>& b, int32_t n_scen = 1) {
+    if (int rc = check_run(b.m, b.n, b.ld, b.drive, b.n_steps, b.t_begin, b.t_end, b.r, b.q, b.R, b.S)) return rc;
+    if (b.n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", b.n_rows);
+    static_cast<BaseArgs<T>&>(a) = b;
+    a.km = make_kmodel<T>(b.m);
+    a.code = layout_code(b.m);
+    a.n_gas = b.m->n_gas;
     a.packing = g_f32_packing.load(std::memory_order_relaxed);
     int sum_pools = 0;
-    for (int g = 0; g < m->n_gas; ++g) sum_pools += m->gas[g].n_pools;
-    a.stream_rows =
-        rows_streamed(g_row_policy.load(std::memory_order_relaxed), m->n_gas, sum_pools, n_scen, n, ld, (int)sizeof(T));
+    for (int g = 0; g < b.m->n_gas; ++g) sum_pools += b.m->gas[g].n_pools;
+    a.stream_rows = rows_streamed(g_row_policy.load(std::memory_order_relaxed), b.m->n_gas, sum_pools, n_scen, b.n, b.ld,
+                                  (int)sizeof(T));
     a.n_scen = n_scen;
     return FIVEEQ_OK;
 }
@@ -474,80 +466,74 @@ int check_form(int32_t form, int32_t k_steps, int32_t k_min) {
 }
 
 // ---- the entry points (validated: nothing is launched before every check has passed) ---------------------------------------
-// the forward model, plain, constrained (MISFIT) or under several scenarios (SCEN): one launch per step, or the fused kernel
-// over spans of k_steps steps
-template <typename T, bool MISFIT = false, bool SCEN = false, bool FORC = false>
-int run_form(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
+// What a forward call carries beyond the base arguments, in the order of the C ABI: the scenario axis and its count
+// (fiveeq_run_scen, fiveeq_run_scen_forc), the forcing rows (fiveeq_run_forc, fiveeq_run_scen_forc) and the misfit rows —
+// REQUIRED by fiveeq_run_obs, OPTIONAL for fiveeq_run_forc (obs and misfit both NULL, or both set); the same for the
+// plan_create twins.  The plain family (fiveeq_step/run/run_fused/run_ksteps, fiveeq_plan_create) carries none: {}.
+enum Use { ABSENT, OPTIONAL, REQUIRED };
+template <typename T>
+struct Features {
+    bool scen = false;           // a scenario family: n_scen is the caller's, checked whatever its value
+    int32_t n_scen = 1;
+    bool forc = false;           // a forcing family: fc is the caller's
+    ForcRows<T> fc;
+    Use misfit = ABSENT;
+    MisfitRows mf;
+};
+
+// Every check of a forward call but its last (the form of a run, the range of a plan), in the ONE order every family reports
+// in (tests/test_forward_precedence_cpu.py): the scenario count, [a plan: plan_out, cleared before anything else,] the base
+// arguments, the forcing rows, obs and misfit given together, the misfit rows.
+template <typename T>
+int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan = false, void** plan_out = nullptr) {
+    if (plan_out) *plan_out = nullptr;
+    if (int rc = f.scen ? check_scen(f.n_scen) : FIVEEQ_OK) return rc;
+    if (plan && !plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
+    if (int rc = make_args(a, b, f.n_scen)) return rc;
+    a.scen = f.scen;
+    if (int rc = f.forc ? check_forcing(a, f.fc.fscale, f.fc.fext, f.fc.n_fext) : FIVEEQ_OK) return rc;
+    if (f.misfit == OPTIONAL && (f.mf.obs == nullptr) != (f.mf.misfit == nullptr))
+        return fail(FIVEEQ_E_INVALID, "obs and misfit go together: both NULL (no misfit) or both set (obs=%p misfit=%p)",
+                    (const void*)f.mf.obs, (void*)f.mf.misfit);
+    if (f.misfit == REQUIRED || (f.misfit == OPTIONAL && f.mf.obs)) return check_misfit(a, f.mf.obs, f.mf.misfit);
+    return FIVEEQ_OK;
+}
+
+// one kernel family: one launch per step, or the fused kernel over spans of k_steps steps
+template <typename T, bool MISFIT, bool SCEN, bool FORC>
+int run_family(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
     if (form == FIVEEQ_FORM_PER_STEP)
         return each_step(a, [&](int t) { return launch_step<T, false, MISFIT, SCEN, FORC>(a, t, st); });
     return each_span(a, k_steps,
                      [&](int t0, int t1) { return launch_fused<T, false, false, false, MISFIT, SCEN, FORC>(a, t0, t1, st); });
 }
 
-// the forcing forms carry the misfit or not by what the call hands them: obs and misfit both NULL, or both set
+// the forward model in the family prepare() found: plain, MISFIT, SCEN, FORC, FORC + MISFIT or SCEN + FORC (the six that
+// are compiled) — picked once per C call, outside the launch loops
 template <typename T>
-int run_form_forc(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
-    return a.mf.misfit ? run_form<T, true, false, true>(a, form, k_steps, st) : run_form<T, false, false, true>(a, form, k_steps, st);
-}
-template <typename T>
-int check_forc_call(RunArgs<T>& a, const T* fscale, const T* fext, int32_t n_fext, const double* obs, double* misfit) {
-    if (int rc = check_forcing(a, fscale, fext, n_fext)) return rc;
-    if ((obs == nullptr) != (misfit == nullptr))
-        return fail(FIVEEQ_E_INVALID, "obs and misfit go together: both NULL (no misfit) or both set (obs=%p misfit=%p)",
-                    (const void*)obs, (void*)misfit);
-    return obs ? check_misfit(a, obs, misfit) : FIVEEQ_OK;
+int run_form(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
+    const bool forc = a.fc.fscale != nullptr, misfit = a.mf.misfit != nullptr;
+    if (a.scen)
+        return forc ? run_family<T, false, true, true>(a, form, k_steps, st) : run_family<T, false, true, false>(a, form, k_steps, st);
+    if (forc)
+        return misfit ? run_family<T, true, false, true>(a, form, k_steps, st) : run_family<T, false, false, true>(a, form, k_steps, st);
+    return misfit ? run_family<T, true, false, false>(a, form, k_steps, st) : run_family<T, false, false, false>(a, form, k_steps, st);
 }
 
-// fiveeq_run_forc: the forward model with per-member forcing scales
+// every fiveeq_run_* of the forward model (k_min: 1 for fiveeq_run_ksteps, whose k_steps has no "whole range" value 0)
 template <typename T>
-int run_forc(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
-             const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, const T* fscale, const T* fext,
-             int32_t n_fext, const double* obs, double* misfit, int32_t form, int32_t k_steps, void* stream) {
+int run_forward(const BaseArgs<T>& b, const Features<T>& f, int32_t form, int32_t k_steps, int32_t k_min, void* stream) {
     RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
-    if (int rc = check_forc_call(a, fscale, fext, n_fext, obs, misfit)) return rc;
-    if (int rc = check_form(form, k_steps, 0)) return rc;
-    return run_form_forc(a, form, k_steps, (hipStream_t)stream);
-}
-
-// fiveeq_run_scen_forc: the scenario axis with per-member forcing scales — the scale rows shared by the scenarios, one category
-// table per scenario
-template <typename T>
-int run_scen_forc(const fiveeq_model* m, int64_t n, int64_t ld, int32_t n_scen, const T* drive, int32_t n_steps, int32_t t_begin,
-                  int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
-                  const T* fscale, const T* fext, int32_t n_fext, int32_t form, int32_t k_steps, void* stream) {
-    if (int rc = check_scen(n_scen)) return rc;
-    RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats, n_scen))
-        return rc;
-    if (int rc = check_forcing(a, fscale, fext, n_fext)) return rc;
-    if (int rc = check_form(form, k_steps, 0)) return rc;
-    return run_form<T, false, true, true>(a, form, k_steps, (hipStream_t)stream);
-}
-
-// fiveeq_step/run/run_fused/run_ksteps (k_min 1), fiveeq_run_obs (MISFIT: obs, misfit) and fiveeq_run_scen (SCEN: n_scen,
-// checked first)
-template <typename T, bool MISFIT = false, bool SCEN = false>
-int run_forward(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-                int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, int32_t form,
-                int32_t k_steps, int32_t k_min, void* stream, const double* obs = nullptr, double* misfit = nullptr,
-                int32_t n_scen = 1) {
-    if (int rc = SCEN ? check_scen(n_scen) : FIVEEQ_OK) return rc;
-    RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats, n_scen))
-        return rc;
-    if (int rc = MISFIT ? check_misfit(a, obs, misfit) : FIVEEQ_OK) return rc;
+    if (int rc = prepare(a, b, f)) return rc;
     if (int rc = check_form(form, k_steps, k_min)) return rc;
-    return run_form<T, MISFIT, SCEN>(a, form, k_steps, (hipStream_t)stream);
+    return run_form(a, form, k_steps, (hipStream_t)stream);
 }
 
 // the streamed histograms: the per-step or the fused kernel <.., BINS = true> writing every member's bin into the ring
 template <typename T, bool FUSED>
-int run_bins(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-             int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
-             double lo, double hi, int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
+int run_bins(const BaseArgs<T>& b, double lo, double hi, int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
     RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    if (int rc = make_args(a, b)) return rc;
     if (int rc = check_ring(a, lo, hi, n_bins, bin_ring, ring_rows)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (FUSED) return each_span(a, 0, [&](int t0, int t1) { return launch_fused<T, false, true>(a, t0, t1, st); });
@@ -555,11 +541,9 @@ int run_bins(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32
 }
 
 template <typename T>
-int run_inverse(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-                int32_t t_end, const T* r, const T* q, T* R, T* S, T* cumE, T* E_traj, T* T_traj, int n_rows,
-                double* stats, void* stream) {
+int run_inverse(const BaseArgs<T>& b, T* cumE, void* stream) {        // (C_traj: the diagnosed emissions E_traj)
     RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, stats)) return rc;
+    if (int rc = make_args(a, b)) return rc;
     if (!cumE) return fail(FIVEEQ_E_INVALID, "cumE is NULL");
     a.cumE = cumE;
     hipStream_t st = (hipStream_t)stream;
@@ -567,12 +551,10 @@ int run_inverse(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
 }
 
 // ---- the compensated fp32 form: the fused kernel <.., COMP = true> over spans of k_steps, with or without the bin ring ----
-int run_fused_comp(const fiveeq_model* m, int64_t n, int64_t ld, const float* drive, int32_t n_steps, int32_t t_begin,
-                   int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj, float* T_traj, int n_rows,
-                   double* stats, int32_t k_steps, double lo, double hi, int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows,
-                   void* stream) {
+int run_fused_comp(const BaseArgs<float>& b, int32_t k_steps, double lo, double hi, int32_t n_bins, uint16_t* bin_ring,
+                   int32_t ring_rows, void* stream) {
     RunArgs<float> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    if (int rc = make_args(a, b)) return rc;
     if (int rc = check_form(FIVEEQ_FORM_FUSED, k_steps, 1)) return rc;
     if (int rc = bin_ring ? check_ring(a, lo, hi, n_bins, bin_ring, ring_rows) : FIVEEQ_OK) return rc;     // optional here
     hipStream_t st = (hipStream_t)stream;
@@ -588,12 +570,11 @@ int small_lanes(int code) { return code == 400 ? 4 : (code == 411 ? 8 : (layout_
 
 // COMP: the compensated fp32 form, small_multi_kernel<.., COMP = true> for every layout, one member per lane
 template <typename T, bool COMP = false>
-int run_small(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-              int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats,
-              int32_t lanes, void* stream) {
+int run_small(const BaseArgs<T>& b, int32_t lanes, void* stream) {
     static_assert(!COMP || std::is_same<T, float>::value, "the compensated form is fp32");
     RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats)) return rc;
+    if (int rc = make_args(a, b)) return rc;
+    const int32_t t_begin = a.t_begin, t_end = a.t_end;
     const int widest = small_lanes(a.code);
     if (lanes == 0) lanes = (widest == 8 && a.stats != nullptr) ? 1 : widest;      // the octet form writes no statistics records
     if (lanes != 1 && lanes != widest)
@@ -660,25 +641,12 @@ struct Plan {
 };
 constexpr uint32_t PLAN_MAGIC = 0x35455146u;  // "FQE5"
 
-// the plan of run_form<T, MISFIT, SCEN>(FIVEEQ_FORM_PER_STEP): that very run, enqueued on a capture stream (FORC: of
-// run_form_forc, the misfit carried when obs and misfit are set; SCEN and FORC: of run_form<T, false, true, true>)
-template <typename T, bool MISFIT = false, bool SCEN = false, bool FORC = false>
-int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, int32_t n_steps, int32_t t_begin,
-                int32_t t_end, const T* r, const T* q, T* R, T* S, T* C_traj, T* T_traj, int n_rows, double* stats, void** plan_out,
-                const double* obs = nullptr, double* misfit = nullptr, int32_t n_scen = 1, const T* fscale = nullptr,
-                const T* fext = nullptr, int32_t n_fext = 0) {
-    if (SCEN) {
-        if (plan_out) *plan_out = nullptr;
-        if (int rc = check_scen(n_scen)) return rc;
-    }
-    if (!plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
-    *plan_out = nullptr;
+// the plan of run_form(FIVEEQ_FORM_PER_STEP) for the family the call is of: that very run, enqueued on a capture stream
+template <typename T>
+int plan_create(const BaseArgs<T>& b, const Features<T>& f, void** plan_out) {
     RunArgs<T> a;
-    if (int rc = make_args(a, m, n, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, stats, n_scen))
-        return rc;
-    if (int rc = MISFIT ? check_misfit(a, obs, misfit) : FIVEEQ_OK) return rc;
-    if (int rc = FORC ? check_forc_call(a, fscale, fext, n_fext, obs, misfit) : FIVEEQ_OK) return rc;
-    if (t_begin == t_end) return fail(FIVEEQ_E_INVALID, "empty step range for a plan");
+    if (int rc = prepare(a, b, f, true, plan_out)) return rc;
+    if (a.t_begin == a.t_end) return fail(FIVEEQ_E_INVALID, "empty step range for a plan");
     hipStream_t cap = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
     hipGraph_t graph = nullptr;
@@ -687,10 +655,7 @@ int plan_create(const fiveeq_model* m, int64_t n, int64_t ld, const T* drive, in
         (void)hipStreamDestroy(cap);
         return fail(FIVEEQ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(e));
     }
-    int rc;
-    if constexpr (FORC && SCEN) rc = run_form<T, false, true, true>(a, FIVEEQ_FORM_PER_STEP, 0, cap);
-    else if constexpr (FORC) rc = run_form_forc(a, FIVEEQ_FORM_PER_STEP, 0, cap);
-    else rc = run_form<T, MISFIT, SCEN>(a, FIVEEQ_FORM_PER_STEP, 0, cap);
+    const int rc = run_form(a, FIVEEQ_FORM_PER_STEP, 0, cap);
     e = hipStreamEndCapture(cap, &graph);
     (void)hipStreamDestroy(cap);
     if (rc != FIVEEQ_OK) {
@@ -763,164 +728,164 @@ int fiveeq_step_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, co
                     int32_t t, const double* r, const double* q, double* R, double* S, double* C_traj, double* T_traj,
                     int32_t n_rows, double* T_stats, void* stream) {
     if (t < 0 || t >= n_steps) return fail(FIVEEQ_E_INVALID, "t=%d outside [0,%d)", t, n_steps);
-    return run_forward<double>(model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                               FIVEEQ_FORM_PER_STEP, 0, 0, stream);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {}, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                    int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
                    double* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_forward<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                               T_stats, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {}, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_fused_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                          int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                          double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_forward<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                               T_stats, FIVEEQ_FORM_FUSED, 0, 0, stream);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {}, FIVEEQ_FORM_FUSED, 0, 0, stream);
 }
 int fiveeq_plan_create_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                            int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                            double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
-    return plan_create<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                          plan_out);
+    return plan_create<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {}, plan_out);
 }
 int fiveeq_step_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                     int32_t t, const float* r, const float* q, float* R, float* S, float* C_traj, float* T_traj,
                     int32_t n_rows, double* T_stats, void* stream) {
     if (t < 0 || t >= n_steps) return fail(FIVEEQ_E_INVALID, "t=%d outside [0,%d)", t, n_steps);
-    return run_forward<float>(model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                              FIVEEQ_FORM_PER_STEP, 0, 0, stream);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t, t + 1, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {}, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                    int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                    float* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_forward<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                              T_stats, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {}, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
 }
 int fiveeq_run_fused_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                          int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                          float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_forward<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                              T_stats, FIVEEQ_FORM_FUSED, 0, 0, stream);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {}, FIVEEQ_FORM_FUSED, 0, 0, stream);
 }
 int fiveeq_run_fused_bins_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                               int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                               double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, double hist_lo,
                               double hist_hi, int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
-    return run_bins<double, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                  T_stats, hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
+    return run_bins<double, true>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                                  hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
 }
 int fiveeq_run_fused_bins_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                               int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                               float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, double hist_lo,
                               double hist_hi, int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
-    return run_bins<float, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                 T_stats, hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
+    return run_bins<float, true>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                                 hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
 }
 int fiveeq_run_bins_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                         int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
                         double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, double hist_lo, double hist_hi,
                         int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
-    return run_bins<double, false>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                   T_stats, hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
+    return run_bins<double, false>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                                   hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
 }
 int fiveeq_run_bins_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                         int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
                         float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, double hist_lo, double hist_hi,
                         int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
-    return run_bins<float, false>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                  T_stats, hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
+    return run_bins<float, false>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                                  hist_lo, hist_hi, n_bins, bin_ring, ring_rows, stream);
 }
 int fiveeq_plan_create_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                            int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                            float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
-    return plan_create<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                          plan_out);
+    return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {}, plan_out);
 }
 
 int fiveeq_run_inverse_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                            int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q,
                            double* R, double* S, double* cumE, double* E_traj, double* T_traj, int32_t n_rows,
                            double* T_stats, void* stream) {
-    return run_inverse<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, cumE, E_traj, T_traj,
-                               n_rows, T_stats, stream);
+    return run_inverse<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, T_stats},
+                               cumE, stream);
 }
 int fiveeq_run_inverse_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                            int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                            float* S, float* cumE, float* E_traj, float* T_traj, int32_t n_rows, double* T_stats,
                            void* stream) {
-    return run_inverse<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, cumE, E_traj, T_traj,
-                              n_rows, T_stats, stream);
+    return run_inverse<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, T_stats},
+                              cumE, stream);
 }
 
 int fiveeq_run_ksteps_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                           int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                           double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, int32_t k_steps,
                           void* stream) {
-    return run_forward<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                               T_stats, FIVEEQ_FORM_FUSED, k_steps, 1, stream);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {}, FIVEEQ_FORM_FUSED, k_steps, 1, stream);
 }
 int fiveeq_run_ksteps_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                           int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                           float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, int32_t k_steps,
                           void* stream) {
-    return run_forward<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                              T_stats, FIVEEQ_FORM_FUSED, k_steps, 1, stream);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {}, FIVEEQ_FORM_FUSED, k_steps, 1, stream);
 }
 int fiveeq_run_fused_comp_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                               int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                               float* T_traj, int32_t n_rows, double* T_stats, int32_t k_steps, double lo, double hi,
                               int32_t n_bins, uint16_t* bin_ring, int32_t ring_rows, void* stream) {
-    return run_fused_comp(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+    return run_fused_comp({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
                           k_steps, lo, hi, n_bins, bin_ring, ring_rows, stream);
 }
 int fiveeq_run_small_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
                          int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                          double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, int32_t lanes_per_member,
                          void* stream) {
-    return run_small<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+    return run_small<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
                              lanes_per_member, stream);
 }
 int fiveeq_run_small_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
                          int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                          float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, int32_t lanes_per_member,
                          void* stream) {
-    return run_small<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+    return run_small<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
                             lanes_per_member, stream);
 }
 int fiveeq_run_small_comp_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                               int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                               float* T_traj, int32_t n_rows, double* T_stats, void* stream) {
-    return run_small<float, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
+    return run_small<float, true>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
                                   1, stream);
 }
 int fiveeq_run_obs_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                        int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
                        double* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit, int32_t form,
                        int32_t k_steps, void* stream) {
-    return run_forward<double, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                     n_rows, T_stats, form, k_steps, 0, stream, obs, misfit);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {false, 1, false, {}, REQUIRED, {obs, misfit}}, form, k_steps, 0, stream);
 }
 int fiveeq_run_obs_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                        int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                        float* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit, int32_t form,
                        int32_t k_steps, void* stream) {
-    return run_forward<float, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                    n_rows, T_stats, form, k_steps, 0, stream, obs, misfit);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {false, 1, false, {}, REQUIRED, {obs, misfit}}, form, k_steps, 0, stream);
 }
 int fiveeq_plan_create_obs_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                                int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
                                double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit,
                                void** plan_out) {
-    return plan_create<double, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                     T_stats, plan_out, obs, misfit);
+    return plan_create<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {false, 1, false, {}, REQUIRED, {obs, misfit}}, plan_out);
 }
 int fiveeq_plan_create_obs_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                                int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
                                float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, const double* obs, double* misfit,
                                void** plan_out) {
-    return plan_create<float, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                    T_stats, plan_out, obs, misfit);
+    return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {false, 1, false, {}, REQUIRED, {obs, misfit}}, plan_out);
 }
 int fiveeq_misfit_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     return fiveeq_layout_supported(n_gas, n_pools) && misfit_layout(layout_code(n_gas, n_pools)) ? 1 : 0;
@@ -930,85 +895,85 @@ int fiveeq_run_scen_f64(const fiveeq_model* model, int64_t n_members, int64_t ld
                         int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
                         double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, int32_t form, int32_t k_steps,
                         void* stream) {
-    return run_forward<double, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj,
-                                            T_traj, n_rows, T_stats, form, k_steps, 0, stream, nullptr, nullptr, n_scen);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {true, n_scen}, form, k_steps, 0, stream);
 }
 int fiveeq_run_scen_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
                         int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
                         float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, int32_t form, int32_t k_steps,
                         void* stream) {
-    return run_forward<float, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj,
-                                           T_traj, n_rows, T_stats, form, k_steps, 0, stream, nullptr, nullptr, n_scen);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {true, n_scen}, form, k_steps, 0, stream);
 }
 int fiveeq_plan_create_scen_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
                                 int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                                 double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
-    return plan_create<double, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                            n_rows, T_stats, plan_out, nullptr, nullptr, n_scen);
+    return plan_create<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {true, n_scen}, plan_out);
 }
 int fiveeq_plan_create_scen_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
                                 int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                                 float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
-    return plan_create<float, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                           n_rows, T_stats, plan_out, nullptr, nullptr, n_scen);
+    return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {true, n_scen}, plan_out);
 }
 int32_t fiveeq_max_scenarios(void) { return MAX_SCENARIOS; }
 int fiveeq_run_scen_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
                              int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                              double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, const double* fscale,
                              const double* fext, int32_t n_fext, int32_t form, int32_t k_steps, void* stream) {
-    return run_scen_forc<double>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                 T_stats, fscale, fext, n_fext, form, k_steps, stream);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {true, n_scen, true, {fscale, fext, n_fext}}, form, k_steps, 0, stream);
 }
 int fiveeq_run_scen_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
                              int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
                              float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext,
                              int32_t n_fext, int32_t form, int32_t k_steps, void* stream) {
-    return run_scen_forc<float>(model, n_members, ld, n_scen, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows,
-                                T_stats, fscale, fext, n_fext, form, k_steps, stream);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {true, n_scen, true, {fscale, fext, n_fext}}, form, k_steps, 0, stream);
 }
 int fiveeq_plan_create_scen_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const double* drive,
                                      int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R,
                                      double* S, double* C_traj, double* T_traj, int32_t n_rows, double* T_stats,
                                      const double* fscale, const double* fext, int32_t n_fext, void** plan_out) {
-    return plan_create<double, false, true, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                                  n_rows, T_stats, plan_out, nullptr, nullptr, n_scen, fscale, fext, n_fext);
+    return plan_create<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {true, n_scen, true, {fscale, fext, n_fext}}, plan_out);
 }
 int fiveeq_plan_create_scen_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, int32_t n_scen, const float* drive,
                                      int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
                                      float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, const float* fscale,
                                      const float* fext, int32_t n_fext, void** plan_out) {
-    return plan_create<float, false, true, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                                 n_rows, T_stats, plan_out, nullptr, nullptr, n_scen, fscale, fext, n_fext);
+    return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {true, n_scen, true, {fscale, fext, n_fext}}, plan_out);
 }
 
 int fiveeq_run_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                         int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
                         double* T_traj, int32_t n_rows, double* T_stats, const double* fscale, const double* fext, int32_t n_fext,
                         const double* obs, double* misfit, int32_t form, int32_t k_steps, void* stream) {
-    return run_forc<double>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                         fscale, fext, n_fext, obs, misfit, form, k_steps, stream);
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {false, 1, true, {fscale, fext, n_fext}, OPTIONAL, {obs, misfit}}, form, k_steps, 0, stream);
 }
 int fiveeq_plan_create_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
                                 int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
                                 double* T_traj, int32_t n_rows, double* T_stats, const double* fscale, const double* fext,
                                 int32_t n_fext, const double* obs, double* misfit, void** plan_out) {
-    return plan_create<double, false, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                                n_rows, T_stats, plan_out, obs, misfit, 1, fscale, fext, n_fext);
+    return plan_create<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {false, 1, true, {fscale, fext, n_fext}, OPTIONAL, {obs, misfit}}, plan_out);
 }
 int fiveeq_run_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                         int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                         float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext, int32_t n_fext,
                         const double* obs, double* misfit, int32_t form, int32_t k_steps, void* stream) {
-    return run_forc<float>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats,
-                         fscale, fext, n_fext, obs, misfit, form, k_steps, stream);
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {false, 1, true, {fscale, fext, n_fext}, OPTIONAL, {obs, misfit}}, form, k_steps, 0, stream);
 }
 int fiveeq_plan_create_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
                                 int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
                                 float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext,
                                 int32_t n_fext, const double* obs, double* misfit, void** plan_out) {
-    return plan_create<float, false, false, true>(model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj,
-                                                n_rows, T_stats, plan_out, obs, misfit, 1, fscale, fext, n_fext);
+    return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {false, 1, true, {fscale, fext, n_fext}, OPTIONAL, {obs, misfit}}, plan_out);
 }
 int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     return fiveeq_layout_supported(n_gas, n_pools) && forcing_layout(layout_code(n_gas, n_pools)) ? 1 : 0;

@@ -416,11 +416,29 @@ class EnsembleEngine(CheckpointMixin):
         t_step = self.n_members * self.n_scenarios * self.bytes_per_member_step("per_step") / HBM_STREAM_BYTES_PER_S
         return 1 if t_step >= 3.0 * LAUNCH_BOUNDARY_S else min(KSTEPS_LAUNCH_BOUND, self.n_steps)
 
+    def mode_refusal(self, mode):
+        """Why this engine does not run in `mode` (one of MODES but 'auto'): the text run() raises, or None.  THE statement of
+        which modes serve which features; where several apply, the first in this order is reported."""
+        forward = ("per_step", "graph", "fused", "ksteps")       # every mode but 'small'
+        rules = (
+            (self.T_hist is not None, ("fused", "per_step"),
+             f"mode {mode!r} does not fill T_hist: use 'fused' or 'per_step' with hist="),
+            (self.compensated, ("fused", "ksteps", "small"),
+             f"mode {mode!r} has no compensated form: the compensation words live in registers, so only the "
+             "time-fused kernel ('fused', 'ksteps') and the small-ensemble kernel ('small', one lane) carry them"),
+            (self.scenario_axis, forward,
+             "mode 'small' has no scenario form: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'"),
+            (self.forcing is not None, forward,
+             "mode 'small' does not carry the forcing scales of forcing=: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'"),
+            (self.observations is not None, forward,
+             "mode 'small' does not carry the misfit of observations=: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'"),
+        )
+        return next((text for has, modes, text in rules if has and mode not in modes), None)
+
     def small_form(self):
-        """Lanes per member mode='small' would run with now (4 or 1); 0 = the small-ensemble kernel does not apply: a run that
-        wants in-loop histograms or the concentration-driven form."""
-        if (not self.small_widest or self.T_hist is not None or self.concentration_driven or self.observations is not None
-                or self.scenario_axis or self.forcing is not None):
+        """Lanes per member mode='small' would run with now (4 or 1); 0 = the small-ensemble kernel does not apply: a feature
+        that mode does not serve (mode_refusal), the concentration-driven form, or a layout or small_lanes without one."""
+        if not self.small_widest or self.concentration_driven or self.mode_refusal("small"):
             return 0
         if self.compensated:                                     # fiveeq_run_small_comp_f32: one member per lane, every layout
             return 1 if self.small_lanes in ("auto", 1) else 0
@@ -495,14 +513,16 @@ class EnsembleEngine(CheckpointMixin):
     def _ptr(self, t, byte_off=0):
         return ctypes.c_void_p(0 if t is None else t.data_ptr() + byte_off)
 
-    def _run_args(self, t_begin, t_end, m0=0, n=None):
-        """C-ABI arguments (model ... T_stats) for members [m0, m0 + n) of this engine's rows (ld = N)."""
+    def _run_args(self, t_begin, t_end, m0=0, n=None, *, n_scen=None, cumE=None):
+        """C-ABI arguments (model ... T_stats) for members [m0, m0 + n) of this engine's rows (ld = N), with the two that some
+        entry points take in between at their places: n_scen (the scenario families, after ld) and cumE (the inverse form,
+        after S)."""
         N, w = self.n_members, self._w
         n = N if n is None else n
-        return (ctypes.byref(self.model), n, N, self._ptr(self.drive), self.n_steps, int(t_begin), int(t_end),
-                self._ptr(self.r, m0 * w), self._ptr(self.q, m0 * w), self._ptr(self.R, m0 * w), self._ptr(self.S, m0 * w),
-                self._ptr(self.C, m0 * w), self._ptr(self.T, m0 * w), self.n_rows,
-                self._ptr(self.T_stats, (m0 // 64) * self.n_steps * 4 * 8))
+        return (ctypes.byref(self.model), n, N, *(() if n_scen is None else (n_scen,)), self._ptr(self.drive), self.n_steps,
+                int(t_begin), int(t_end), self._ptr(self.r, m0 * w), self._ptr(self.q, m0 * w), self._ptr(self.R, m0 * w),
+                self._ptr(self.S, m0 * w), *(() if cumE is None else (cumE,)), self._ptr(self.C, m0 * w),
+                self._ptr(self.T, m0 * w), self.n_rows, self._ptr(self.T_stats, (m0 // 64) * self.n_steps * 4 * 8))
 
     def _fn(self, name):
         return getattr(self.lib, f"fiveeq_{name}_{self._sfx}")
@@ -524,20 +544,20 @@ class EnsembleEngine(CheckpointMixin):
           per_step(t_begin, t_end, m0, n, stream)  one launch per step for members [m0, m0 + n);
           fused(t_begin, t_end, k, stream)         the fused kernel over spans of k steps, all members;
           plan(t_begin, t_end, m0, n, plan_out)    the per-step launches of members [m0, m0 + n) captured into a plan."""
-        def args(t_begin, t_end, m0=0, n=None):
-            a = self._run_args(t_begin, t_end, m0, n)
-            if self.scenario_axis:                              # the scale rows are shared, the tables [S, n_steps, 4]
-                fc = (() if self.forcing is None else
-                      (self._ptr(self.fscale, m0 * self._w), self._ptr(self.fext), self.forcing.n_categories))
-                return (*a[:3], self.n_scenarios, *a[3:], *fc)
-            if self.forcing is not None:                        # (obs, misfit): both NULL without observations=
-                mis = self._obs_args(m0) if self.observations is not None else (None, None)
-                return (*a, self._ptr(self.fscale, m0 * self._w), self._ptr(self.fext), self.forcing.n_categories, *mis)
-            return a if self.observations is None else (*a, *self._obs_args(m0))
+        scen, forc, obs = self.scenario_axis, self.forcing is not None, self.observations is not None
 
-        if self.scenario_axis or self.observations is not None or self.forcing is not None:
-            sfx = (("scen_forc" if self.forcing is not None else "scen") if self.scenario_axis
-                   else ("forc" if self.forcing is not None else "obs"))
+        def args(t_begin, t_end, m0=0, n=None):
+            a = self._run_args(t_begin, t_end, m0, n, n_scen=self.n_scenarios if scen else None)
+            if forc:                                            # with scenarios: the scale rows shared, the tables [S, n_steps, 4]
+                a += (self._ptr(self.fscale, m0 * self._w), self._ptr(self.fext), self.forcing.n_categories)
+            if obs:
+                a += self._obs_args(m0)
+            elif forc and not scen:                             # fiveeq_run_forc's (obs, misfit): both NULL without observations=
+                a += (None, None)
+            return a
+
+        if scen or forc or obs:
+            sfx = "_".join(word for word, on in (("scen", scen), ("forc", forc), ("obs", obs and not forc)) if on)
             run, plan = self._fn("run_" + sfx), self._fn("plan_create_" + sfx)
 
             def per_step(t, t1, m0, n, s):
@@ -564,8 +584,7 @@ class EnsembleEngine(CheckpointMixin):
         return max(self.auto_k_steps() if k_steps is None else int(k_steps), 1)
 
     def _run_inverse(self, t_begin, t_end, stream):
-        a = self._run_args(t_begin, t_end)
-        return self._fn("run_inverse")(*a[:11], self._ptr(self.cumE), *a[11:], self._stream(stream))
+        return self._fn("run_inverse")(*self._run_args(t_begin, t_end, cumE=self._ptr(self.cumE)), self._stream(stream))
 
     def step(self, t, stream=None):
         """One timestep = one kernel launch (asynchronous)."""
@@ -607,19 +626,9 @@ class EnsembleEngine(CheckpointMixin):
         self.last_mode = mode            # what 'auto' resolved to (tests, bench.py's config.mode)
         if mode not in self.MODES:
             raise ValueError(f"unknown mode {mode!r}")
-        if self.T_hist is not None and mode not in ("fused", "per_step"):
-            raise ValueError(f"mode {mode!r} does not fill T_hist: use 'fused' or 'per_step' with hist=")
-        if self.compensated and mode not in ("fused", "ksteps", "small"):
-            raise ValueError(f"mode {mode!r} has no compensated form: the compensation words live in registers, so only the "
-                             "time-fused kernel ('fused', 'ksteps') and the small-ensemble kernel ('small', one lane) carry them")
-        if self.scenario_axis and mode == "small":
-            raise ValueError("mode 'small' has no scenario form: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'")
-        if self.forcing is not None and mode == "small":
-            raise ValueError("mode 'small' does not carry the forcing scales of forcing=: use 'per_step', 'graph', 'fused', "
-                             "'ksteps' or 'auto'")
-        if self.observations is not None and mode == "small":
-            raise ValueError("mode 'small' does not carry the misfit of observations=: use 'per_step', 'graph', 'fused', "
-                             "'ksteps' or 'auto'")
+        refusal = self.mode_refusal(mode)
+        if refusal:
+            raise ValueError(refusal)
         if mode == "small" and not self.small_form():
             raise ValueError("mode 'small' serves runs without in-loop histograms or the inverse form, with 4 lanes per "
                              "member for a lone 4-pool gas only and 8 for pools [4, 1, 1] without collect_stats "
@@ -802,10 +811,12 @@ class EnsembleEngine(CheckpointMixin):
         side = main if self.hist_pass_stream == "same" else concurrent_side_streams(self.lib, main, 1)[0]
         side.wait_stream(main)
         lo_h, hi_h, nb = self.hist_spec
-        if self.compensated:                                     # one launch per chunk either way: k_steps = the chunk
-            fused = lambda *a: self.lib.fiveeq_run_fused_comp_f32(*a[:15], a[6] - a[5], *a[15:])     # noqa: E731
-        else:
-            fused = self._fn("run_fused_bins")
+
+        def fused(t, t1, *ring):                                 # compensated: one launch per chunk either way, k_steps = the chunk
+            a = self._run_args(t, t1)
+            return (self.lib.fiveeq_run_fused_comp_f32(*a, t1 - t, *ring) if self.compensated
+                    else self._fn("run_fused_bins")(*a, *ring))
+
         used = [False, False]
         rc, t, i = _capi.OK, t_begin, 0
         while t < t_end and rc == _capi.OK:
@@ -814,7 +825,7 @@ class EnsembleEngine(CheckpointMixin):
             buf = ring["buf"][slot]
             if used[slot]:
                 main.wait_event(ring["drained"][slot])
-            rc = fused(*self._run_args(t, t1), lo_h, hi_h, nb, self._ptr(buf), S, self._stream(main))
+            rc = fused(t, t1, lo_h, hi_h, nb, self._ptr(buf), S, self._stream(main))
             side.wait_stream(main)
             if rc == _capi.OK:
                 rc = self.lib.fiveeq_hist_bins(t1 - t, N, N, self._ptr(buf[t % S:]), nb, self._ptr(self.T_hist[t:t1]),

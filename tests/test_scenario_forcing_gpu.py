@@ -198,14 +198,14 @@ def test_unit_scales_are_the_plain_scenario_engine_bit_for_bit(kind, dtype):
             assert all(torch.equal(got[k], want[k]) for k in KEYS), (kind, dtype, what, mode, kw)
     for form, k in ((_capi.FORM_FUSED, 0), (_capi.FORM_FUSED, 90), (_capi.FORM_PER_STEP, 0)):
         eng = EnsembleEngine(p, N, E, F_ext=F, dtype=dtype, forcing=none, device="cuda:0")
-        a = eng._run_args(0, n_steps)
-        rc = eng._fn("run_scen_forc")(*a[:3], S, *a[3:], eng._ptr(eng.fscale), None, 0, form, k, eng._stream())
+        a = eng._run_args(0, n_steps, n_scen=S)
+        rc = eng._fn("run_scen_forc")(*a, eng._ptr(eng.fscale), None, 0, form, k, eng._stream())
         _capi.check(eng.lib, rc)
         got = _out(eng)
         assert all(torch.equal(got[k], want[k]) for k in KEYS), (kind, dtype, form, k)
         plan = ctypes.c_void_p()
         eng.reset_state()
-        rc = eng._fn("plan_create_scen_forc")(*a[:3], S, *a[3:], eng._ptr(eng.fscale), None, 0, ctypes.byref(plan))
+        rc = eng._fn("plan_create_scen_forc")(*a, eng._ptr(eng.fscale), None, 0, ctypes.byref(plan))
         _capi.check(eng.lib, rc)
         _capi.check(eng.lib, eng.lib.fiveeq_plan_launch(plan, eng._stream()))
         torch.cuda.synchronize()
@@ -258,9 +258,8 @@ def test_a_member_sub_range_writes_nothing_outside_itself(form, dtype, m0, n):
         getattr(eng, name)[..., ~inside] = SENT
     w0, w1 = m0 // 64, m0 // 64 + (n + 63) // 64                  # the records this call addresses
     eng.T_stats[:] = SENT
-    a = eng._run_args(0, n_steps, m0, n)
-    rc = eng._fn("run_scen_forc")(*a[:3], S, *a[3:], eng._ptr(eng.fscale, m0 * eng._w), eng._ptr(eng.fext), K, form, 0,
-                                  eng._stream())
+    a = eng._run_args(0, n_steps, m0, n, n_scen=S)
+    rc = eng._fn("run_scen_forc")(*a, eng._ptr(eng.fscale, m0 * eng._w), eng._ptr(eng.fext), K, form, 0, eng._stream())
     _capi.check(eng.lib, rc)
     torch.cuda.synchronize()
     for name in KEYS:
