@@ -17,7 +17,11 @@ proportional to the CO2 emissions, volcanic spikes) by its own factors.  The his
 misfit constrains the aerosol scale; the projection is a scenario engine with forcing=ScenarioForcings — one aerosol table per
 scenario, following that scenario's emissions — and the SAME scale rows.
 
-    python example/scenario_projections.py [--members N] [--out FILE] [--forcing]
+--weights keeps EVERY member instead: each is weighted by its likelihood (constrain.importance_weights, integer weights) and the
+summaries are the exact weighted percentiles of gather_summary(weights=); the effective sample size is printed beside the number
+rejection sampling would have accepted.
+
+    python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights]
 """
 import argparse
 import os
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("--members", type=int, default=100_000)
     ap.add_argument("--out", default="scenario_projections.csv")
     ap.add_argument("--forcing", action="store_true", help="per-member forcing scales, per-scenario aerosol tables")
+    ap.add_argument("--weights", action="store_true", help="importance-weight every member instead of rejection sampling")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -64,6 +69,7 @@ def main():
                           device="cuda:0")
     hist.run(0, t_branch, mode="auto")
     keep = constrain.accept_rejection(hist.chi2(), constrain.ACCEPT_SEED, 0, N)
+    how = dict(weights=constrain.importance_weights(hist.chi2())) if a.weights else dict(accepted=keep)
 
     out_steps = [t for t in range(t_branch, n_steps, 10)] + [n_steps - 1]
     torch.cuda.synchronize()
@@ -71,13 +77,16 @@ def main():
                           scenario_names=list(SCENARIOS), forcing=sf, device="cuda:0")
     proj.run(t_branch, n_steps, mode="auto")
     pct = (5.0, 50.0, 95.0)
-    sums = [proj.gather_summary(out_steps, percentiles=pct, scenario=s, accepted=keep) for s in range(proj.n_scenarios)]
+    sums = [proj.gather_summary(out_steps, percentiles=pct, scenario=s, **how) for s in range(proj.n_scenarios)]
     scenario.write_scenario_summary_csv(a.out, proj.scenario_names, run_years[out_steps], sums, pct)
     if sf is not None:
-        aer = p["fx_scale"][0][keep]
-        print(f"aerosol scale: prior 0.3 .. 2.0, accepted members {float(aer.min()):.2f} .. {float(aer.max()):.2f} "
+        aer = p["fx_scale"][0][how["weights"] > 0 if a.weights else keep]
+        print(f"aerosol scale: prior 0.3 .. 2.0, {'weighted' if a.weights else 'accepted'} members {float(aer.min()):.2f} .. {float(aer.max()):.2f} "
               f"(mean {float(aer.mean()):.2f})")
-    print(f"{N} members, {int(keep.sum())} accepted on {obs.n_obs} observed years; branch at {int(run_years[t_branch])}; "
+    used = f"{int(keep.sum())} accepted"
+    if a.weights:
+        used = f"{int(sums[0]['count'][0])} weighted, ess {sums[0]['ess']:.1f} (rejection sampling: {int(keep.sum())} accepted)"
+    print(f"{N} members, {used} on {obs.n_obs} observed years; branch at {int(run_years[t_branch])}; "
           f"projection mode {proj.last_mode}; summary -> {a.out}")
     for name, sm in zip(proj.scenario_names, sums):
         q = sm["percentiles"][-1].tolist()

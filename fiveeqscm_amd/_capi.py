@@ -138,6 +138,12 @@ SIGNATURES = {
     "fiveeq_select_bins_f32": (ctypes.c_int, [_i32, _i64, _i64, _p, _p, _i32, _p, _p, _i64, _p, _p]),
     "fiveeq_select_pick_f64": (ctypes.c_int, [_i32, _i32, _i64, _p, _p, _i32, _p, _p, _p]),
     "fiveeq_select_pick_f32": (ctypes.c_int, [_i32, _i32, _i64, _p, _p, _i32, _p, _p, _p]),
+    "fiveeq_wrow_moments_chunks": (ctypes.c_int64, [_i32, _i64]),
+    **{f"fiveeq_{name}_{sfx}": (ctypes.c_int, args) for sfx in ("f64", "f32") for name, args in (
+        ("wrow_moments", [_i32, _i64, _i64, _p, _p, _p, _p, _p]),
+        ("whist_rows_ranged", [_i32, _i64, _i64, _p, _p, _p, _i32, _p, _p]),
+        ("wselect_bins", [_i32, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p, _i64, _p, _p]),
+        ("wselect_pick", [_i32, _i32, _i64, _p, _p, _p, _i32, _p, _p, _p]))},
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_wide_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_nt_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -150,7 +156,7 @@ _lib = None
 # every source of the library, in the order csrc/Makefile (SRCS) hashes them
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
-    "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_diag.hpp")) + (
+    "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_diag.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

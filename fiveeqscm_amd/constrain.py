@@ -12,12 +12,18 @@ Members are then kept by a threshold on chi2 or by rejection sampling, and the s
     obs = Observations.from_years(run_years, obs_years, T_obs, sigma, baseline=(1850, 1900))
     eng = EnsembleEngine(params, N, E, observations=obs, ...);  eng.run(mode="auto")
     keep = accept_rejection(eng.chi2(), seed, m0, n_total, group)
+
+or every member is kept and weighted by its likelihood (include/fiveeq.h, "WEIGHTED SUMMARY"):
+
+    w = importance_weights(eng.chi2(), group);  eng.gather_summary(steps, weights=w)
 """
 import hashlib
 
 import numpy as np
 
 ACCEPT_SEED = 0x0B5E47ED            # the rejection rule's default key: its uniforms are a dimension of their own LHS
+W_ONE = 1 << 32                     # the integer weight of the best member (importance_weights); the largest weight a member may carry
+MAX_WEIGHTED_MEMBERS = 1 << 31      # fewer members than this over all ranks: every sum of weights then fits int64
 
 
 class Observations:
@@ -161,3 +167,32 @@ def accept_rejection(chi2, seed, m0, n_total, group=None):
     u = params.lhs_rows(int(n_total), [0], int(m0), int(m0) + n, seed=int(seed))[0]
     with np.errstate(invalid="ignore", over="ignore"):
         return u < np.exp(-(np.asarray(chi2, dtype=np.float64) - cmin) / 2.0)
+
+
+def importance_weights(chi2, group=None):
+    """Integer importance weights w_m = floor(W_ONE exp(-(chi2_m - chi2_min) / 2)), W_ONE = 2^32, chi2_min the global minimum
+    (all-reduce MIN over `group`): the likelihood of every member instead of accept_rejection's coin flip on it.  int64 [N],
+    a torch tensor on chi2's device or a NumPy array, like chi2.  The best member gets exactly W_ONE, a NaN score 0.
+    Member-local and evaluated by ONE routine (NumPy's exp on the host, wherever the scores live), so a member gets the same
+    weight for every shard split and world size.  Collective over `group` when torch.distributed runs (the minimum, and the
+    member count: fewer than 2^31 members over all ranks, so that every sum of weights fits int64 — ValueError beyond)."""
+    import torch
+
+    from .distributed import _all_reduce, _dist
+    n = int(chi2.shape[0])
+    if n >= MAX_WEIGHTED_MEMBERS:
+        raise ValueError(f"importance_weights: {n} members; integer weights need fewer than 2^31 over all ranks")
+    cmin = _global_min(chi2, group)
+    dist, _, _, exchange = _dist(group)
+    if exchange:
+        on_gpu = isinstance(chi2, torch.Tensor) and chi2.is_cuda
+        dev = chi2.device if on_gpu else torch.device("cpu" if dist.get_backend(group) == "gloo" else f"cuda:{torch.cuda.current_device()}")
+        total = torch.tensor([n], dtype=torch.int64, device=dev)
+        _all_reduce(dist, group, total, dist.ReduceOp.SUM)
+        if int(total[0]) >= MAX_WEIGHTED_MEMBERS:
+            raise ValueError(f"importance_weights: {int(total[0])} members over all ranks; integer weights need fewer than 2^31")
+    c = chi2.detach().to(torch.float64).cpu().numpy() if isinstance(chi2, torch.Tensor) else np.asarray(chi2, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        like = np.exp(-(c - cmin) / 2.0)                       # <= 1: cmin is the minimum; NaN for a NaN score
+    w = np.floor(np.where(np.isnan(like), 0.0, np.minimum(like, 1.0)) * float(W_ONE)).astype(np.int64)   # exact: a power of two
+    return torch.from_numpy(w).to(chi2.device) if isinstance(chi2, torch.Tensor) else w

@@ -1309,6 +1309,134 @@ int fiveeq_select_bins_f32(int32_t n_rows, int64_t n_members, int64_t ld, const 
                            int32_t n_bins, const uint32_t* binmask, float* cand, int64_t cap, uint64_t* cand_n, void* stream) {
     return select_bins<float>(n_rows, n_members, ld, rows, ranges, n_bins, binmask, cand, cap, cand_n, stream);
 }
+// ---- weighted end-of-run summary passes (kernels 7a-7d) ------------------------------------------------------------
+}  // extern "C"
+namespace {
+bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+// the checks every weighted pass over rows shares: the sizes, the row pointer and the weights
+template <typename T>
+int wsummary_check(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uint64_t* weights) {
+    if (int rc = summary_check(n_rows, n, ld, rows)) return rc;
+    if (n_rows > 0 && !weights) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(rows, sizeof(T)) || misaligned(weights, 8)) return fail(FIVEEQ_E_INVALID, "rows / weights not aligned to their element size");
+    return FIVEEQ_OK;
+}
+int wsummary_bins_check(int32_t n_bins) {
+    if (n_bins < 1 || n_bins > fiveeq::HIST_MAX_BINS)
+        return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, fiveeq::HIST_MAX_BINS);
+    return FIVEEQ_OK;
+}
+template <typename T>
+int wrow_moments(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uint64_t* weights, double* partial, double* moments,
+                 void* stream) {
+    if (int rc = wsummary_check(n_rows, n, ld, rows, weights)) return rc;
+    if (n_rows == 0) return FIVEEQ_OK;
+    if (!partial || !moments) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(partial, 8) || misaligned(moments, 8)) return fail(FIVEEQ_E_INVALID, "partial / moments not 8-byte aligned");
+    const int64_t chunk = summary_chunk(n_rows, n);
+    const int64_t chunks = (n + chunk - 1) / chunk;
+    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    hipLaunchKernelGGL(fiveeq::wrow_moments_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
+                       (hipStream_t)stream, n, ld, chunk, rows, reinterpret_cast<const unsigned long long*>(weights), partial);
+    hipLaunchKernelGGL(fiveeq::wrow_moments_fold_kernel, dim3((unsigned)n_rows), dim3(64), 0, (hipStream_t)stream, chunks,
+                       partial, moments);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+template <typename T>
+int whist_rows(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uint64_t* weights, const double* ranges, int32_t n_bins,
+               uint64_t* hist, void* stream) {
+    if (int rc = wsummary_check(n_rows, n, ld, rows, weights)) return rc;
+    if (int rc = wsummary_bins_check(n_bins)) return rc;
+    if (n_rows == 0) return FIVEEQ_OK;
+    if (!ranges || !hist) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(ranges, 8) || misaligned(hist, 8)) return fail(FIVEEQ_E_INVALID, "ranges / hist not 8-byte aligned");
+    // the chunking of the unweighted ranged histogram (at least 8 members per bin and workgroup), in whole 16-byte loads
+    int64_t chunk = summary_chunk(n_rows, n);
+    const int64_t unit = 4 * FIVEEQ_BLOCK, floor_ = (8LL * n_bins + unit - 1) / unit * unit;
+    if (chunk < floor_) chunk = floor_;
+    const int64_t chunks = (n + chunk - 1) / chunk;
+    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    hipLaunchKernelGGL(fiveeq::whist_rows_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
+                       (hipStream_t)stream, n, ld, chunk, rows, reinterpret_cast<const unsigned long long*>(weights), ranges, n_bins,
+                       reinterpret_cast<unsigned long long*>(hist));
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+template <typename T>
+int wselect_bins(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uint64_t* weights, const double* ranges,
+                 int32_t n_bins, const uint32_t* binmask, T* cand, uint64_t* candw, int64_t cap, uint64_t* cand_n, void* stream) {
+    if (int rc = wsummary_check(n_rows, n, ld, rows, weights)) return rc;
+    if (int rc = wsummary_bins_check(n_bins)) return rc;
+    if (cap < 0) return fail(FIVEEQ_E_INVALID, "cap=%lld must be >= 0", (long long)cap);
+    if (n_rows == 0) return FIVEEQ_OK;
+    if (!ranges || !binmask || !cand_n || (cap > 0 && (!cand || !candw))) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(ranges, 8) || misaligned(binmask, 4) || misaligned(cand, sizeof(T)) || misaligned(candw, 8) || misaligned(cand_n, 8))
+        return fail(FIVEEQ_E_INVALID, "ranges / binmask / cand / candw / cand_n not aligned to their element size");
+    const int64_t chunk = summary_chunk(n_rows, n);
+    const int64_t chunks = (n + chunk - 1) / chunk;
+    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    hipLaunchKernelGGL(fiveeq::wselect_bins_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
+                       (hipStream_t)stream, n, ld, chunk, rows, reinterpret_cast<const unsigned long long*>(weights), ranges, n_bins,
+                       binmask, cand, reinterpret_cast<unsigned long long*>(candw), cap, reinterpret_cast<unsigned long long*>(cand_n));
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+template <typename T>
+int wselect_pick(int32_t n_rows, int32_t n_seg, int64_t width, const T* pool, const uint64_t* poolw, const uint64_t* seg_n,
+                 int32_t n_targets, const int64_t* targets, double* picked, void* stream) {
+    if (n_rows < 0 || n_rows > 65535) return fail(FIVEEQ_E_INVALID, "n_rows=%d outside 0..65535", n_rows);
+    if (n_seg < 1) return fail(FIVEEQ_E_INVALID, "n_seg=%d must be >= 1", n_seg);
+    if (width < 0) return fail(FIVEEQ_E_INVALID, "width=%lld must be >= 0", (long long)width);
+    if (n_targets < 1 || n_targets > 65535) return fail(FIVEEQ_E_INVALID, "n_targets=%d outside 1..65535", n_targets);
+    if (n_rows == 0) return FIVEEQ_OK;
+    if ((width > 0 && (!pool || !poolw)) || !seg_n || !targets || !picked) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(pool, sizeof(T)) || misaligned(poolw, 8) || misaligned(seg_n, 8) || misaligned(targets, 8) || misaligned(picked, 8))
+        return fail(FIVEEQ_E_INVALID, "pool / poolw / seg_n / targets / picked not aligned to their element size");
+    hipLaunchKernelGGL(fiveeq::wselect_pick_kernel<T>, dim3((unsigned)n_rows, (unsigned)n_targets), dim3(fiveeq::PICK_BLOCK), 0,
+                       (hipStream_t)stream, n_seg, width, pool, reinterpret_cast<const unsigned long long*>(poolw),
+                       reinterpret_cast<const unsigned long long*>(seg_n), n_targets, reinterpret_cast<const long long*>(targets),
+                       picked);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int64_t fiveeq_wrow_moments_chunks(int32_t n_rows, int64_t n_members) { return fiveeq_row_moments_chunks(n_rows, n_members); }
+int fiveeq_wrow_moments_f64(int32_t n_rows, int64_t n_members, int64_t ld, const double* rows, const uint64_t* weights,
+                            double* partial, double* moments, void* stream) {
+    return wrow_moments<double>(n_rows, n_members, ld, rows, weights, partial, moments, stream);
+}
+int fiveeq_wrow_moments_f32(int32_t n_rows, int64_t n_members, int64_t ld, const float* rows, const uint64_t* weights,
+                            double* partial, double* moments, void* stream) {
+    return wrow_moments<float>(n_rows, n_members, ld, rows, weights, partial, moments, stream);
+}
+int fiveeq_whist_rows_ranged_f64(int32_t n_rows, int64_t n_members, int64_t ld, const double* rows, const uint64_t* weights,
+                                 const double* ranges, int32_t n_bins, uint64_t* hist, void* stream) {
+    return whist_rows<double>(n_rows, n_members, ld, rows, weights, ranges, n_bins, hist, stream);
+}
+int fiveeq_whist_rows_ranged_f32(int32_t n_rows, int64_t n_members, int64_t ld, const float* rows, const uint64_t* weights,
+                                 const double* ranges, int32_t n_bins, uint64_t* hist, void* stream) {
+    return whist_rows<float>(n_rows, n_members, ld, rows, weights, ranges, n_bins, hist, stream);
+}
+int fiveeq_wselect_bins_f64(int32_t n_rows, int64_t n_members, int64_t ld, const double* rows, const uint64_t* weights,
+                            const double* ranges, int32_t n_bins, const uint32_t* binmask, double* cand, uint64_t* candw,
+                            int64_t cap, uint64_t* cand_n, void* stream) {
+    return wselect_bins<double>(n_rows, n_members, ld, rows, weights, ranges, n_bins, binmask, cand, candw, cap, cand_n, stream);
+}
+int fiveeq_wselect_bins_f32(int32_t n_rows, int64_t n_members, int64_t ld, const float* rows, const uint64_t* weights,
+                            const double* ranges, int32_t n_bins, const uint32_t* binmask, float* cand, uint64_t* candw,
+                            int64_t cap, uint64_t* cand_n, void* stream) {
+    return wselect_bins<float>(n_rows, n_members, ld, rows, weights, ranges, n_bins, binmask, cand, candw, cap, cand_n, stream);
+}
+int fiveeq_wselect_pick_f64(int32_t n_rows, int32_t n_seg, int64_t width, const double* pool, const uint64_t* poolw,
+                            const uint64_t* seg_n, int32_t n_targets, const int64_t* targets, double* picked, void* stream) {
+    return wselect_pick<double>(n_rows, n_seg, width, pool, poolw, seg_n, n_targets, targets, picked, stream);
+}
+int fiveeq_wselect_pick_f32(int32_t n_rows, int32_t n_seg, int64_t width, const float* pool, const uint64_t* poolw,
+                            const uint64_t* seg_n, int32_t n_targets, const int64_t* targets, double* picked, void* stream) {
+    return wselect_pick<float>(n_rows, n_seg, width, pool, poolw, seg_n, n_targets, targets, picked, stream);
+}
 int fiveeq_math_probe_f64(int32_t op, int64_t n, const double* x, double* y, void* stream) {
     return math_probe<double>(op, n, x, y, stream);
 }

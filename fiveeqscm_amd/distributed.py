@@ -457,3 +457,229 @@ def gather_summary(rows, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats
     mom = torch.from_numpy(mom_np)           # a few numbers per row: they stay on the host
     return {"count": mom[:, 0].clone(), "mean": mom[:, 1].clone(), "var": mom[:, 2] / mom[:, 0], "min": mom[:, 3].clone(),
             "max": mom[:, 4].clone(), "percentiles": None if pct_np is None else torch.from_numpy(pct_np)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The WEIGHTED summary: integer importance weights, exact weighted percentiles (include/fiveeq.h, "WEIGHTED SUMMARY").
+# ---------------------------------------------------------------------------------------------------------------------
+WMOM_WORDS = 8                   # 8-byte words per row record of fiveeq_wrow_moments_* (layout: include/fiveeq.h)
+
+
+def weighted_rank(p, weight_sum):
+    """k_p = max(1, ceil(p / 100 * W)): the cumulative weight percentile p must reach, in exact rational arithmetic on the
+    exact value of p (Fraction(p)) — a Python int."""
+    from fractions import Fraction
+    f = Fraction(p)
+    if not 0 <= f <= 100:
+        raise ValueError(f"percentile {p} outside [0, 100]")
+    k = f * int(weight_sum) / 100
+    return max(1, -((-k.numerator) // k.denominator))
+
+
+def _weighted_plan(counts_np, cumw, W, percentiles, skip):
+    """The host step between the weighted histogram and the selection.  counts_np / cumw [K, n_bins] int64: the weight per
+    bin over all ranks and its running sum; W their total; skip [K]: rows that need no selection.  Returns (targets [K, P]
+    int64, binmask [K, ceil(n_bins / 32)] uint32): per row the bins that hold a k_p, marked, and per percentile the
+    cumulative weight to reach AMONG THE CANDIDATES (the members of marked bins, ascending): the weight of the marked bins
+    below its bin plus k_p minus the weight of all bins below it — at least 1; 0 for a skipped row."""
+    K, n_bins = counts_np.shape
+    kp = np.array([weighted_rank(p, W) for p in percentiles], dtype=np.int64)               # [P]
+    bb = np.stack([np.searchsorted(cumw[k], kp, side="left") for k in range(K)]).clip(max=n_bins - 1)      # [K, P]
+    bb[skip] = 0
+    rk = np.arange(K)[:, None]
+    marked = np.zeros((K, n_bins), dtype=bool)
+    marked[rk, bb] = True
+    marked[skip] = False
+    zero = np.zeros((K, 1), dtype=np.int64)
+    below_bin = np.concatenate([zero, cumw[:, :-1]], axis=1)                                # weight in bins < b
+    cand_below = np.concatenate([zero, np.cumsum(counts_np * marked, axis=1)[:, :-1]], axis=1)
+    targets = cand_below[rk, bb] + (kp[None, :] - below_bin[rk, bb])
+    targets[skip] = 0
+    words = (n_bins + 31) // 32
+    bits = np.zeros((K, words * 32), dtype=np.uint8)
+    bits[:, :n_bins] = marked
+    binmask = np.packbits(bits.reshape(K, words, 32), axis=2, bitorder="little").view(np.uint32).reshape(K, words)
+    return targets.astype(np.int64), binmask
+
+
+def _weighted_moments_dev(lib, _capi, ctypes, st, rows, weights, out):
+    """fiveeq_wrow_moments_* of this rank's rows into `out` (a [K, 8] view of 8-byte words on the rows' device)."""
+    K, n = rows.shape
+    if n == 0:                                             # an empty shard: the neutral record
+        rec = np.zeros((K, WMOM_WORDS), dtype=np.int64)
+        rec[:, 3:5] = np.array([np.inf, -np.inf]).view(np.int64)
+        out.copy_(torch.from_numpy(rec))
+        return
+    chunks = int(lib.fiveeq_wrow_moments_chunks(K, n))
+    work = torch.empty(K * chunks * WMOM_WORDS, dtype=torch.float64, device=rows.device)
+    fn = lib.fiveeq_wrow_moments_f64 if rows.dtype == torch.float64 else lib.fiveeq_wrow_moments_f32
+    with _on(rows.device):
+        _capi.check(lib, fn(K, n, rows.stride(0), ctypes.c_void_p(rows.data_ptr()), ctypes.c_void_p(weights.data_ptr()),
+                            ctypes.c_void_p(work.data_ptr()), ctypes.c_void_p(out.data_ptr()), st))
+
+
+def gather_weighted_summary(rows, weights, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, n_bins=None):
+    """rows [K, n_local] ON THE GPU with this rank's integer weights [n_local] (int64 on the same device, 0..2^32 each:
+    constrain.importance_weights, or the caller's own).  Collective over `group`.  The definition is include/fiveeq.h's
+    "WEIGHTED SUMMARY": percentile p = the smallest x whose cumulative weight reaches k_p = weighted_rank(p, W) — exact, and
+    the same bits for every world size and shard split, because every sum that decides it is an integer sum.
+    Returns on every rank a dict: count (members with w > 0), mean, var, std, min, max ([K] fp64 host tensors), weight_sum
+    (Python int), ess (float), method; on rank `dst` also 'percentiles' [K, P] fp64 (None elsewhere).
+    Flow: moments pass -> all-gather and merge of the records -> weighted histogram between the global extrema -> all-reduce
+    SUM (int64) -> the host marks the bins holding each k_p -> selection of (value, weight) pairs -> gather to `dst` -> pick.
+    A rank whose members all weigh 0, or that has none, takes part in every collective."""
+    if rows.dim() != 2:
+        raise ValueError("rows: want [K, n_local]")
+    if rows.shape[1] > 0 and (rows.stride(1) != 1 or rows.stride(0) < rows.shape[1]):      # rows of a wider buffer are read in place
+        rows = rows.contiguous()
+    _need_device_rows(rows)
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or weights.device != rows.device \
+            or tuple(weights.shape) != (rows.shape[1],):
+        raise ValueError(f"weights: want an int64 tensor of shape [{rows.shape[1]}] on {rows.device}")
+    weights = weights.contiguous()
+    P = len(percentiles)
+    if P < 1:
+        raise ValueError("no percentiles asked for")
+    for p in percentiles:
+        weighted_rank(p, 1)                               # the range check, before anything is launched
+    dist, rank, world, exchange = _dist(group)
+    lib, _capi, ctypes, st = _lib_and_stream(rows)
+    n_bins = SELECT_BINS if n_bins is None else int(n_bins)
+    K, n_local = rows.shape
+    dev, ld, w_el = rows.device, rows.stride(0), rows.element_size()
+    sfx = "f64" if rows.dtype == torch.float64 else "f32"
+    ptr = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)      # noqa: E731
+    host_wire = exchange and dist.get_backend(group) == "gloo"
+
+    # one device buffer for what comes back after the histogram: weight per bin [K, n_bins] int64, then the records [K, 8]
+    head = torch.zeros(K * n_bins + K * WMOM_WORDS, dtype=torch.int64, device=dev)
+    counts = head[:K * n_bins].view(K, n_bins)
+    rec_dev = head[K * n_bins:].view(K, WMOM_WORDS)
+
+    # ---- pass 1: moments, and with them the extrema over the members that carry weight ------------------------------------
+    _weighted_moments_dev(lib, _capi, ctypes, st, rows, weights, rec_dev)
+    parts = None
+    if exchange:
+        mine = np.concatenate([rec_dev.cpu().numpy().reshape(-1), np.array([n_local], dtype=np.int64)])
+        got = _all_gather_np(dist, group, world, mine, dev)                                 # [world, K * 8 + 1]
+        parts, n_each = got[:, :-1].reshape(world, K, WMOM_WORDS), got[:, -1]
+        f = parts[:, :, :5].view(np.float64)
+        ranges = torch.from_numpy(np.ascontiguousarray(np.stack([f[:, :, 3].min(axis=0), f[:, :, 4].max(axis=0)], axis=1))).to(dev)
+    else:
+        ranges = rec_dev[:, 3:5].view(torch.float64).contiguous()      # one rank: the extrema never leave the device here
+        n_each = np.array([n_local], dtype=np.int64)
+
+    # ---- pass 2: weight per bin between the global extrema; integer sums, so the all-reduce is exact -----------------------
+    if n_local > 0:
+        with _on(dev):
+            _capi.check(lib, getattr(lib, f"fiveeq_whist_rows_ranged_{sfx}")(K, n_local, ld, ptr(rows), ptr(weights), ptr(ranges),
+                                                                             n_bins, ptr(counts), st))
+    if exchange:
+        _all_reduce(dist, group, counts, dist.ReduceOp.SUM)
+    head_np = head.cpu().numpy()
+    counts_np = head_np[:K * n_bins].reshape(K, n_bins)
+    if parts is None:
+        parts = head_np[K * n_bins:].reshape(1, K, WMOM_WORDS)
+    if stats is not None:
+        stats["bytes_to_root"], stats["allreduce_bytes"] = 0, (counts.numel() * 8 if exchange else 0)
+        stats["bytes_to_root_per_rank"] = [0] * world
+
+    # ---- host: the merged record (rank order: the same bits every run), the integer ranks ----------------------------------
+    n_total = int(n_each.sum())
+    if n_total >= (1 << 31):
+        raise ValueError(f"weighted summary: {n_total} members over all ranks; integer weights need fewer than 2^31")
+    flags = np.bitwise_or.reduce(parts[:, :, 6], axis=0)                                    # [K]
+    if (flags & 2).any():
+        raise ValueError("weights: values outside [0, 2^32]")
+    W = sum(int(v) for v in parts[:, 0, 7])                                                 # the weights are shared by the rows
+    if W == 0:
+        raise ValueError("weighted summary: the weights of all members on all ranks sum to 0")
+    n_pos = parts[:, 0, 5].astype(np.int64)                                                 # members with w > 0, per rank
+    fp = parts[:, :, :5].view(np.float64)
+    s1, s2, sw2 = np.zeros(K), np.zeros(K), 0.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(parts.shape[0]):
+            s1, s2, sw2 = s1 + fp[r, :, 0], s2 + fp[r, :, 1], sw2 + float(fp[r, 0, 2])
+        lo_np, hi_np = fp[:, :, 3].min(axis=0), fp[:, :, 4].max(axis=0)
+        mean = s1 / float(W)
+        var = np.maximum(s2 / float(W) - mean * mean, 0.0)                                  # (NaN stays NaN)
+    nan_row = (flags & 1) != 0
+    mean, var = np.where(nan_row, np.nan, mean), np.where(nan_row, np.nan, var)
+    out = {"count": torch.full((K,), float(n_pos.sum()), dtype=torch.float64), "mean": torch.from_numpy(mean),
+           "var": torch.from_numpy(var), "std": torch.from_numpy(np.sqrt(var)), "min": torch.from_numpy(lo_np.copy()),
+           "max": torch.from_numpy(hi_np.copy()), "weight_sum": W, "ess": float(W) * float(W) / sw2,
+           "method": "weighted_inverted_cdf", "percentiles": None}
+
+    cumw = np.cumsum(counts_np, axis=1)                                                     # int64: W < 2^63
+    flat = ~(hi_np > lo_np)                               # one value carries all the weight: it IS every percentile
+    skip = nan_row | flat
+    if not np.array_equal(cumw[~nan_row, -1], np.full(int((~nan_row).sum()), W, dtype=np.int64)):
+        k = int(np.argwhere((cumw[:, -1] != W) & ~nan_row)[0, 0])
+        raise RuntimeError(f"weighted summary: row {k}'s histogram weighs {int(cumw[k, -1])} where the weights sum to {W}")
+    targets, binmask = _weighted_plan(counts_np, cumw, W, percentiles, skip)
+    words = binmask.shape[1]
+
+    # ---- ONE upload: targets [K, P] int64, then the bin masks [K, words] uint32 -------------------------------------------
+    up = torch.from_numpy(np.concatenate([targets.astype(np.int64).reshape(-1).view(np.uint8), binmask.reshape(-1).view(np.uint8)])).to(dev)
+    o_mask = K * P * 8
+
+    # ---- pass 3: selection; pass 4: pick.  The weighted histogram does not count members, so a row's candidate buffer is
+    # sized by this rank's members with w > 0 (most members of a tightly constrained ensemble weigh 0); rows go in blocks
+    # while rows x that bound (the largest over the ranks: every rank blocks alike) exceeds SELECT_CAND_BYTES ------------------
+    select = getattr(lib, f"fiveeq_wselect_bins_{sfx}")
+    pick = getattr(lib, f"fiveeq_wselect_pick_{sfx}")
+    cap = max(1, int(n_pos[rank if exchange else 0]))
+    block = max(1, min(K, SELECT_CAND_BYTES // (max(1, int(n_pos.max())) * (w_el + 8))))
+    picked = np.full((K, P), np.nan)
+    for k0 in range(0, K, block):
+        k1 = min(K, k0 + block)
+        Kb = k1 - k0
+        tail = torch.zeros(Kb + Kb * P, dtype=torch.int64, device=dev)                       # [cand_n Kb (uint64) | picked Kb * P (fp64)]
+        cand = torch.empty((Kb, cap), dtype=rows.dtype, device=dev)
+        candw = torch.empty((Kb, cap), dtype=torch.int64, device=dev)
+        t_off, m_off = k0 * P * 8, o_mask + k0 * words * 4
+        with _on(dev):
+            if n_local > 0:
+                _capi.check(lib, select(Kb, n_local, ld, ptr(rows, k0 * ld * w_el), ptr(weights), ptr(ranges, k0 * 16), n_bins,
+                                        ptr(up, m_off), ptr(cand), ptr(candw), cap, ptr(tail), st))
+            if not exchange:
+                _capi.check(lib, pick(Kb, 1, cap, ptr(cand), ptr(candw), ptr(tail), P, ptr(up, t_off), ptr(tail, Kb * 8), st))
+        if exchange:
+            cand_n = tail[:Kb].cpu().numpy()
+            all_n = _all_gather_np(dist, group, world, cand_n, dev)                         # [world, Kb]
+            width = max(int(all_n.max()), 1)
+
+            def padded(t):
+                t = t[:, :min(width, cap)]
+                if t.shape[1] < width:
+                    t = torch.cat([t, t.new_zeros((Kb, width - t.shape[1]))], dim=1)
+                return t.cpu().contiguous() if host_wire else t.contiguous()
+
+            send_x, send_w = padded(cand), padded(candw)
+            recv_x = [torch.empty_like(send_x) for _ in range(world)] if rank == dst else None
+            recv_w = [torch.empty_like(send_w) for _ in range(world)] if rank == dst else None
+            dist.gather(send_x, recv_x, dst=dst, group=group)
+            dist.gather(send_w, recv_w, dst=dst, group=group)
+            if stats is not None:
+                per_rank = [0 if r == dst else int(all_n[r].sum()) * (w_el + 8) for r in range(world)]
+                stats["bytes_to_root"] += sum(per_rank)
+                stats["bytes_to_root_per_rank"] = [a + b for a, b in zip(stats["bytes_to_root_per_rank"], per_rank)]
+            if rank != dst:
+                continue
+            pool = torch.stack(recv_x, dim=1).to(dev).contiguous()                          # [Kb, world, width]
+            poolw = torch.stack(recv_w, dim=1).to(dev).contiguous()
+            seg_n = torch.from_numpy(np.ascontiguousarray(all_n.T)).to(dev)                 # [Kb, world]
+            with _on(dev):
+                _capi.check(lib, pick(Kb, world, width, ptr(pool), ptr(poolw), ptr(seg_n), P, ptr(up, t_off), ptr(tail, Kb * 8), st))
+        picked[k0:k1] = tail.cpu().numpy()[Kb:].view(np.float64).reshape(Kb, P)
+    if exchange and rank != dst:
+        return out
+    with np.errstate(invalid="ignore"):
+        good = skip[:, None] | ((picked >= lo_np[:, None]) & (picked <= hi_np[:, None]))
+    if not good.all():
+        k, j = [int(v) for v in np.argwhere(~good)[0]]
+        raise RuntimeError(f"weighted selection lost its percentile (row {k}, p={percentiles[j]}): target {int(targets[k, j])}, "
+                           f"picked {picked[k, j]}")
+    pct = np.where(nan_row[:, None], np.nan, np.where(flat[:, None], np.broadcast_to(lo_np[:, None], (K, P)), picked))
+    out["percentiles"] = torch.from_numpy(pct)
+    return out

@@ -913,7 +913,7 @@ class EnsembleEngine(CheckpointMixin):
         return chi2_from_misfit(self.misfit, self.observations.P)
 
     def gather_summary(self, steps, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, gas=None, accepted=None,
-                       scenario=None):
+                       scenario=None, weights=None):
         """End-of-run summary of T — or, with `gas` = a gas index, of that gas's concentration C — at the stored `steps` over
         ALL members of all ranks (collective over `group`; see distributed.gather_summary): merged moments on every rank,
         exact percentiles on rank `dst`.  With collect_stats the moments of T come from the records the kernels wrote while
@@ -922,8 +922,15 @@ class EnsembleEngine(CheckpointMixin):
         members of all ranks only — the selected rows are compacted on the device and go through the same passes (the
         in-kernel moment records cover every member, so they are not used); `count` is the global number accepted.  A rank
         with no accepted member still takes part in every collective.  scenario: the scenario summarised (required with
-        the scenario axis; `accepted` masks the members of that scenario)."""
-        from .distributed import gather_summary
+        the scenario axis; `accepted` masks the members of that scenario).
+        weights: integer weights of this shard's members, int64 [N] on the engine's device, 0..2^32 each
+        (constrain.importance_weights): the summary is then the WEIGHTED one over all members of all ranks
+        (distributed.gather_weighted_summary; include/fiveeq.h, "WEIGHTED SUMMARY") — exact weighted percentiles by the
+        inverted CDF, and the result also holds weight_sum, ess, std and method = "weighted_inverted_cdf"; `count` is the
+        global number of members with a positive weight.  Not together with `accepted`."""
+        from .distributed import gather_summary, gather_weighted_summary
+        if weights is not None and accepted is not None:
+            raise ValueError("gather_summary: weights= and accepted= exclude each other (a weight of 0 drops a member)")
         sc = self._scen(scenario)
         stored = self.T if gas is None else self.C
         if stored is None or self.concentration_driven and gas is not None:
@@ -940,6 +947,11 @@ class EnsembleEngine(CheckpointMixin):
         T_rows = self.T if sc is None else self.T[sc]
         C_rows = None if self.C is None else (self.C if sc is None else self.C[sc])
         rows = T_rows[picked] if gas is None else C_rows[picked, int(gas)]
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or tuple(weights.shape) != (self.n_members,) \
+                    or weights.device != rows.device:
+                raise ValueError(f"weights: want an int64 tensor of shape [{self.n_members}] on {rows.device}")
+            return gather_weighted_summary(rows, weights, percentiles, dst=dst, group=group, stats=stats)
         if accepted is not None:
             mask = torch.as_tensor(accepted, device=self.device)
             if mask.dtype != torch.bool or tuple(mask.shape) != (self.n_members,):

@@ -543,6 +543,60 @@ int fiveeq_select_pick_f64(int32_t n_rows, int32_t n_seg, int64_t width, const d
 int fiveeq_select_pick_f32(int32_t n_rows, int32_t n_seg, int64_t width, const float *pool, const uint64_t *seg_n,
                            int32_t n_targets, const int64_t *ranks, double *picked, void *stream);
 
+/* new — WEIGHTED SUMMARY: the passes above over (value, weight) pairs, for importance-weighted ensembles (DESIGN.md section
+ * 3.11; host side: fiveeqscm_amd/distributed.py gather_weighted_summary, weights: fiveeqscm_amd/constrain.py
+ * importance_weights).  Additive: no symbol above changes.
+ *
+ * DEFINITION.  A row x of n members over all ranks carries INTEGER weights w, 0 <= w_i <= 2^32, n < 2^31, W = sum w < 2^63.
+ * Integer sums are exact and order-independent, so atomics, shard splits and all-reduces cannot change a bit of what follows.
+ *   percentile p   the smallest x_i with  sum_{x_j <= x_i} w_j >= k_p  (the inverted CDF), where
+ *                  k_p = max(1, ceil(p / 100 * W)) with p taken as the EXACT rational value of the number handed in and the
+ *                  product evaluated in integer / rational arithmetic on the host: no floating-point product decides a rank.
+ *   weight 0       the member does not exist, whatever its value (NaN and +-inf included).
+ *   NaN, w > 0     the row's percentiles, mean and std are NaN (min / max ignore the NaN).
+ *   W == 0         over all ranks: an error (ValueError on every rank).
+ *   moments        mean = sum w x / W, var = sum w x^2 / W - mean^2, min / max over the members with w > 0; the three sums
+ *                  (and sum w^2) accumulated in fp64 in a fixed order per rank, merged over the ranks in rank order.
+ *   ess            W^2 / sum w^2 (fp64);  count = the members with w > 0;  weight_sum = W, exact.
+ * weights dev [n_members] uint64, shared by the rows; rows dev [n_rows][ld] as above.  Pointers must be aligned to their
+ * element size; rows, ld * sizeof(element) and weights aligned to 16 bytes get 16-byte loads.
+ *
+ * (1w) moments dev [n_rows][8], words of 8 bytes: 0 sum w x, 1 sum w x^2, 2 sum w^2, 3 min, 4 max (fp64; members with
+ *      w > 0) | 5 count of w > 0, 6 flags (bit 0: a NaN value with w > 0; bit 1: a weight above 2^32 — the caller's
+ *      error), 7 sum w (uint64 bit patterns).  partial dev [n_rows][K][8] is workspace, K = fiveeq_wrow_moments_chunks. */
+int64_t fiveeq_wrow_moments_chunks(int32_t n_rows, int64_t n_members);
+int fiveeq_wrow_moments_f64(int32_t n_rows, int64_t n_members, int64_t ld, const double *rows, const uint64_t *weights,
+                            double *partial, double *moments, void *stream);
+int fiveeq_wrow_moments_f32(int32_t n_rows, int64_t n_members, int64_t ld, const float *rows, const uint64_t *weights,
+                            double *partial, double *moments, void *stream);
+/* (2w) hist[row][b] += the WEIGHT of the members with w > 0 in bin b — THE BIN RULE above with ranges dev [n_rows][2] fp64 =
+ *      (lo, hi) read from device memory (the extrema of (1w)); hi <= lo: bin 0; a NaN has no bin.  hist dev
+ *      [n_rows][n_bins] uint64, ACCUMULATED INTO; 1 <= n_bins <= 4096. */
+int fiveeq_whist_rows_ranged_f64(int32_t n_rows, int64_t n_members, int64_t ld, const double *rows, const uint64_t *weights,
+                                 const double *ranges, int32_t n_bins, uint64_t *hist, void *stream);
+int fiveeq_whist_rows_ranged_f32(int32_t n_rows, int64_t n_members, int64_t ld, const float *rows, const uint64_t *weights,
+                                 const double *ranges, int32_t n_bins, uint64_t *hist, void *stream);
+/* (3w) selection: the (value, weight) pairs of the members with w > 0 in the bins binmask marks (as in (3)) are appended to
+ *      cand / candw dev [n_rows][cap] (same place in both, any order within a row); cand_n dev [n_rows] uint64, ACCUMULATED
+ *      INTO, counts the candidates FOUND; those beyond cap are counted but not stored.  The weighted histogram does not
+ *      count members: size cap from the count of w > 0 of (1w). */
+int fiveeq_wselect_bins_f64(int32_t n_rows, int64_t n_members, int64_t ld, const double *rows, const uint64_t *weights,
+                            const double *ranges, int32_t n_bins, const uint32_t *binmask,
+                            double *cand, uint64_t *candw, int64_t cap, uint64_t *cand_n, void *stream);
+int fiveeq_wselect_bins_f32(int32_t n_rows, int64_t n_members, int64_t ld, const float *rows, const uint64_t *weights,
+                            const double *ranges, int32_t n_bins, const uint32_t *binmask,
+                            float *cand, uint64_t *candw, int64_t cap, uint64_t *cand_n, void *stream);
+/* (4w) pick: picked[row][q] = the smallest candidate x whose cumulative candidate weight (candidates <= x) reaches
+ *      targets[row][q] >= 1 — host bookkeeping on the histogram of (2w): the weight of the marked bins below the
+ *      percentile's bin, plus k_p minus the weight of all bins below it.  One workgroup per (row, target), radix selection
+ *      on sums of weight, no sort, any number of candidates (the whole row when every member fell into one bin).  pool /
+ *      poolw dev [n_rows][n_seg][width], seg_n dev [n_rows][n_seg] as in (4).  picked dev [n_rows][n_targets] fp64; NaN
+ *      where the target is below 1 or above the candidates' weight. */
+int fiveeq_wselect_pick_f64(int32_t n_rows, int32_t n_seg, int64_t width, const double *pool, const uint64_t *poolw,
+                            const uint64_t *seg_n, int32_t n_targets, const int64_t *targets, double *picked, void *stream);
+int fiveeq_wselect_pick_f32(int32_t n_rows, int32_t n_seg, int64_t width, const float *pool, const uint64_t *poolw,
+                            const uint64_t *seg_n, int32_t n_targets, const int64_t *targets, double *picked, void *stream);
+
 /* STREAMED HISTOGRAMS through a ring of BIN INDICES (round 3).  fiveeq_run_fused_bins_* is
  * fiveeq_run_fused_* (same arguments, same results, C_traj / T_traj / T_stats as there) that ALSO writes, for every step t of
  * the span and every member m, the histogram bin of T(t, m) — the rule of fiveeq_hist_rows_* with (hist_lo, hist_hi, n_bins),
