@@ -21,7 +21,12 @@ scenario, following that scenario's emissions — and the SAME scale rows.
 summaries are the exact weighted percentiles of gather_summary(weights=); the effective sample size is printed beside the number
 rejection sampling would have accepted.
 
-    python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights]
+--resample M shrinks the ensemble before it is projected (include/fiveeq.h, "RESAMPLING"): after the history the members
+are resampled into M equal-weight ones — by their importance weights with --weights, else from the accepted members (each
+drawn floor or ceil of M / accepted times) — and only
+those are branched into the scenarios (EnsembleEngine.resampled) and summarised, with the plain unweighted gather_summary.
+
+    python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights] [--resample M]
 """
 import argparse
 import os
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("--out", default="scenario_projections.csv")
     ap.add_argument("--forcing", action="store_true", help="per-member forcing scales, per-scenario aerosol tables")
     ap.add_argument("--weights", action="store_true", help="importance-weight every member instead of rejection sampling")
+    ap.add_argument("--resample", type=int, default=0, metavar="M", help="project only M resampled equal-weight members")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -73,18 +79,24 @@ def main():
 
     out_steps = [t for t in range(t_branch, n_steps, 10)] + [n_steps - 1]
     torch.cuda.synchronize()
-    proj = EnsembleEngine(p, N, E_s, R0=hist.R, S0=hist.S, output_steps=out_steps, store_concentrations=False,
+    p_proj, n_proj, R0, S0 = p, N, hist.R, hist.S
+    if a.resample:                                            # a dense equal-weight posterior: only it is stepped from here on
+        plan = constrain.resample(how["weights"], a.resample, seed=constrain.ACCEPT_SEED) if a.weights \
+            else constrain.resample(keep, a.resample, seed=constrain.ACCEPT_SEED)
+        (p_proj, R0, S0), n_proj, how = hist.resampled(plan), plan.n_members, {}
+        print(f"resampled {N} members into {n_proj} equal-weight ones ({int(torch.unique(plan.src).numel())} distinct sources)")
+    proj = EnsembleEngine(p_proj, n_proj, E_s, R0=R0, S0=S0, output_steps=out_steps, store_concentrations=False,
                           scenario_names=list(SCENARIOS), forcing=sf, device="cuda:0")
     proj.run(t_branch, n_steps, mode="auto")
     pct = (5.0, 50.0, 95.0)
     sums = [proj.gather_summary(out_steps, percentiles=pct, scenario=s, **how) for s in range(proj.n_scenarios)]
     scenario.write_scenario_summary_csv(a.out, proj.scenario_names, run_years[out_steps], sums, pct)
     if sf is not None:
-        aer = p["fx_scale"][0][how["weights"] > 0 if a.weights else keep]
-        print(f"aerosol scale: prior 0.3 .. 2.0, {'weighted' if a.weights else 'accepted'} members {float(aer.min()):.2f} .. {float(aer.max()):.2f} "
+        aer = p_proj["fx_scale"][0] if a.resample else p["fx_scale"][0][how["weights"] > 0 if a.weights else keep]
+        print(f"aerosol scale: prior 0.3 .. 2.0, {'resampled' if a.resample else 'weighted' if a.weights else 'accepted'} members {float(aer.min()):.2f} .. {float(aer.max()):.2f} "
               f"(mean {float(aer.mean()):.2f})")
     used = f"{int(keep.sum())} accepted"
-    if a.weights:
+    if a.weights and not a.resample:
         used = f"{int(sums[0]['count'][0])} weighted, ess {sums[0]['ess']:.1f} (rejection sampling: {int(keep.sum())} accepted)"
     print(f"{N} members, {used} on {obs.n_obs} observed years; branch at {int(run_years[t_branch])}; "
           f"projection mode {proj.last_mode}; summary -> {a.out}")

@@ -17,6 +17,7 @@ N_BOX = 2
 DRIVE_STRIDE = 8
 LHS_MAX_TOTAL = 1 << 28
 MAX_FEXT = 4
+WSCAN_TILE = 1024                   # weights per workgroup of fiveeq_wscan (fiveeq_resample.hpp)
 
 OK = 0
 E_INVALID = -1
@@ -144,6 +145,11 @@ SIGNATURES = {
         ("whist_rows_ranged", [_i32, _i64, _i64, _p, _p, _p, _i32, _p, _p]),
         ("wselect_bins", [_i32, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p, _i64, _p, _p]),
         ("wselect_pick", [_i32, _i32, _i64, _p, _p, _p, _i32, _p, _p, _p]))},
+    "fiveeq_wscan_chunks": (ctypes.c_int64, [_i64]),
+    "fiveeq_wscan": (ctypes.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "fiveeq_resample_pick": (ctypes.c_int, [_i64, _p, ctypes.c_uint64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    "fiveeq_gather_rows_f64": (ctypes.c_int, [_i32, _i64, _i64, _p, _i64, _p, _p, _p]),
+    "fiveeq_gather_rows_f32": (ctypes.c_int, [_i32, _i64, _i64, _p, _i64, _p, _p, _p]),
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_wide_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_nt_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -156,7 +162,8 @@ _lib = None
 # every source of the library, in the order csrc/Makefile (SRCS) hashes them
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
-    "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_diag.hpp")) + (
+    "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
+    "fiveeq_diag.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

@@ -196,3 +196,198 @@ def importance_weights(chi2, group=None):
         like = np.exp(-(c - cmin) / 2.0)                       # <= 1: cmin is the minimum; NaN for a NaN score
     w = np.floor(np.where(np.isnan(like), 0.0, np.minimum(like, 1.0)) * float(W_ONE)).astype(np.int64)   # exact: a power of two
     return torch.from_numpy(w).to(chi2.device) if isinstance(chi2, torch.Tensor) else w
+
+
+# ---- resampling: (members, integer weights) -> a dense equal-weight posterior (include/fiveeq.h, "RESAMPLING") ------------
+MAX_RESAMPLED = (1 << 31) - 1       # outputs over all ranks: int32 source indices, and j s + b < 2^62 on the device
+_PER_MEMBER_KEYS = ("r0", "rC", "rT", "q", "f_scale", "fx_scale")
+
+
+def resample_offset(seed, n_out, weight_sum):
+    """The offset rho of the resampling positions: 0 without a seed, else the first 8 bytes (little-endian) of
+    sha256("<seed>:<M>:<W>") modulo W — a pure function of its arguments, computed on the host."""
+    if seed is None:
+        return 0
+    digest = hashlib.sha256(f"{seed}:{int(n_out)}:{int(weight_sum)}".encode()).digest()
+    return int.from_bytes(digest[:8], "little") % int(weight_sum)
+
+
+def resample_plan(local_sums, rank, n_out, rho):
+    """The rank arithmetic of the resampling, in Python integers (no process group needed): local_sums = every rank's weight
+    sum in rank order, rank = this one, n_out = M outputs over all ranks, 0 <= rho < W.  Returns a dict
+      W, C_lo   the weight of all ranks, and of the ranks before this one
+      j0, j1    this rank's outputs [j0, j1): j(C) = min(M, max(0, ceil((C M - rho) / W))) at C_lo and C_lo + its own sum
+      q, a, s, b   W = q M + s, rho = a M + b: p_j = j q + a + (j s + b) div M stays inside int64 on the device."""
+    sums = [int(v) for v in local_sums]
+    M, rho, rank = int(n_out), int(rho), int(rank)
+    if not 0 <= rank < len(sums):
+        raise ValueError(f"rank {rank} outside 0..{len(sums) - 1}")
+    if any(v < 0 for v in sums):
+        raise ValueError("resample: negative weight sums")
+    W = sum(sums)
+    if W == 0:
+        raise ValueError("resample: the weights of all members on all ranks sum to 0")
+    if W >= 1 << 63:
+        raise ValueError("resample: the weights sum to 2^63 or more")
+    if not 1 <= M <= MAX_RESAMPLED:
+        raise ValueError(f"resample: n_out={M} outside 1..2^31-1")
+    if not 0 <= rho < W:
+        raise ValueError(f"resample: offset {rho} outside [0, W={W})")
+    C_lo = sum(sums[:rank])
+    first = lambda C: min(M, max(0, -((rho - C * M) // W)))          # noqa: E731   ceil((C M - rho) / W)
+    q, s = divmod(W, M)
+    a, b = divmod(rho, M)
+    return {"W": W, "C_lo": C_lo, "j0": first(C_lo), "j1": first(C_lo + sums[rank]), "q": q, "a": a, "s": s, "b": b}
+
+
+class Resample:
+    """What constrain.resample returns: this rank's share of the M equal-weight outputs.
+      n_out       M, the outputs over all ranks          n_members   this rank's outputs — differs per rank and CAN BE 0
+      j0          the global index of this rank's first output        n_source    this rank's source members
+      weight_sum  W over all ranks (Python int)          offset      rho
+      src         int32 [n_members] on the weights' device (a NumPy array for host weights): output k is a copy of this
+                  rank's member src[k]; non-decreasing."""
+
+    def __init__(self, n_out, j0, weight_sum, offset, src, n_source):
+        self.n_out, self.j0, self.weight_sum, self.offset, self.src, self.n_source = n_out, j0, weight_sum, offset, src, n_source
+        self.n_members = int(src.shape[0])
+
+    def gather(self, rows):
+        """rows [..., N] (N = this rank's source members; contiguous, fp64 or fp32) -> a NEW tensor [..., n_members] with
+        out[..., k] = rows[..., src[k]]; the leading axes are flattened into the row count of one fiveeq_gather_rows_* launch.
+        Rows on the GPU need device weights behind this plan and go through the HIP kernel; host rows (NumPy arrays or CPU
+        tensors) are gathered by its NumPy twin."""
+        import torch
+
+        from . import _resample_host
+        if tuple(rows.shape[-1:]) != (self.n_source,):
+            raise ValueError(f"gather: rows of shape {tuple(rows.shape)}, want [..., {self.n_source}]")
+        on_gpu = isinstance(rows, torch.Tensor) and rows.is_cuda
+        if not on_gpu:
+            src = self.src.cpu().numpy() if isinstance(self.src, torch.Tensor) else self.src
+            if isinstance(rows, torch.Tensor):
+                return torch.from_numpy(_resample_host.gather_rows(rows.detach().numpy(), src))
+            return _resample_host.gather_rows(rows, src)
+        if not isinstance(self.src, torch.Tensor) or self.src.device != rows.device:
+            raise ValueError(f"gather: rows on {rows.device}, but the plan's indices are not (resample device weights there)")
+        if rows.dtype not in (torch.float64, torch.float32) or not rows.is_contiguous():
+            raise ValueError("gather: want contiguous fp64 or fp32 rows")
+        import ctypes
+
+        from . import _capi
+        lib = _capi.load()
+        M, N = self.n_members, self.n_source
+        out = torch.empty(tuple(rows.shape[:-1]) + (M,), dtype=rows.dtype, device=rows.device)
+        n_rows = rows.numel() // N
+        if M and n_rows:
+            fn = lib.fiveeq_gather_rows_f64 if rows.dtype == torch.float64 else lib.fiveeq_gather_rows_f32
+            p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+            with torch.cuda.device(rows.device):
+                st = ctypes.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+                _capi.check(lib, fn(n_rows, M, N, p(rows), M, p(out), p(self.src), st))
+        return out
+
+    def gather_params(self, params):
+        """A copy of the parameter dict in which the per-member entries r0, rC, rT, q, f_scale and fx_scale — those of shape
+        [K, N] — are gathered to [K, n_members]; everything else is shared by reference."""
+        out = dict(params)
+        for key in _PER_MEMBER_KEYS:
+            v = params.get(key)
+            if v is not None and getattr(v, "ndim", 0) == 2 and v.shape[-1] == self.n_source:
+                out[key] = self.gather(v if getattr(v, "is_contiguous", lambda: True)() else v.contiguous())
+        return out
+
+
+def resample(weights, n_out=None, seed=None, group=None):
+    """Systematic resampling in integer arithmetic (include/fiveeq.h, "RESAMPLING"): this shard's members with their integer
+    weights -> a Resample naming, for each of this rank's outputs, the member it copies.  The M = n_out outputs over all ranks
+    carry equal weight; member m is drawn floor or ceil of M w_m / W times, a member of weight 0 never; the ranks' outputs in
+    rank order are the same list for every world size and shard split.
+    weights: int64 [N] (importance_weights; 0..2^32 each, n_out required), or a boolean mask (0 / 1 weights).  A mask WITHOUT
+    n_out is compacted: M = the number accepted over all ranks and the offset is 0 WHATEVER `seed` says, so the outputs are
+    exactly the accepted members, each once, in order; a mask with n_out is resampled like any other weights.  A CUDA tensor takes the HIP kernels (scan, pick) and gives device indices; a NumPy array their NumPy twins.
+    seed: None puts the first position at 0; else the offset is resample_offset(seed, M, W).
+    Collective over `group` when torch.distributed runs: ONE all-gather of (local weight sum, member count, range flag).
+    ValueError on EVERY rank — also when only one rank's argument is at fault, since the local findings travel in the flag —
+    for an array of another type or shape, weights outside [0, 2^32], 2^31 or more members, a total weight of 0, and n_out
+    missing or outside 1..2^31-1.  Outputs are not rebalanced: a rank owns the outputs its members' cumulative weight covers, so n_members
+    differs per rank and can be 0 (shards of one Latin hypercube carry near-equal posterior mass)."""
+    import torch
+
+    from . import _resample_host
+    from .distributed import _all_gather_np, _dist
+    on_torch = isinstance(weights, torch.Tensor)
+    w = weights if on_torch else np.asarray(weights)
+    is_mask = w.dtype == (torch.bool if on_torch else np.dtype(bool))
+    # what only THIS rank may see wrong travels in the gathered flag word, so that every rank raises and none is left waiting
+    # in the collective: bit 2 the array's type or shape, bit 3 the shard's size, bit 4 n_out
+    flag = 0
+    if w.ndim != 1 or not (is_mask or w.dtype == (torch.int64 if on_torch else np.dtype(np.int64))):
+        flag |= 4
+    n = int(w.shape[0]) if w.ndim >= 1 else 0
+    if n >= MAX_WEIGHTED_MEMBERS:
+        flag |= 8
+    if (n_out is None and not is_mask) or (n_out is not None and not 1 <= int(n_out) <= MAX_RESAMPLED):
+        flag |= 16
+    on_gpu = on_torch and w.is_cuda
+    cum = None
+    local_sum = 0
+    if flag:
+        pass                                                   # nothing is scanned: the refusal follows the exchange
+    elif on_gpu and n:
+        import ctypes
+
+        from . import _capi
+        lib = _capi.load()
+        w = w.to(torch.int64).contiguous()
+        cum = torch.empty(n + 1, dtype=torch.int64, device=w.device)       # the scan, and behind it the flag word
+        work = torch.empty(int(lib.fiveeq_wscan_chunks(n)), dtype=torch.int64, device=w.device)
+        p = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + 8 * off)      # noqa: E731
+        with torch.cuda.device(w.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
+            _capi.check(lib, lib.fiveeq_wscan(n, p(w), p(work), p(cum), p(cum, n), st))
+        local_sum, flag = (int(v) for v in cum[n - 1:].cpu())                # bit 1: a weight outside [0, 2^32]
+        cum = cum[:n]
+    elif n:
+        host_w = w.detach().numpy() if on_torch else w
+        cum, flag = _resample_host.wscan(host_w.astype(np.int64))
+        local_sum = int(cum[-1].astype(np.int64))
+
+    dist, rank, world, exchange = _dist(group)
+    mine = np.array([local_sum, n, flag], dtype=np.int64)
+    if exchange:
+        dev = w.device if on_gpu else torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) != "gloo" else None
+        got = _all_gather_np(dist, group, world, mine, dev)
+    else:
+        got = mine[None]
+    flags = int(np.bitwise_or.reduce(got[:, 2]))
+    if flags & 4:
+        raise ValueError("resample: weights must be an int64 [N] array of integer weights or a boolean [N] mask")
+    if flags & 16:
+        raise ValueError(f"resample: n_out={n_out} must be given for integer weights (a mask defaults to the number accepted) "
+                         "and lie in 1..2^31-1")
+    if flags & 2:
+        raise ValueError("resample: weights outside [0, 2^32]")
+    if flags & 8 or int(got[:, 1].sum()) >= MAX_WEIGHTED_MEMBERS:
+        raise ValueError(f"resample: {int(got[:, 1].sum())} members over all ranks; integer weights need fewer than 2^31")
+    sums = [int(v) for v in got[:, 0]]
+    W = sum(sums)
+    if W == 0:
+        raise ValueError("resample: the weights of all members on all ranks sum to 0")
+    M = W if n_out is None else int(n_out)
+    if not 1 <= M <= MAX_RESAMPLED:
+        raise ValueError(f"resample: n_out={M} outside 1..2^31-1")
+    rho = 0 if is_mask and n_out is None else resample_offset(seed, M, W)
+    plan = resample_plan(sums, rank if exchange else 0, M, rho)
+    j0, mine_out = plan["j0"], plan["j1"] - plan["j0"]
+    args = (plan["C_lo"], M, plan["q"], plan["a"], plan["s"], plan["b"], j0, mine_out)
+    if on_gpu:
+        src = torch.empty(mine_out, dtype=torch.int32, device=w.device)
+        if mine_out:
+            with torch.cuda.device(w.device):
+                _capi.check(lib, lib.fiveeq_resample_pick(n, p(cum), *args, p(src), st))
+    else:
+        src = _resample_host.pick(cum, *args) if mine_out else np.zeros(0, dtype=np.int32)
+        if on_torch:
+            src = torch.from_numpy(src)
+    return Resample(M, j0, W, rho, src, n)

@@ -1437,6 +1437,80 @@ int fiveeq_wselect_pick_f32(int32_t n_rows, int32_t n_seg, int64_t width, const 
                             const uint64_t* seg_n, int32_t n_targets, const int64_t* targets, double* picked, void* stream) {
     return wselect_pick<float>(n_rows, n_seg, width, pool, poolw, seg_n, n_targets, targets, picked, stream);
 }
+// ---- resampling a weighted ensemble (kernels 8a-8c) ------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+constexpr int64_t RESAMPLE_MAX = 0x7fffffffLL;              // members of a shard and outputs: int32 indices
+template <typename T>
+int gather_rows(int32_t n_rows, int64_t n_out, int64_t ld_in, const T* rows_in, int64_t ld_out, T* rows_out, const int32_t* src,
+                void* stream) {
+    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
+    if (n_out < 0 || n_out > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_out=%lld outside 0..2^31-1", (long long)n_out);
+    if (ld_in < 1 || ld_in > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "ld_in=%lld outside 1..2^31-1", (long long)ld_in);
+    if (ld_out < n_out) return fail(FIVEEQ_E_INVALID, "ld_out=%lld < n_out=%lld", (long long)ld_out, (long long)n_out);
+    if (n_rows == 0 || n_out == 0) return FIVEEQ_OK;
+    if (!rows_in || !rows_out || !src) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(rows_in, sizeof(T)) || misaligned(rows_out, sizeof(T)) || misaligned(src, 4))
+        return fail(FIVEEQ_E_INVALID, "rows_in / rows_out / src not aligned to their element size");
+    hipLaunchKernelGGL(fiveeq::gather_rows_kernel<T>, dim3((unsigned)((n_out + FIVEEQ_BLOCK - 1) / FIVEEQ_BLOCK)), dim3(FIVEEQ_BLOCK), 0,
+                       (hipStream_t)stream, n_rows, n_out, ld_in, rows_in, ld_out, rows_out, src);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int64_t fiveeq_wscan_chunks(int64_t n_members) {
+    if (n_members < 1) return 0;
+    return (n_members + fiveeq::WSCAN_TILE - 1) / fiveeq::WSCAN_TILE * fiveeq::WSCAN_WORDS;
+}
+int fiveeq_wscan(int64_t n_members, const uint64_t* weights, uint64_t* partial, uint64_t* cum, uint64_t* flags, void* stream) {
+    if (n_members < 1 || n_members > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n_members);
+    if (!weights || !partial || !cum || !flags) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(weights, 8) || misaligned(partial, 8) || misaligned(cum, 8) || misaligned(flags, 8))
+        return fail(FIVEEQ_E_INVALID, "weights / partial / cum / flags not 8-byte aligned");
+    const int64_t tiles = (n_members + fiveeq::WSCAN_TILE - 1) / fiveeq::WSCAN_TILE;
+    const unsigned long long* w = reinterpret_cast<const unsigned long long*>(weights);
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(partial);
+    hipLaunchKernelGGL(fiveeq::wscan_sums_kernel, dim3((unsigned)tiles), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_members, w, part);
+    hipLaunchKernelGGL(fiveeq::wscan_spine_kernel, dim3(1), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, tiles, part,
+                       reinterpret_cast<unsigned long long*>(flags));
+    hipLaunchKernelGGL(fiveeq::wscan_tiles_kernel, dim3((unsigned)tiles), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_members, w, part,
+                       reinterpret_cast<unsigned long long*>(cum));
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+int fiveeq_resample_pick(int64_t n_members, const uint64_t* cum, uint64_t c_lo, int64_t M, int64_t q, int64_t a, int64_t s, int64_t b,
+                         int64_t j0, int64_t n_out, int32_t* src, void* stream) {
+    if (n_members < 1 || n_members > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n_members);
+    if (M < 1 || M > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "M=%lld outside 1..2^31-1", (long long)M);
+    if (q < 0 || a < 0) return fail(FIVEEQ_E_INVALID, "q=%lld, a=%lld must be >= 0", (long long)q, (long long)a);
+    if (s < 0 || s >= M || b < 0 || b >= M)
+        return fail(FIVEEQ_E_INVALID, "s=%lld, b=%lld outside [0, M=%lld)", (long long)s, (long long)b, (long long)M);
+    if (j0 < 0 || n_out < 0 || j0 > M || n_out > M - j0)
+        return fail(FIVEEQ_E_INVALID, "j0=%lld, n_out=%lld: not a range of the M=%lld outputs", (long long)j0, (long long)n_out, (long long)M);
+    // the last position, (M - 1) q + a + ((M - 1) s + b) div M, must stay below 2^63 (it is below W for a plan of the host)
+    const unsigned __int128 last = (unsigned __int128)(M - 1) * (unsigned __int128)q + (unsigned __int128)a +
+                                   (unsigned __int128)(((M - 1) * s + b) / M);
+    if (last > (unsigned __int128)INT64_MAX)
+        return fail(FIVEEQ_E_INVALID, "q=%lld, a=%lld: positions beyond 2^63", (long long)q, (long long)a);
+    if (n_out == 0) return FIVEEQ_OK;
+    if (!cum || !src) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
+    if (misaligned(cum, 8) || misaligned(src, 4)) return fail(FIVEEQ_E_INVALID, "cum / src not aligned to their element size");
+    hipLaunchKernelGGL(fiveeq::resample_pick_kernel, dim3((unsigned)((n_out + fiveeq::PICK_SRC_BLOCK - 1) / fiveeq::PICK_SRC_BLOCK)),
+                       dim3(fiveeq::PICK_SRC_BLOCK), 0, (hipStream_t)stream, n_members, reinterpret_cast<const unsigned long long*>(cum),
+                       (unsigned long long)c_lo, (unsigned long long)M, (unsigned long long)q, (unsigned long long)a,
+                       (unsigned long long)s, (unsigned long long)b, j0, n_out, src);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+int fiveeq_gather_rows_f64(int32_t n_rows, int64_t n_out, int64_t ld_in, const double* rows_in, int64_t ld_out, double* rows_out,
+                           const int32_t* src, void* stream) {
+    return gather_rows<double>(n_rows, n_out, ld_in, rows_in, ld_out, rows_out, src, stream);
+}
+int fiveeq_gather_rows_f32(int32_t n_rows, int64_t n_out, int64_t ld_in, const float* rows_in, int64_t ld_out, float* rows_out,
+                           const int32_t* src, void* stream) {
+    return gather_rows<float>(n_rows, n_out, ld_in, rows_in, ld_out, rows_out, src, stream);
+}
 int fiveeq_math_probe_f64(int32_t op, int64_t n, const double* x, double* y, void* stream) {
     return math_probe<double>(op, n, x, y, stream);
 }

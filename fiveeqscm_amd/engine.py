@@ -962,6 +962,34 @@ class EnsembleEngine(CheckpointMixin):
             sums = torch.cat([self.stats_sums(int(t), int(t) + 1, scenario=sc) for t in steps])[:, 1:5].contiguous()
         return gather_summary(rows, percentiles, dst=dst, group=group, stats=stats, local_sums=sums)
 
+    def resampled(self, plan):
+        """(params, R0, S0) of the equal-weight ensemble `plan` (a constrain.Resample of this shard's members, from device
+        weights) draws from this engine: ready for EnsembleEngine(params, plan.n_members, emissions, R0=R0, S0=S0, ...), which
+        then continues, for each of its members k, the run of this engine's member plan.src[k] bit for bit.
+        params is this engine's parameter dict with the per-member entries r0, rC, rT, q (and f_scale, fx_scale with
+        forcing=) replaced by gathers of the engine's own device rows, in its dtype; R0 / S0 are gathers of the state R / S
+        as it stands (the scenario axis is kept: [S, SP, M] / [S, 2, M]).  One fiveeq_gather_rows_* launch each.
+        plan.n_members differs per rank and can be 0 — an engine needs at least one member.  Concentration-driven engines are
+        refused: their cumulative emissions (cumE) are per-member state that would have to travel too."""
+        if self.concentration_driven:
+            raise ValueError("resampled: a concentration-driven engine carries cumE, which the resampled triple does not hold")
+        if not isinstance(plan.src, torch.Tensor) or plan.src.device != self.device or plan.n_source != self.n_members:
+            raise ValueError(f"resampled: want a plan over this engine's {self.n_members} members with indices on {self.device}")
+        if self._ps_unjoined:
+            self.join()
+        G = self.n_gas
+        with torch.cuda.device(self.device):
+            r = plan.gather(self.r)                                  # [3 G, M], gas-major (r0, rC, rT)
+            params = dict(self.params)
+            params["r0"], params["rC"], params["rT"] = r[0::3], r[1::3], r[2::3]
+            params["q"] = plan.gather(self.q)
+            if self.fscale is not None:
+                fs = plan.gather(self.fscale)                        # [G + K, M], gas rows first
+                params["f_scale"] = fs[:G]
+                if fs.shape[0] > G:
+                    params["fx_scale"] = fs[G:]
+            return params, plan.gather(self.R), plan.gather(self.S)
+
     def T_histogram(self, lo, hi, n_bins=4096, rows=None, out=None, stream=None, scenario=None):
         """Fixed-bin histograms of the stored T rows on the device: int64 tensor [n_rows, n_bins]
         (bin b counts lo + b w <= T < lo + (b+1) w; outliers land in the edge bins).  `out` lets

@@ -597,6 +597,49 @@ int fiveeq_wselect_pick_f64(int32_t n_rows, int32_t n_seg, int64_t width, const 
 int fiveeq_wselect_pick_f32(int32_t n_rows, int32_t n_seg, int64_t width, const float *pool, const uint64_t *poolw,
                             const uint64_t *seg_n, int32_t n_targets, const int64_t *targets, double *picked, void *stream);
 
+/* new — RESAMPLING: (members, integer weights) -> a dense, equal-weight ensemble of M members, for branching, checkpointing
+ * and unweighted tools (host side: fiveeqscm_amd/constrain.py resample, EnsembleEngine.resampled).
+ * Additive: no symbol above changes, FIVEEQ_ABI_VERSION stays 13.
+ *
+ * DEFINITION.  Systematic resampling in integer arithmetic, so that shard splits, atomics and the world size cannot change
+ * a bit.  Members m = 0 .. n-1 over all ranks in rank order; integer weights 0 <= w_m <= 2^32, n < 2^31, 1 <= W = sum w < 2^63
+ * (the contract of WEIGHTED SUMMARY); c_m = sum_{i <= m} w_i the inclusive cumulative weight.  M outputs, 1 <= M < 2^31, and an
+ * integer offset rho, 0 <= rho < W.  Output j (0 <= j < M) sits at the position
+ *     p_j = floor((j W + rho) / M)
+ * and is a copy of source(j) = the first m with c_m > p_j.  Hence a member of weight 0 is never drawn, member m is drawn
+ * floor(M w_m / W) or ceil(M w_m / W) times, and the outputs come in non-decreasing source order.
+ *   overflow-free  the host splits W = q M + s and rho = a M + b (0 <= s, b < M; arbitrary-precision integers); then
+ *                  p_j = j q + a + (j s + b) div M, with j s + b < 2^62 and j q + a <= p_j < W: 64-bit on the device.
+ *   shards         a rank whose members own the cumulative range [C_lo, C_hi) owns the outputs [j(C_lo), j(C_hi)),
+ *                  j(C) = min(M, max(0, ceil((C M - rho) / W))) on the host.  The ranks' output shards concatenated in rank
+ *                  order are the global list — for every world size and split, with empty shards and shards of zero mass.
+ *   masks          weights in {0, 1}, M = W, rho = 0: p_j = j, and the output is the accepted members, each once, in order.
+ *   offset         rho = (the first 8 bytes, little-endian, of sha256("<seed>:<M>:<W>")) mod W; no seed: rho = 0.
+ *
+ * (1r) scan: cum[m] = w_0 + ... + w_m (modulo 2^64), m < n_members; cum[n_members - 1] is the shard's weight sum.  flags dev
+ *      [1] is WRITTEN: bit 1 (the convention of (1w)) when a weight is above 2^32 — the caller's error, and cum then means
+ *      nothing.  Reduce, then scan: tile sums, a scan of the tile sums by one workgroup, tile scans — three launches ordered
+ *      by the stream; no kernel waits on another workgroup.  Integer sums: the same bits in any order.  partial dev
+ *      [fiveeq_wscan_chunks(n_members)] uint64 is workspace (two words per tile of 1024 weights).  weights / cum aligned to 16
+ *      bytes get 16-byte accesses.  1 <= n_members < 2^31. */
+int64_t fiveeq_wscan_chunks(int64_t n_members);
+int fiveeq_wscan(int64_t n_members, const uint64_t *weights, uint64_t *partial, uint64_t *cum, uint64_t *flags, void *stream);
+/* (2r) pick: src[k] = the first LOCAL member m with cum[m] > p_{j0 + k} - c_lo, k < n_out: the upper bound of the position in
+ *      this shard's scan, c_lo the weight of the shards before it.  (M, q, a, s, b) as above; [j0, j0 + n_out) must be the
+ *      shard's own outputs (a position outside the shard's range is clamped to its first / last member: src always holds
+ *      valid indices).  src dev [n_out] int32.  1 <= M < 2^31, 0 <= s, b < M, q, a, j0, n_out >= 0, j0 + n_out <= M, and
+ *      the last position below 2^63.  n_out == 0: nothing to do. */
+int fiveeq_resample_pick(int64_t n_members, const uint64_t *cum, uint64_t c_lo, int64_t M, int64_t q, int64_t a, int64_t s,
+                         int64_t b, int64_t j0, int64_t n_out, int32_t *src, void *stream);
+/* (3r) gather: rows_out[r][k] = rows_in[r][src[k]], r < n_rows, k < n_out, all rows in one launch.  rows_in dev
+ *      [n_rows][ld_in], rows_out dev [n_rows][ld_out], ld_out >= n_out; nothing is written beyond column n_out.  0 <= src[k] <
+ *      ld_in (a column whose index is not is left unwritten and nothing is read for it).  n_out == 0 or n_rows == 0:
+ *      nothing to do. */
+int fiveeq_gather_rows_f64(int32_t n_rows, int64_t n_out, int64_t ld_in, const double *rows_in, int64_t ld_out, double *rows_out,
+                           const int32_t *src, void *stream);
+int fiveeq_gather_rows_f32(int32_t n_rows, int64_t n_out, int64_t ld_in, const float *rows_in, int64_t ld_out, float *rows_out,
+                           const int32_t *src, void *stream);
+
 /* STREAMED HISTOGRAMS through a ring of BIN INDICES (round 3).  fiveeq_run_fused_bins_* is
  * fiveeq_run_fused_* (same arguments, same results, C_traj / T_traj / T_stats as there) that ALSO writes, for every step t of
  * the span and every member m, the histogram bin of T(t, m) — the rule of fiveeq_hist_rows_* with (hist_lo, hist_hi, n_bins),

@@ -6,6 +6,7 @@ instruction mix (VALU by type, SALU, LDS, global).  Runs in the CPU container (c
     python tools/kernel_isa_stats.py --digest [FILE.s]    # every kernel: mangled name and sha256 of its assembly
     python tools/kernel_isa_stats.py --compare-forc PARENT.s [NEW.s]   # profiles/r08/forcing_isa.txt
     python tools/kernel_isa_stats.py --compare-scen-forc PARENT.s [NEW.s]   # profiles/r09/scenario_forcing_isa.txt
+    python tools/kernel_isa_stats.py --compare-digest PARENT.s [NEW.s]      # profiles/r12/resample_isa.txt
 
 --compare-forc: PARENT.s is the assembly of the commit before the FORC template parameter (step_kernel / fused_kernel gained
 it as their last one, default false), NEW.s the tree's (compiled when not given).  Every kernel of PARENT.s is looked up in
@@ -15,6 +16,9 @@ occupancy and instruction count; then every FORC = true instantiation is listed 
 --compare-scen-forc: the same for the commit before step_scen_kernel gained FORC as its last template parameter (default
 false; fused_kernel's parameter list did not change, it gained the SCEN + FORC instantiations): every kernel of PARENT.s
 against NEW.s, then every new instantiation beside its SCEN, FORC = false counterpart.
+
+--compare-digest: every kernel of PARENT.s against its namesake in NEW.s by the digest below (the same machine code or not),
+then the facts of the kernels only NEW.s has.
 
 --digest hashes each kernel from its `<name>:` label through `.end_amdhsa_kernel` (code and kernel descriptor), with
 comments and blank lines dropped and the function-numbered labels (.LBB<n>_, .Lfunc_end<n>) made position-independent:
@@ -44,12 +48,38 @@ def compile_asm():
         return open(os.path.join(tmp, "fiveeq_capi-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
 
 
-def digest(asm):
+def digests(asm):
+    """{mangled kernel name: sha256 of its normalised assembly}"""
+    out = {}
     for m in KERNEL.finditer(asm):
         lines = (line.split(";")[0].rstrip() for line in m.group(0).splitlines())
         text = "\n".join(line for line in lines if line.strip())
         text = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", re.sub(r"\.LBB\d+_", ".LBB_", text))
-        print(m.group(1), hashlib.sha256(text.encode()).hexdigest())
+        out[m.group(1)] = hashlib.sha256(text.encode()).hexdigest()
+    return out
+
+
+def digest(asm):
+    for name, h in digests(asm).items():
+        print(name, h)
+
+
+def compare_digest(parent_asm, new_asm):
+    old, new = digests(parent_asm), digests(new_asm)
+    missing = [n for n in old if n not in new]
+    changed = [n for n in old if n in new and new[n] != old[n]]
+    for n in missing:
+        print("MISSING", n)
+    for n in changed:
+        print("CHANGED", n)
+    added = facts(new_asm)
+    known = set(facts(parent_asm))
+    fresh = sorted(n for n in added if n not in known)
+    print(f"kernels of the parent build compared by digest: {len(old)}; missing: {len(missing)}; changed: {len(changed)}; "
+          f"new: {len(fresh)}\n")
+    for name in fresh:
+        print(name)
+        print("   vgpr %3d sgpr %3d lds %5d scratch %d waves/SIMD %d instr %d" % added[name])
 
 
 def facts(asm):
@@ -118,6 +148,9 @@ def compare_scen_forc(parent_asm, new_asm):
 def main():
     if sys.argv[1:2] == ["--compare-scen-forc"]:
         compare_scen_forc(open(sys.argv[2]).read(), open(sys.argv[3]).read() if len(sys.argv) > 3 else compile_asm())
+        return
+    if sys.argv[1:2] == ["--compare-digest"]:
+        compare_digest(open(sys.argv[2]).read(), open(sys.argv[3]).read() if len(sys.argv) > 3 else compile_asm())
         return
     if sys.argv[1:2] == ["--digest"]:
         digest(open(sys.argv[2]).read() if len(sys.argv) > 2 else compile_asm())
