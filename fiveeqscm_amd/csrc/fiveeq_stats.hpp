@@ -42,8 +42,11 @@ __device__ __forceinline__ void wave_stats(const bool active, const T Tn, double
     const double v = (double)Tn;
     const double s1 = wave_reduce_to_lane63<OpAdd>(active ? v : 0.0, 0.0);
     const double s2 = wave_reduce_to_lane63<OpAdd>(active ? v * v : 0.0, 0.0);
-    const double mn = wave_reduce_to_lane63<OpMin>(active ? v : inf, inf);
-    const double mx = wave_reduce_to_lane63<OpMax>(active ? v : -inf, -inf);
+    // fmin / fmax drop a NaN operand but keep NaN when BOTH are: a NaN member enters the extrema as the neutral element, so a
+    // record whose members are all NaN has min = +inf, max = -inf here as in wave_stats_flush() below
+    const bool ordered = active && v == v;
+    const double mn = wave_reduce_to_lane63<OpMin>(ordered ? v : inf, inf);
+    const double mx = wave_reduce_to_lane63<OpMax>(ordered ? v : -inf, -inf);
     if ((threadIdx.x & 63) == 63) {
         out[0] = s1;
         out[1] = s2;
@@ -70,8 +73,9 @@ __device__ __forceinline__ void wave_stats(const bool a0, const bool a1, const f
     const double x = (double)Tn.x, y = (double)Tn.y;
     const double s1 = wave_reduce_to_lanes_31_63<OpAdd>((a0 ? x : 0.0) + (a1 ? y : 0.0), 0.0);
     const double s2 = wave_reduce_to_lanes_31_63<OpAdd>((a0 ? x * x : 0.0) + (a1 ? y * y : 0.0), 0.0);
-    const double mn = wave_reduce_to_lanes_31_63<OpMin>(fmin(a0 ? x : inf, a1 ? y : inf), inf);
-    const double mx = wave_reduce_to_lanes_31_63<OpMax>(fmax(a0 ? x : -inf, a1 ? y : -inf), -inf);
+    const bool o0 = a0 && x == x, o1 = a1 && y == y;      // (a NaN member: the neutral element, as above)
+    const double mn = wave_reduce_to_lanes_31_63<OpMin>(fmin(o0 ? x : inf, o1 ? y : inf), inf);
+    const double mx = wave_reduce_to_lanes_31_63<OpMax>(fmax(o0 ? x : -inf, o1 ? y : -inf), -inf);
     const int lane = threadIdx.x & 63;
     double* const out = lane == 31 ? out_lo : (lane == 63 ? out_hi : nullptr);
     if (out != nullptr) {
@@ -97,6 +101,9 @@ constexpr int STAT_ROW = 65;
 // min / max as ONE instruction.  fmin()/fmax() on a value the compiler cannot prove canonical get a v_max(x, x) in front
 // (sNaN quieting) — 56 of them in the fused kernel's statistics flush; the values here come out of the model's FMAs.  A NaN
 // operand is ignored by v_min / v_max like by fmin / fmax (IEEE mode), so the record of a wave with a NaN member is the same.
+// The folds START from the neutral element (+inf / -inf), like the partial-wave path below: a record whose members are ALL NaN
+// then has min = +inf, max = -inf by every route (started from the first value it had NaN extrema; wave_stats() above feeds
+// its ladder the neutral element for a NaN member to the same end).
 __device__ __forceinline__ float fe_min_raw(float a, float b) {
     float r;
     asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -127,7 +134,7 @@ __device__ __forceinline__ void wave_stats_flush(const T* tile /* [STAT_STEPS][S
     const double inf = __builtin_inf();
     double s1 = 0.0, s2 = 0.0, mn, mx;
     if (n_valid >= 64) {                                   // a full wave (all but the ensemble's last): no per-value tests, and
-        T lo_v = tile[j * STAT_ROW + p * 8], hi_v = lo_v;  // min / max in the values' own precision (exact), converted once
+        T lo_v = (T)inf, hi_v = (T)-inf;                   // min / max in the values' own precision (exact), converted once
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const T t = tile[j * STAT_ROW + p * 8 + i];
@@ -182,8 +189,7 @@ __device__ __forceinline__ void wave_stats_flush(const float2v* tile /* [STAT_ST
     const double inf = __builtin_inf();
     double s1 = 0.0, s2 = 0.0, mn, mx;
     if (n_valid >= 128) {                                  // a full wave: same order of the sums as below, no per-value tests
-        const float2v first = tile[j * STAT_ROW + p * 8];
-        float lo_v = first.x, hi_v = first.x;
+        float lo_v = (float)inf, hi_v = (float)-inf;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float2v v2 = tile[j * STAT_ROW + p * 8 + i];
