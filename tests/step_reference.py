@@ -21,6 +21,7 @@ units of eps(dtype) x scale:
     T     sum_j of the S_j scales
     E     k (sum_i |R_i| (1 + |em1_i|) + |C*| + |C0|) / |alpha sum_i a_i tau_i c em1_i|      (the inverse step's diagnosed rate:
           the terms of its numerator over its denominator, and alpha's own conditioning k)
+    cum   |cum| + dt x the scale of E                                (the inverse step's cumulative emissions, cum + E dt)
 
 the forcing terms being |F_ext| and per gas |f1 ln(C/C0)| (dropped by the guard), |f2 (C - C0)|, |f3 sqrt C| (0 under the
 guard) and |f3 sqrt C0|.  The S and T scales depend on eps through the last term and are returned as a pair (A, B):
@@ -126,12 +127,13 @@ def step_forward(mc, r, q, R, S, cum, E, F_ext):
 def step_inverse(mc, r, q, R, S, cum, C_target, F_ext):
     """The concentration-driven counterpart: C_target [G] (the concentration at the END of the step) in, the diagnosed
     emission rate E [G] out, with its scale sE; cum [G] is the member's own cumulative emissions before the step.
-    Also R, S, C (the concentration reached), T, iirf and their scales, as step_forward()."""
+    Also R, S, C (the concentration reached), T, iirf and their scales, as step_forward(), and the member's cumulative
+    emissions AFTER the step, cum [G] = cum_g + E_g dt, with their scale scum = |cum_g| + dt sE_g."""
     with mp.workdps(DPS):
         S = [M(v) for v in S]
         T_old = S[0] + S[1]
         F, F_abs, dF = M(F_ext), abs(M(F_ext)), M(0)
-        out = dict(R=[], C=[], E=[], iirf=[], sR=[], sC=[], sE=[])
+        out = dict(R=[], C=[], E=[], iirf=[], sR=[], sC=[], sE=[], cum=[], scum=[])
         for g, gs in enumerate(mc["gases"]):
             Rg = [M(v) for v in R[g]]
             iirf, alpha, k = _alpha(gs, mc["iirf_max"], [M(v) for v in r[g]], Rg, M(cum[g]), T_old)
@@ -148,6 +150,7 @@ def step_inverse(mc, r, q, R, S, cum, C_target, F_ext):
             F, F_abs, dF = F + Fg, F_abs + Fg_abs, dF + dFdC * sC
             out["R"].append(Rn), out["C"].append(C), out["E"].append(Eg), out["iirf"].append(iirf)
             out["sC"].append(sC), out["sE"].append(sE)
+            out["cum"].append(M(cum[g]) + Eg * mc["dt"]), out["scum"].append(abs(M(cum[g])) + mc["dt"] * sE)
             out["sR"].append([abs(Ri) + k * abs(di) for Ri, di in zip(Rg, dR)])
         Sn, A, B = _thermal(mc, [M(v) for v in q], S, F, F_abs, dF)
         out.update(S=Sn, T=Sn[0] + Sn[1], sS=(A, B), sT=(A[0] + A[1], B[0] + B[1]))

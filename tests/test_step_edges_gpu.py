@@ -9,7 +9,7 @@ nobody excluded:  |got - ref| <= 8 max(K_ORACLE, 1) eps(dtype) scale  (K_ORACLE:
 device primitives' 2 ulp (2.5 for the fp32 log) against libm's <= 1, the host's pre-rounded folded constants, the FMAs'
 other association), never more than the project's own tolerances.
 
-MEASURED (MI355X): at most 1.3 eps x scale in every form, class and output — the table is in the docstring of
+MEASURED (MI355X): at most 1.5 eps x scale in every form, class and output — the table is in the docstring of
 test_one_step_against_the_50_digit_reference.
 
 ONE ARITHMETIC: every other launch shape and feature carrier gives the bits of the matching accuracy run, for that step and
@@ -92,6 +92,7 @@ ACCURACY_FORMS = {
     "f32 per-step, packing off": dict(prec="f32", kw=dict(dtype=torch.float32), mode="per_step", packing=0),
     "f32 compensated fused": dict(prec="f32", kw=dict(dtype=torch.float32, compensated=True), mode="fused", packing=1),
     "f64 inverse per-step": dict(prec="f64", kw=dict(dtype=torch.float64), mode="per_step", packing=1, inverse=True),
+    "f32 inverse per-step": dict(prec="f32", kw=dict(dtype=torch.float32), mode="per_step", packing=1, inverse=True),
 }
 
 
@@ -122,10 +123,12 @@ def test_one_step_against_the_50_digit_reference(lib, kind, N, form):
                                      {4}     0.575  0.697  0.682  0.503
         f64 inverse per-step         4+1+1          0.501  0.668  0.444  0.513
                                      {4}            0.980  0.844  1.234  0.106
+        f32 inverse per-step         4+1+1          0.523  0.652  0.567  0.463
+                                     {4}            0.933  0.845  1.491  0.108
 
-    No class stands out (the worst figure of a class is between 0.3 and 1.3 everywhere): a single step from exact inputs is
-    dominated by the last rounding of each output, and the bound of 8 is not approached.  The test prints every figure, per
-    class."""
+    No class stands out (the worst figure of a class is between 0.3 and 1.5 everywhere, but for E of the {4} inverse forms:
+    0.02 to 0.11): a single step from exact inputs is dominated by the last rounding of each output, and the bound of 8 is
+    not approached.  The test prints every figure, per class."""
     f = ACCURACY_FORMS[form]
     prec, inverse = f["prec"], bool(f.get("inverse"))
     eps = sr.EPS[prec]
