@@ -647,7 +647,8 @@ int fiveeq_gather_rows_f32(int32_t n_rows, int64_t n_out, int64_t ld_in, const f
  * member-step where a ring of T rows takes 4 or 8.  fiveeq_hist_bins then counts rows of such indices into
  * hist dev [n_rows][n_bins] uint64 (ACCUMULATED INTO).  The caller runs spans of at most ring_rows steps and drains the
  * ring between them (EnsembleEngine does, on a second stream).  The pass does not see T: per-step moments, if wanted,
- * come from T_stats. */
+ * come from T_stats.  fiveeq_hist_bins skips every index >= n_bins (0xFFFF among them) and changes nothing outside
+ * hist[row][0 .. n_bins - 1] of the n_rows rows it is given. */
 int fiveeq_run_fused_bins_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
                               const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
                               const double *r, const double *q, double *R, double *S,

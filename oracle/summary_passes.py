@@ -29,16 +29,45 @@ def _rows(ptr, dtype, n_rows, n, ld):
     return _view(ptr, dtype, (n_rows - 1) * ld + n if n_rows else 0), [slice(k * ld, k * ld + n) for k in range(n_rows)]
 
 
-def bin_rule(x, lo, hi, n_bins, dtype):
-    """THE BIN RULE of include/fiveeq.h for rows of `dtype`; NaN -> -1 (no bin).  fp32 rows: one fp32 FMA (restated in fp64
-    and rounded to fp32 once), fp64 rows: the fp64 formula.  Both monotone in x, which is all the selection needs."""
-    inv_w = n_bins / (hi - lo) if hi > lo else 0.0
+def fma_f32(x, a, c):
+    """fma(x, a, c) of fp32 operands, correctly rounded to fp32 (one rounding, like the device's v_fma_f32), elementwise.
+    The product of two floats is exact in fp64 (48 significant bits, exponents within +-300); TwoSum gives the fp64 sum s of
+    product and addend and its exact residual; where the residual is not zero s is ROUNDED TO ODD (the neighbour of s on the
+    residual's side when the last bit of s is even), which keeps the sticky information a second rounding needs; that value
+    rounds once to fp32 (53 >= 24 + 2 bits).  Infinite and NaN intermediates pass through as fp64 arithmetic gives them."""
+    x, a, c = (np.asarray(v, dtype=np.float32).astype(np.float64) for v in (x, a, c))
     with np.errstate(invalid="ignore", over="ignore"):
+        p = x * a
+        s = p + c
+        t = s - p
+        err = (p - (s - t)) + (c - t)
+        fix = np.isfinite(s) & (err != 0.0) & ((np.asarray(s).view(np.int64) & 1) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(err > 0.0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def rule_constants_f32(lo, inv_w):
+    """make_rule of fiveeq_stats.hpp for fp32 rows: (scale, offset) = ((float)clamp(inv_w, +-3.0e38), (float)clamp(-lo * inv_w,
+    +-3.0e38)), from fp64 lo and inv_w — finite whatever the range."""
+    big = 3.0e38
+    with np.errstate(over="ignore"):
+        return (np.float32(min(max(np.float64(inv_w), -big), big)),
+                np.float32(min(max(-np.float64(lo) * np.float64(inv_w), -big), big)))
+
+
+def bin_rule(x, lo, hi, n_bins, dtype):
+    """THE BIN RULE of include/fiveeq.h for rows of `dtype`, EXACTLY; NaN -> -1 (no bin).  inv_w = n_bins / (hi - lo) in fp64
+    (0.0 when hi <= lo: the ranged entry points' constant row).  fp32 rows: pos = fma(x, scale, offset) in fp32, one rounding
+    (fma_f32, rule_constants_f32); fp64 rows: pos = (x - lo) * inv_w.  Then clamp to [0, n_bins - 1] (a NaN pos — inf * 0 —
+    clamps to 0), then truncate."""
+    lo, hi = np.float64(lo), np.float64(hi)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        inv_w = np.float64(n_bins) / (hi - lo) if hi > lo else np.float64(0.0)
         if dtype == np.float32:
-            pos = (x.astype(np.float64) * np.float64(np.float32(inv_w)) + np.float64(np.float32(-lo * inv_w))).astype(np.float32)
+            pos = fma_f32(x, *rule_constants_f32(lo, inv_w))
         else:
-            pos = (x - lo) * inv_w
-        b = np.trunc(np.clip(np.nan_to_num(pos, nan=0.0), 0.0, n_bins - 1)).astype(np.int64)
+            pos = (np.asarray(x, dtype=np.float64) - lo) * inv_w
+        b = np.trunc(np.clip(np.nan_to_num(pos, nan=0.0, posinf=np.inf, neginf=-np.inf), 0.0, n_bins - 1)).astype(np.int64)
     return np.where(np.isnan(x), -1, b)
 
 
