@@ -52,6 +52,8 @@ def main():
     ap.add_argument("--forcing", action="store_true", help="per-member forcing scales, per-scenario aerosol tables")
     ap.add_argument("--weights", action="store_true", help="importance-weight every member instead of rejection sampling")
     ap.add_argument("--resample", type=int, default=0, metavar="M", help="project only M resampled equal-weight members")
+    ap.add_argument("--metrics", default="", metavar="LEVELS", help="comma-separated warming levels (K): also print, per scenario, "
+                    "peak warming, P(exceed level) and the crossing year, from one pass over the stored rows")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -103,6 +105,26 @@ def main():
     for name, sm in zip(proj.scenario_names, sums):
         q = sm["percentiles"][-1].tolist()
         print(f"  {name:5s} T({int(run_years[-1])}) 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} K")
+    if a.metrics:
+        from fiveeqscm_amd import metrics
+        from fiveeqscm_amd.distributed import gather_summary, gather_weighted_summary
+        levels = tuple(float(v) for v in a.metrics.split(","))
+        m = proj.trajectory_metrics(levels=levels)              # all scenarios in one launch, stored steps only
+        w = how.get("weights")
+        for s, name in enumerate(proj.scenario_names):
+            peak = m.peak[s].reshape(1, -1)
+            if w is not None:
+                q = gather_weighted_summary(peak, w, pct)["percentiles"][0].tolist()
+            else:
+                q = gather_summary(peak[:, how["accepted"]].contiguous() if "accepted" in how else peak, pct)["percentiles"][0].tolist()
+            print(f"  {name:5s} peak warming 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} K")
+            first = m.first[s] if "accepted" not in how else m.first[s][:, how["accepted"]]
+            for l, (crossed, total) in enumerate(metrics.exceedance(first, weights=w)):
+                line = f"        P(T >= {levels[l]:g} K) = {crossed / total:.4f}"
+                if crossed:
+                    c = metrics.crossing_summary(first[l], run_years, pct, weights=w)["percentiles"][0].tolist()
+                    line += f"; first stored year at or above, among those that cross, 5/50/95 %: {c[0]:.0f} / {c[1]:.0f} / {c[2]:.0f}"
+                print(line)
     hist.close()
     proj.close()
 

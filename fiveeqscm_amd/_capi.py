@@ -18,6 +18,12 @@ DRIVE_STRIDE = 8
 LHS_MAX_TOTAL = 1 << 28
 MAX_FEXT = 4
 WSCAN_TILE = 1024                   # weights per workgroup of fiveeq_wscan (fiveeq_resample.hpp)
+MAX_LEVELS = 8                      # FIVEEQ_MAX_LEVELS / FIVEEQ_MAX_WINDOWS of fiveeq_traj_metrics_* (fiveeq_metrics.hpp)
+MAX_WINDOWS = 4
+METRICS_TILE_F64 = 512              # members per workgroup of traj_metrics_kernel: 256 lanes of 16 bytes of a row
+METRICS_TILE_F32 = 1024
+METRICS_UNROLL = 8                  # rows whose loads its row loop issues before it uses the first (16-byte loads)
+METRICS_UNROLL_NARROW = 2           # the same on the element-load path; load() checks all four against the library
 
 OK = 0
 E_INVALID = -1
@@ -150,6 +156,12 @@ SIGNATURES = {
     "fiveeq_resample_pick": (ctypes.c_int, [_i64, _p, ctypes.c_uint64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
     "fiveeq_gather_rows_f64": (ctypes.c_int, [_i32, _i64, _i64, _p, _i64, _p, _p, _p]),
     "fiveeq_gather_rows_f32": (ctypes.c_int, [_i32, _i64, _i64, _p, _i64, _p, _p, _p]),
+    "fiveeq_max_levels": (_i32, []),
+    "fiveeq_max_windows": (_i32, []),
+    "fiveeq_metrics_tile": (_i32, [_i32]),
+    "fiveeq_metrics_unroll": (_i32, [_i32]),
+    "fiveeq_traj_metrics_f64": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _i32, _p]),
+    "fiveeq_traj_metrics_f32": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _i32, _p]),
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_wide_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_nt_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -163,7 +175,7 @@ _lib = None
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
-    "fiveeq_diag.hpp")) + (
+    "fiveeq_metrics.hpp", "fiveeq_diag.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 
@@ -212,6 +224,9 @@ def load(path=None):
     if lib.fiveeq_sizeof_model() != ctypes.sizeof(Model):
         raise ImportError(f"{lib_path}: sizeof(fiveeq_model)={lib.fiveeq_sizeof_model()} but the ctypes "
                           f"mirror is {ctypes.sizeof(Model)} bytes")
+    shape = (lib.fiveeq_metrics_tile(8), lib.fiveeq_metrics_tile(4), lib.fiveeq_metrics_unroll(1), lib.fiveeq_metrics_unroll(0))
+    if shape != (METRICS_TILE_F64, METRICS_TILE_F32, METRICS_UNROLL, METRICS_UNROLL_NARROW):
+        raise ImportError(f"{lib_path}: traj_metrics_kernel's tiles / unrolls are {shape}, the binding's constants say otherwise")
     # The library must have been compiled from the sources lying next to this file: a prebuilt .so that travelled to
     # another box, or survived a source edit, is refused instead of tested.  (FIVEEQ_ALLOW_STALE_LIB=1: experiment
     # variants built from patched sources, tools/ only.)

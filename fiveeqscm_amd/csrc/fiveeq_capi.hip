@@ -1511,6 +1511,98 @@ int fiveeq_gather_rows_f32(int32_t n_rows, int64_t n_out, int64_t ld_in, const f
                            const int32_t* src, void* stream) {
     return gather_rows<float>(n_rows, n_out, ld_in, rows_in, ld_out, rows_out, src, stream);
 }
+// ---- per-member trajectory metrics of stored rows (kernel 9) ---------------------------------------------------------------
+}  // extern "C"
+namespace {
+static_assert(fiveeq::METRICS_MAX_LEVELS == FIVEEQ_MAX_LEVELS && fiveeq::METRICS_MAX_WINDOWS == FIVEEQ_MAX_WINDOWS,
+              "fiveeq_metrics.hpp and fiveeq.h disagree");
+template <typename T>
+int traj_metrics(int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, const T* rows, int64_t scen_stride, const int32_t* steps,
+                 int32_t n_levels, const double* levels, int32_t n_windows, const int32_t* windows, double* fmet, int32_t* imet,
+                 int32_t first_call, void* stream) {
+    if (int rc = check_scen(n_scen)) return rc;
+    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
+    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
+    if (ld < n) return fail(FIVEEQ_E_INVALID, "ld=%lld < n_members=%lld", (long long)ld, (long long)n);
+    if (n_scen > 1 && scen_stride < (int64_t)n_rows * ld)
+        return fail(FIVEEQ_E_INVALID, "scen_stride=%lld < n_rows * ld = %lld", (long long)scen_stride, (long long)((int64_t)n_rows * ld));
+    if (n_levels < 0 || n_levels > FIVEEQ_MAX_LEVELS) return fail(FIVEEQ_E_INVALID, "n_levels=%d outside 0..%d", n_levels, FIVEEQ_MAX_LEVELS);
+    if (n_windows < 0 || n_windows > FIVEEQ_MAX_WINDOWS)
+        return fail(FIVEEQ_E_INVALID, "n_windows=%d outside 0..%d", n_windows, FIVEEQ_MAX_WINDOWS);
+    if (n_levels > 0 && !levels) return fail(FIVEEQ_E_INVALID, "levels is NULL with n_levels=%d", n_levels);
+    if (n_windows > 0 && !windows) return fail(FIVEEQ_E_INVALID, "windows is NULL with n_windows=%d", n_windows);
+    if (n_rows > 0 && !rows) return fail(FIVEEQ_E_INVALID, "rows is NULL");
+    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
+    if (!fmet) return fail(FIVEEQ_E_INVALID, "fmet is NULL");
+    if (!imet) return fail(FIVEEQ_E_INVALID, "imet is NULL");
+    if (misaligned(rows, sizeof(T))) return fail(FIVEEQ_E_INVALID, "rows must be %d-byte aligned", (int)sizeof(T));
+    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
+    if (misaligned(fmet, 8)) return fail(FIVEEQ_E_INVALID, "fmet must be 8-byte aligned");
+    if (misaligned(imet, 4)) return fail(FIVEEQ_E_INVALID, "imet must be 4-byte aligned");
+    fiveeq::MetricsSpec sp = {};
+    for (int l = 0; l < n_levels; ++l) {
+        if (std::isnan(levels[l])) return fail(FIVEEQ_E_INVALID, "levels[%d] is NaN", l);
+        sp.level[l] = levels[l];
+    }
+    for (int w = 0; w < n_windows; ++w) {
+        const int32_t a = windows[2 * w], b = windows[2 * w + 1];
+        if (a < 0 || a > b) return fail(FIVEEQ_E_INVALID, "windows[%d] = [%d, %d): want 0 <= a <= b", w, a, b);
+        sp.win[w][0] = a, sp.win[w][1] = b;
+    }
+    sp.n_levels = n_levels, sp.n_windows = n_windows;
+    if (n_rows == 0 && !first_call) return FIVEEQ_OK;         // nothing to fold into the state
+    // 16-byte row loads where every lane's address rows + s scen_stride + k ld + m (m a multiple of the lane's members) is
+    // aligned: the members [0, n_vec) in whole lanes; the ragged tail (fewer members than a lane's) and unaligned rows take the
+    // element loads, in a launch of their own on the columns from n_vec
+    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
+    const bool wide = !misaligned(rows, 16) && ld % per16 == 0 && (n_scen == 1 || scen_stride % per16 == 0);
+    const int64_t n_vec = wide ? n / per16 * per16 : 0;
+    const auto grid = [&](int64_t members) {
+        return dim3((unsigned)((members + fiveeq::METRICS_TILE<T> - 1) / fiveeq::METRICS_TILE<T>), (unsigned)n_scen);
+    };
+#define FIVEEQ_METRICS_LAUNCH1(F, NL, VEC, m0, members)                                                                          \
+    hipLaunchKernelGGL((fiveeq::traj_metrics_kernel<T, F, NL, VEC>), grid(members), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream,   \
+                       n_rows, (int)(members), ld, rows + (m0), scen_stride, steps, sp, fmet + (m0), imet + (m0))
+#define FIVEEQ_METRICS_LAUNCH(NL)                                                                                                \
+    case NL:                                                                                                                     \
+        if (n_vec > 0) {                                                                                                         \
+            if (first_call) FIVEEQ_METRICS_LAUNCH1(true, NL, true, 0, n_vec);                                                    \
+            else FIVEEQ_METRICS_LAUNCH1(false, NL, true, 0, n_vec);                                                              \
+        }                                                                                                                        \
+        if (n_vec < n) {                                                                                                         \
+            if (first_call) FIVEEQ_METRICS_LAUNCH1(true, NL, false, n_vec, n - n_vec);                                           \
+            else FIVEEQ_METRICS_LAUNCH1(false, NL, false, n_vec, n - n_vec);                                                     \
+        }                                                                                                                        \
+        break;
+    switch (n_levels) {                                        // a kernel per number of levels (fiveeq_metrics.hpp)
+        FIVEEQ_METRICS_LAUNCH(0) FIVEEQ_METRICS_LAUNCH(1) FIVEEQ_METRICS_LAUNCH(2) FIVEEQ_METRICS_LAUNCH(3) FIVEEQ_METRICS_LAUNCH(4)
+        FIVEEQ_METRICS_LAUNCH(5) FIVEEQ_METRICS_LAUNCH(6) FIVEEQ_METRICS_LAUNCH(7) FIVEEQ_METRICS_LAUNCH(8)
+    }
+#undef FIVEEQ_METRICS_LAUNCH
+#undef FIVEEQ_METRICS_LAUNCH1
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int32_t fiveeq_max_levels(void) { return FIVEEQ_MAX_LEVELS; }
+int32_t fiveeq_max_windows(void) { return FIVEEQ_MAX_WINDOWS; }
+int32_t fiveeq_metrics_tile(int32_t elem_bytes) {
+    return elem_bytes == 8 ? fiveeq::METRICS_TILE<double> : elem_bytes == 4 ? fiveeq::METRICS_TILE<float> : 0;
+}
+int32_t fiveeq_metrics_unroll(int32_t wide) { return wide ? fiveeq::METRICS_UNROLL : fiveeq::METRICS_UNROLL_NARROW; }
+int fiveeq_traj_metrics_f64(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const double* rows, int64_t scen_stride,
+                            const int32_t* steps, int32_t n_levels, const double* levels, int32_t n_windows, const int32_t* windows,
+                            double* fmet, int32_t* imet, int32_t first_call, void* stream) {
+    return traj_metrics<double>(n_scen, n_rows, n_members, ld, rows, scen_stride, steps, n_levels, levels, n_windows, windows, fmet, imet,
+                                first_call, stream);
+}
+int fiveeq_traj_metrics_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const float* rows, int64_t scen_stride,
+                            const int32_t* steps, int32_t n_levels, const double* levels, int32_t n_windows, const int32_t* windows,
+                            double* fmet, int32_t* imet, int32_t first_call, void* stream) {
+    return traj_metrics<float>(n_scen, n_rows, n_members, ld, rows, scen_stride, steps, n_levels, levels, n_windows, windows, fmet, imet,
+                               first_call, stream);
+}
 int fiveeq_math_probe_f64(int32_t op, int64_t n, const double* x, double* y, void* stream) {
     return math_probe<double>(op, n, x, y, stream);
 }

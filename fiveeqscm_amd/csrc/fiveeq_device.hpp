@@ -21,6 +21,7 @@
 //                       6   row_moments_kernel, select_bins_kernel, select_pick_kernel: the end-of-run summary
 //   fiveeq_wsummary.hpp 7   wrow_moments_kernel, whist_rows_kernel, wselect_bins_kernel, wselect_pick_kernel: the weighted summary
 //   fiveeq_resample.hpp 8   wscan_*_kernel, resample_pick_kernel, gather_rows_kernel: resampling a weighted ensemble
+//   fiveeq_metrics.hpp  9   traj_metrics_kernel per-member peak, level crossings and window sums of the stored rows, in one streaming pass
 //   fiveeq_diag.hpp     stream_copy_kernel, stream_copy_wide_kernel, stream_copy_nt_kernel, math_probe_kernel, busy_kernel
 // and what they share: fiveeq_math.hpp (the model struct, lane types, fe_* math), fiveeq_stats.hpp (per-wave statistics, the bin
 // rule), fiveeq_member.hpp (member_step(), the misfit update, the lane's member span and row access).
@@ -67,4 +68,5 @@ constexpr int DRIVE_STRIDE = 8;
 #include "fiveeq_summary.hpp"
 #include "fiveeq_wsummary.hpp"
 #include "fiveeq_resample.hpp"
+#include "fiveeq_metrics.hpp"
 #include "fiveeq_diag.hpp"

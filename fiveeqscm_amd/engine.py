@@ -962,6 +962,22 @@ class EnsembleEngine(CheckpointMixin):
             sums = torch.cat([self.stats_sums(int(t), int(t) + 1, scenario=sc) for t in steps])[:, 1:5].contiguous()
         return gather_summary(rows, percentiles, dst=dst, group=group, stats=stats, local_sums=sums)
 
+    def trajectory_metrics(self, levels=(), windows=(), scenario=None, state=None):
+        """Per-member metrics of the stored T rows (metrics.trajectory_metrics over self.T and self.out_steps): peak and the
+        step it is reached, per level the first stored step at or above it and the number of stored steps there, per step
+        window [a, b) the sum and mean of the stored steps inside, the number of NaN rows — one streaming HIP pass.  With the
+        scenario axis, scenario=None covers all scenarios in one launch and the results carry a leading [S] axis; an index
+        covers that scenario.  Only reads the engine: R, S, T and C are untouched.  `peak` (as peak.reshape(1, -1)) goes
+        straight into distributed.gather_summary / gather_weighted_summary as a one-row block."""
+        from .metrics import trajectory_metrics
+        if self.T is None or self.n_rows == 0:
+            raise RuntimeError("no stored T rows: trajectory metrics need output_steps")
+        if self._ps_unjoined:
+            self.join()
+        rows = self.T[self._scen(scenario)] if self.scenario_axis and scenario is not None else self.T
+        with torch.cuda.device(self.device):
+            return trajectory_metrics(rows, self.out_steps, levels=levels, windows=windows, state=state)
+
     def resampled(self, plan):
         """(params, R0, S0) of the equal-weight ensemble `plan` (a constrain.Resample of this shard's members, from device
         weights) draws from this engine: ready for EnsembleEngine(params, plan.n_members, emissions, R0=R0, S0=S0, ...), which

@@ -640,6 +640,53 @@ int fiveeq_gather_rows_f64(int32_t n_rows, int64_t n_out, int64_t ld_in, const d
 int fiveeq_gather_rows_f32(int32_t n_rows, int64_t n_out, int64_t ld_in, const float *rows_in, int64_t ld_out, float *rows_out,
                            const int32_t *src, void *stream);
 
+/* new — TRAJECTORY METRICS: per member (and scenario), from the STORED T rows of a run, what an overshoot is judged by: the
+ * peak and when it is reached, when each warming level is first crossed and for how many stored steps it is held, and sums
+ * over step windows (a 2081-2100 mean) — DESIGN.md section 3.13; host side: fiveeqscm_amd/metrics.py,
+ * EnsembleEngine.trajectory_metrics.  Additive: no symbol above changes, FIVEEQ_ABI_VERSION stays 13.
+ *
+ * ONE streaming pass over rows dev [n_scen][n_rows][ld] (scenario blocks scen_stride elements apart; with n_scen == 1
+ * scen_stride is not used), all metrics at once, the per-member state carried in and out so that the rows can come in
+ * blocks.  steps dev [n_rows] int32: entry k is the model step row k holds.  levels HOST [n_levels] fp64, 0 <= n_levels <=
+ * fiveeq_max_levels() (FIVEEQ_MAX_LEVELS); windows HOST [n_windows][2] int32 = [a_w, b_w), 0 <= n_windows <=
+ * fiveeq_max_windows() (FIVEEQ_MAX_WINDOWS); both are copied by the call.  The state of member m of scenario s:
+ *     fmet dev [n_scen][1 + n_windows][ld] fp64:      peak, then wsum[w]
+ *     imet dev [n_scen][2 + 2 n_levels][ld] int32:    t_peak, n_nan, then first[l], then n_above[l]
+ * DEFINITION.  Tw = the row value widened exactly to fp64.  For every row k in row order, t = steps[k]:
+ *     if Tw is NaN:        n_nan += 1                (a NaN fails every comparison: no part in peak / first / n_above)
+ *     if Tw > peak:        peak = Tw; t_peak = t     (strict: the EARLIEST step attaining the peak is kept)
+ *     for each level l:    if Tw >= level_l: n_above[l] += 1; if first[l] < 0: first[l] = t
+ *     for each window w:   if a_w <= t < b_w: wsum[w] = wsum[w] + Tw       (one rounded fp64 add; NaN propagates)
+ * first_call != 0: the call starts from peak = -inf, t_peak = -1, first = -1, counts and sums 0 and does NOT read the state
+ * blocks; first_call == 0: it continues the state it is handed.  Rows [0, k) in one call and rows [k, n) in a second give
+ * the bits of one call: every result is an integer or an fp64 sum in row order, so launch shape, row split and shard split
+ * cannot change a bit.  n_rows == 0 with first_call: the state is initialised; without: nothing is done.  Columns
+ * [n_members, ld) of the state blocks are never written.
+ * THE CALLER OWES: steps strictly increasing within a call and across the calls of one state (steps is device memory: the
+ * library cannot look; fiveeqscm_amd/metrics.py checks) — "first" and "earliest" mean row order.
+ * FIVEEQ_E_INVALID, before anything is launched, for: n_scen outside 1..fiveeq_max_scenarios(); n_rows < 0; n_members < 1 or
+ * >= 2^31; ld < n_members; scen_stride < n_rows * ld with n_scen > 1; n_levels / n_windows out of range; a NaN level; a
+ * window with a > b or a < 0; a NULL pointer (rows / steps may be NULL with n_rows == 0, levels / windows with a count of
+ * 0); a pointer not aligned to its element (rows, steps 4, fmet 8, imet 4).  Rows aligned to 16 bytes with ld (and
+ * scen_stride) a multiple of 16 bytes get 16-byte loads — an optimisation, not a contract. */
+#define FIVEEQ_MAX_LEVELS   8
+#define FIVEEQ_MAX_WINDOWS  4
+int32_t fiveeq_max_levels(void);
+int32_t fiveeq_max_windows(void);
+/* the kernel's shape, for tests that pick their sizes at its edges: members per workgroup for rows of elem_bytes (8 or 4; 0
+ * for anything else), and the rows whose loads the row loop issues before it uses the first (wide != 0: the 16-byte loads;
+ * 0: the element loads) */
+int32_t fiveeq_metrics_tile(int32_t elem_bytes);
+int32_t fiveeq_metrics_unroll(int32_t wide);
+int fiveeq_traj_metrics_f64(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const double *rows,
+                            int64_t scen_stride, const int32_t *steps, int32_t n_levels, const double *levels,
+                            int32_t n_windows, const int32_t *windows, double *fmet, int32_t *imet, int32_t first_call,
+                            void *stream);
+int fiveeq_traj_metrics_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const float *rows,
+                            int64_t scen_stride, const int32_t *steps, int32_t n_levels, const double *levels,
+                            int32_t n_windows, const int32_t *windows, double *fmet, int32_t *imet, int32_t first_call,
+                            void *stream);
+
 /* STREAMED HISTOGRAMS through a ring of BIN INDICES (round 3).  fiveeq_run_fused_bins_* is
  * fiveeq_run_fused_* (same arguments, same results, C_traj / T_traj / T_stats as there) that ALSO writes, for every step t of
  * the span and every member m, the histogram bin of T(t, m) — the rule of fiveeq_hist_rows_* with (hist_lo, hist_hi, n_bins),
