@@ -26,7 +26,11 @@ are resampled into M equal-weight ones — by their importance weights with --we
 drawn floor or ceil of M / accepted times) — and only
 those are branched into the scenarios (EnsembleEngine.resampled) and summarised, with the plain unweighted gather_summary.
 
-    python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights] [--resample M]
+--drivers prints, per scenario and for the last stored T row and the peak, the parameters ranked by the share of the spread
+they explain (EnsembleEngine.drivers: eta2, the first-order sensitivity index, with the correlation) — once over all projected
+members and once under the posterior the run uses (weights, accepted, or the resampled members, which are their own posterior).
+
+    python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights] [--resample M] [--drivers]
 """
 import argparse
 import os
@@ -54,6 +58,7 @@ def main():
     ap.add_argument("--resample", type=int, default=0, metavar="M", help="project only M resampled equal-weight members")
     ap.add_argument("--metrics", default="", metavar="LEVELS", help="comma-separated warming levels (K): also print, per scenario, "
                     "peak warming, P(exceed level) and the crossing year, from one pass over the stored rows")
+    ap.add_argument("--drivers", action="store_true", help="rank the parameters by the share of the spread of T they explain")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -125,6 +130,18 @@ def main():
                     c = metrics.crossing_summary(first[l], run_years, pct, weights=w)["percentiles"][0].tolist()
                     line += f"; first stored year at or above, among those that cross, 5/50/95 %: {c[0]:.0f} / {c[1]:.0f} / {c[2]:.0f}"
                 print(line)
+    if a.drivers:
+        names = proj.parameter_rows()[0]
+        peak = proj.trajectory_metrics().peak
+        cases = [("all members", {})] + ([("posterior", how)] if how else [])
+        for s, name in enumerate(proj.scenario_names):
+            y = torch.stack([proj.T[s, -1].to(torch.float64), peak[s]])
+            for label, kw in cases:
+                d = proj.drivers(y, **kw)
+                print(f"  {name:5s} drivers, {label} (ess {d.moments.ess:.0f}, eta2 of an unrelated parameter {d.noise_floor:.4f}):")
+                for k, what in enumerate((f"T({int(run_years[-1])})", "peak")):
+                    top = torch.argsort(d.eta2[:, k].nan_to_num(-1.0), descending=True)[:5].tolist()
+                    print(f"        {what:8s} " + ", ".join(f"{names[i]} {float(d.eta2[i, k]):.3f} (r {float(d.moments.corr[i, k]):+.2f})" for i in top))
     hist.close()
     proj.close()
 

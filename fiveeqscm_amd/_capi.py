@@ -24,6 +24,12 @@ METRICS_TILE_F64 = 512              # members per workgroup of traj_metrics_kern
 METRICS_TILE_F32 = 1024
 METRICS_UNROLL = 8                  # rows whose loads its row loop issues before it uses the first (16-byte loads)
 METRICS_UNROLL_NARROW = 2           # the same on the element-load path; load() checks all four against the library
+MAX_JOINT_ROWS = 32                 # fiveeq_max_joint_rows() / fiveeq_max_cond_bins() of the joint statistics (fiveeq_joint.hpp)
+MAX_COND_BINS = 32
+# fiveeq_joint_tile(0..7): x rows, y rows per workgroup of the co-moment pass; members per chunk; members per lane and load of
+# fp64 / fp32 rows; bins, y rows per workgroup of the conditional sums; lanes per workgroup.  load() checks them.
+JOINT_TILE = (4, 4, 4096, 2, 4, 16, 4, 256)
+JOINT_TILE_X, JOINT_TILE_Y, JOINT_CHUNK, JOINT_LANE_F64, JOINT_LANE_F32, COND_TILE_BINS, COND_TILE_Y, JOINT_BLOCK = JOINT_TILE
 
 OK = 0
 E_INVALID = -1
@@ -162,6 +168,15 @@ SIGNATURES = {
     "fiveeq_metrics_unroll": (_i32, [_i32]),
     "fiveeq_traj_metrics_f64": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _i32, _p]),
     "fiveeq_traj_metrics_f32": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _i32, _p]),
+    "fiveeq_max_joint_rows": (_i32, []),
+    "fiveeq_max_cond_bins": (_i32, []),
+    "fiveeq_joint_tile": (_i32, [_i32]),
+    "fiveeq_joint_chunks": (ctypes.c_int64, [_i64]),
+    "fiveeq_joint_moments_words": (ctypes.c_int64, [_i32, _i32]),
+    "fiveeq_cond_sums_words": (ctypes.c_int64, [_i32, _i32, _i32]),
+    **{f"fiveeq_{name}_{sfx}": (ctypes.c_int, args) for sfx in ("f64", "f32") for name, args in (
+        ("joint_moments", [_i64, _i32, _i64, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+        ("cond_sums", [_i64, _i32, _i64, _p, _i32, _i64, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]))},
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_wide_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_nt_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -175,7 +190,7 @@ _lib = None
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
-    "fiveeq_metrics.hpp", "fiveeq_diag.hpp")) + (
+    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 
@@ -227,6 +242,9 @@ def load(path=None):
     shape = (lib.fiveeq_metrics_tile(8), lib.fiveeq_metrics_tile(4), lib.fiveeq_metrics_unroll(1), lib.fiveeq_metrics_unroll(0))
     if shape != (METRICS_TILE_F64, METRICS_TILE_F32, METRICS_UNROLL, METRICS_UNROLL_NARROW):
         raise ImportError(f"{lib_path}: traj_metrics_kernel's tiles / unrolls are {shape}, the binding's constants say otherwise")
+    joint = tuple(lib.fiveeq_joint_tile(k) for k in range(len(JOINT_TILE))) + (lib.fiveeq_max_joint_rows(), lib.fiveeq_max_cond_bins())
+    if joint != JOINT_TILE + (MAX_JOINT_ROWS, MAX_COND_BINS):
+        raise ImportError(f"{lib_path}: the joint passes' tiles / limits are {joint}, the binding's constants say otherwise")
     # The library must have been compiled from the sources lying next to this file: a prebuilt .so that travelled to
     # another box, or survived a source edit, is refused instead of tested.  (FIVEEQ_ALLOW_STALE_LIB=1: experiment
     # variants built from patched sources, tools/ only.)

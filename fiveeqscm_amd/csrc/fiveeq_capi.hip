@@ -1603,6 +1603,127 @@ int fiveeq_traj_metrics_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, i
     return traj_metrics<float>(n_scen, n_rows, n_members, ld, rows, scen_stride, steps, n_levels, levels, n_windows, windows, fmet, imet,
                                first_call, stream);
 }
+// ---- joint statistics of per-member rows (kernels 10a / 10b) ----------------------------------------------------------------
+}  // extern "C"
+namespace {
+// the checks both joint passes share; every message names the argument
+template <typename T>
+int joint_check(int64_t n, int32_t n_x, int64_t ld_x, const T* x, int32_t n_y, int64_t ld_y, const T* y, const uint64_t* weights,
+                const double* pivots, const double* partial) {
+    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
+    if (n_x < 1 || n_x > fiveeq::JOINT_MAX_ROWS) return fail(FIVEEQ_E_INVALID, "n_x=%d outside 1..%d", n_x, fiveeq::JOINT_MAX_ROWS);
+    if (n_y < 1 || n_y > fiveeq::JOINT_MAX_ROWS) return fail(FIVEEQ_E_INVALID, "n_y=%d outside 1..%d", n_y, fiveeq::JOINT_MAX_ROWS);
+    if (ld_x < n) return fail(FIVEEQ_E_INVALID, "ld_x=%lld < n_members=%lld", (long long)ld_x, (long long)n);
+    if (ld_y < n) return fail(FIVEEQ_E_INVALID, "ld_y=%lld < n_members=%lld", (long long)ld_y, (long long)n);
+    if (!x) return fail(FIVEEQ_E_INVALID, "x is NULL");
+    if (!y) return fail(FIVEEQ_E_INVALID, "y is NULL");
+    if (!weights) return fail(FIVEEQ_E_INVALID, "weights is NULL");
+    if (!pivots) return fail(FIVEEQ_E_INVALID, "pivots is NULL");
+    if (!partial) return fail(FIVEEQ_E_INVALID, "partial is NULL");
+    if (misaligned(x, sizeof(T))) return fail(FIVEEQ_E_INVALID, "x must be %d-byte aligned", (int)sizeof(T));
+    if (misaligned(y, sizeof(T))) return fail(FIVEEQ_E_INVALID, "y must be %d-byte aligned", (int)sizeof(T));
+    if (misaligned(weights, 8)) return fail(FIVEEQ_E_INVALID, "weights must be 8-byte aligned");
+    if (misaligned(pivots, 8)) return fail(FIVEEQ_E_INVALID, "pivots must be 8-byte aligned");
+    if (misaligned(partial, 8)) return fail(FIVEEQ_E_INVALID, "partial must be 8-byte aligned");
+    return FIVEEQ_OK;
+}
+template <typename T>
+int joint_moments(int64_t n, int32_t n_x, int64_t ld_x, const T* x, int32_t n_y, int64_t ld_y, const T* y, const uint64_t* weights,
+                  const double* pivots, double* partial, double* co, double* margins, uint64_t* info, uint64_t* nanrows, void* stream) {
+    if (int rc = joint_check(n, n_x, ld_x, x, n_y, ld_y, y, weights, pivots, partial)) return rc;
+    if (!co) return fail(FIVEEQ_E_INVALID, "co is NULL");
+    if (!margins) return fail(FIVEEQ_E_INVALID, "margins is NULL");
+    if (!info) return fail(FIVEEQ_E_INVALID, "info is NULL");
+    if (!nanrows) return fail(FIVEEQ_E_INVALID, "nanrows is NULL");
+    if (misaligned(co, 8)) return fail(FIVEEQ_E_INVALID, "co must be 8-byte aligned");
+    if (misaligned(margins, 8)) return fail(FIVEEQ_E_INVALID, "margins must be 8-byte aligned");
+    if (misaligned(info, 8)) return fail(FIVEEQ_E_INVALID, "info must be 8-byte aligned");
+    if (misaligned(nanrows, 8)) return fail(FIVEEQ_E_INVALID, "nanrows must be 8-byte aligned");
+    const int64_t chunks = fiveeq_joint_chunks(n), R = n_x + n_y, pairs = (int64_t)n_x * n_y;
+    const unsigned tiles = (unsigned)(((n_x + fiveeq::JOINT_TX - 1) / fiveeq::JOINT_TX) * ((n_y + fiveeq::JOINT_TY - 1) / fiveeq::JOINT_TY));
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned long long* upart = reinterpret_cast<const unsigned long long*>(partial);
+    hipLaunchKernelGGL(fiveeq::joint_moments_kernel<T>, dim3((unsigned)chunks, tiles), dim3(FIVEEQ_BLOCK), 0, st, n, n_x, ld_x, x, n_y,
+                       ld_y, y, reinterpret_cast<const unsigned long long*>(weights), pivots, partial);
+    hipLaunchKernelGGL(fiveeq::joint_fold_f64_kernel, dim3((unsigned)pairs), dim3(64), 0, st, chunks, partial, co);
+    hipLaunchKernelGGL(fiveeq::joint_fold_f64_kernel, dim3((unsigned)(2 * R)), dim3(64), 0, st, chunks, partial + pairs * chunks, margins);
+    hipLaunchKernelGGL(fiveeq::joint_fold_u64_kernel, dim3((unsigned)R), dim3(64), 0, st, chunks, upart + (pairs + 2 * R) * chunks,
+                       reinterpret_cast<unsigned long long*>(nanrows));
+    hipLaunchKernelGGL(fiveeq::joint_fold_info_kernel, dim3(1), dim3(64), 0, st, chunks, R, upart + (pairs + 2 * R) * chunks,
+                       upart + (pairs + 3 * R) * chunks, reinterpret_cast<unsigned long long*>(info));
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+template <typename T>
+int cond_sums(int64_t n, int32_t n_x, int64_t ld_x, const T* x, int32_t n_y, int64_t ld_y, const T* y, const uint64_t* weights,
+              int32_t n_bins, const double* edges, const double* pivots, double* partial, double* sums, uint64_t* binw, uint64_t* xnan,
+              void* stream) {
+    if (int rc = joint_check(n, n_x, ld_x, x, n_y, ld_y, y, weights, pivots, partial)) return rc;
+    if (n_bins < 1 || n_bins > fiveeq::JOINT_MAX_BINS) return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, fiveeq::JOINT_MAX_BINS);
+    if (n_bins > 1 && !edges) return fail(FIVEEQ_E_INVALID, "edges is NULL with n_bins=%d", n_bins);
+    if (!sums) return fail(FIVEEQ_E_INVALID, "sums is NULL");
+    if (!binw) return fail(FIVEEQ_E_INVALID, "binw is NULL");
+    if (!xnan) return fail(FIVEEQ_E_INVALID, "xnan is NULL");
+    if (misaligned(edges, 8)) return fail(FIVEEQ_E_INVALID, "edges must be 8-byte aligned");
+    if (misaligned(sums, 8)) return fail(FIVEEQ_E_INVALID, "sums must be 8-byte aligned");
+    if (misaligned(binw, 8)) return fail(FIVEEQ_E_INVALID, "binw must be 8-byte aligned");
+    if (misaligned(xnan, 8)) return fail(FIVEEQ_E_INVALID, "xnan must be 8-byte aligned");
+    const int64_t chunks = fiveeq_joint_chunks(n), cells = (int64_t)n_x * n_bins;
+    const unsigned tiles = (unsigned)(n_x * ((n_bins + fiveeq::COND_TB - 1) / fiveeq::COND_TB) * ((n_y + fiveeq::COND_TY - 1) / fiveeq::COND_TY));
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned long long* upart = reinterpret_cast<const unsigned long long*>(partial);
+    hipLaunchKernelGGL(fiveeq::cond_sums_kernel<T>, dim3((unsigned)chunks, tiles), dim3(FIVEEQ_BLOCK), 0, st, n, n_x, ld_x, x, n_y, ld_y, y,
+                       reinterpret_cast<const unsigned long long*>(weights), n_bins, edges, pivots, partial);
+    hipLaunchKernelGGL(fiveeq::joint_fold_f64_kernel, dim3((unsigned)(cells * n_y)), dim3(64), 0, st, chunks, partial, sums);
+    hipLaunchKernelGGL(fiveeq::joint_fold_u64_kernel, dim3((unsigned)cells), dim3(64), 0, st, chunks, upart + cells * n_y * chunks,
+                       reinterpret_cast<unsigned long long*>(binw));
+    hipLaunchKernelGGL(fiveeq::joint_fold_u64_kernel, dim3((unsigned)n_x), dim3(64), 0, st, chunks, upart + cells * (n_y + 1) * chunks,
+                       reinterpret_cast<unsigned long long*>(xnan));
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int32_t fiveeq_max_joint_rows(void) { return fiveeq::JOINT_MAX_ROWS; }
+int32_t fiveeq_max_cond_bins(void) { return fiveeq::JOINT_MAX_BINS; }
+int32_t fiveeq_joint_tile(int32_t which) {
+    switch (which) {
+        case 0: return fiveeq::JOINT_TX;
+        case 1: return fiveeq::JOINT_TY;
+        case 2: return fiveeq::JOINT_CHUNK;
+        case 3: return fiveeq::Wide<double>::N;
+        case 4: return fiveeq::Wide<float>::N;
+        case 5: return fiveeq::COND_TB;
+        case 6: return fiveeq::COND_TY;
+        case 7: return FIVEEQ_BLOCK;
+        default: return 0;
+    }
+}
+int64_t fiveeq_joint_chunks(int64_t n_members) {
+    return n_members < 1 ? 0 : (n_members + fiveeq::JOINT_CHUNK - 1) / fiveeq::JOINT_CHUNK;
+}
+int64_t fiveeq_joint_moments_words(int32_t n_x, int32_t n_y) { return (int64_t)n_x * n_y + 3 * (int64_t)(n_x + n_y) + 3; }
+int64_t fiveeq_cond_sums_words(int32_t n_x, int32_t n_y, int32_t n_bins) { return (int64_t)n_x * n_bins * (n_y + 1) + n_x; }
+int fiveeq_joint_moments_f64(int64_t n_members, int32_t n_x, int64_t ld_x, const double* x, int32_t n_y, int64_t ld_y, const double* y,
+                             const uint64_t* weights, const double* pivots, double* partial, double* co, double* margins,
+                             uint64_t* info, uint64_t* nanrows, void* stream) {
+    return joint_moments<double>(n_members, n_x, ld_x, x, n_y, ld_y, y, weights, pivots, partial, co, margins, info, nanrows, stream);
+}
+int fiveeq_joint_moments_f32(int64_t n_members, int32_t n_x, int64_t ld_x, const float* x, int32_t n_y, int64_t ld_y, const float* y,
+                             const uint64_t* weights, const double* pivots, double* partial, double* co, double* margins,
+                             uint64_t* info, uint64_t* nanrows, void* stream) {
+    return joint_moments<float>(n_members, n_x, ld_x, x, n_y, ld_y, y, weights, pivots, partial, co, margins, info, nanrows, stream);
+}
+int fiveeq_cond_sums_f64(int64_t n_members, int32_t n_x, int64_t ld_x, const double* x, int32_t n_y, int64_t ld_y, const double* y,
+                         const uint64_t* weights, int32_t n_bins, const double* edges, const double* pivots, double* partial,
+                         double* sums, uint64_t* binw, uint64_t* xnan, void* stream) {
+    return cond_sums<double>(n_members, n_x, ld_x, x, n_y, ld_y, y, weights, n_bins, edges, pivots, partial, sums, binw, xnan, stream);
+}
+int fiveeq_cond_sums_f32(int64_t n_members, int32_t n_x, int64_t ld_x, const float* x, int32_t n_y, int64_t ld_y, const float* y,
+                         const uint64_t* weights, int32_t n_bins, const double* edges, const double* pivots, double* partial,
+                         double* sums, uint64_t* binw, uint64_t* xnan, void* stream) {
+    return cond_sums<float>(n_members, n_x, ld_x, x, n_y, ld_y, y, weights, n_bins, edges, pivots, partial, sums, binw, xnan, stream);
+}
 int fiveeq_math_probe_f64(int32_t op, int64_t n, const double* x, double* y, void* stream) {
     return math_probe<double>(op, n, x, y, stream);
 }

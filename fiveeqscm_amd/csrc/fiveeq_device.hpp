@@ -22,6 +22,7 @@
 //   fiveeq_wsummary.hpp 7   wrow_moments_kernel, whist_rows_kernel, wselect_bins_kernel, wselect_pick_kernel: the weighted summary
 //   fiveeq_resample.hpp 8   wscan_*_kernel, resample_pick_kernel, gather_rows_kernel: resampling a weighted ensemble
 //   fiveeq_metrics.hpp  9   traj_metrics_kernel per-member peak, level crossings and window sums of the stored rows, in one streaming pass
+//   fiveeq_joint.hpp    10  joint_moments_kernel, cond_sums_kernel and their folds: co-moments and conditional sums of per-member rows
 //   fiveeq_diag.hpp     stream_copy_kernel, stream_copy_wide_kernel, stream_copy_nt_kernel, math_probe_kernel, busy_kernel
 // and what they share: fiveeq_math.hpp (the model struct, lane types, fe_* math), fiveeq_stats.hpp (per-wave statistics, the bin
 // rule), fiveeq_member.hpp (member_step(), the misfit update, the lane's member span and row access).
@@ -69,4 +70,5 @@ constexpr int DRIVE_STRIDE = 8;
 #include "fiveeq_wsummary.hpp"
 #include "fiveeq_resample.hpp"
 #include "fiveeq_metrics.hpp"
+#include "fiveeq_joint.hpp"
 #include "fiveeq_diag.hpp"

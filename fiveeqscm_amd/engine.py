@@ -978,6 +978,40 @@ class EnsembleEngine(CheckpointMixin):
         with torch.cuda.device(self.device):
             return trajectory_metrics(rows, self.out_steps, levels=levels, windows=windows, state=state)
 
+    def parameter_rows(self, names=None):
+        """(names, rows [K, N]) — this shard's per-member parameters as device rows in the engine's dtype, in the order r0[g],
+        rC[g], rT[g] per gas, q[0], q[1], ECS, TCR (params.ecs_tcr of the q rows) and, with forcing=, f_scale[g] and
+        fx_scale[k].  names: the rows wanted, in the order wanted.  Reads the engine's rows; writes nothing."""
+        from .params import ecs_tcr, forcing_2x
+        G = self.n_gas
+        have = [f"{k}[{g}]" for g in range(G) for k in ("r0", "rC", "rT")] + ["q[0]", "q[1]", "ECS", "TCR"]
+        ecs, tcr = ecs_tcr(self.q, self.params["d"], forcing_2x(self.params))
+        rows = [self.r, self.q, ecs[None], tcr[None]]
+        if self.fscale is not None:
+            have += [f"f_scale[{g}]" for g in range(G)] + [f"fx_scale[{k}]" for k in range(int(self.fscale.shape[0]) - G)]
+            rows.append(self.fscale)
+        rows = torch.cat(rows)
+        if names is None:
+            return have, rows
+        names = list(names)
+        unknown = [n for n in names if n not in have]
+        if unknown:
+            raise ValueError(f"parameter_rows: no rows {unknown}; this engine has {have}")
+        return names, rows[[have.index(n) for n in names]].contiguous()
+
+    def drivers(self, y, names=None, bins=16, weights=None, accepted=None, group=None):
+        """Which parameter drives y: joint.sensitivity(parameter_rows(names), y, ...) — eta2, the correlations and slopes of
+        the engine's parameter rows against y [Ky, N], any device rows of this shard's members (stored T rows,
+        trajectory_metrics().peak[None], chi2()[None]; with the scenario axis, one scenario's rows).  At most 32 parameter rows
+        a call: pass names= for a larger set.  Collective over `group`.  Returns joint.Sensitivity; its x axis follows
+        parameter_rows(names)[0]."""
+        from .joint import sensitivity
+        if self._ps_unjoined:
+            self.join()
+        x = self.parameter_rows(names)[1]
+        with torch.cuda.device(self.device):
+            return sensitivity(x, y, bins=bins, weights=weights, accepted=accepted, group=group)
+
     def resampled(self, plan):
         """(params, R0, S0) of the equal-weight ensemble `plan` (a constrain.Resample of this shard's members, from device
         weights) draws from this engine: ready for EnsembleEngine(params, plan.n_members, emissions, R0=R0, S0=S0, ...), which

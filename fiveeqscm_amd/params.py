@@ -100,6 +100,17 @@ def k_q(TCR, ECS, d, F2x):
     return np.stack([(TCR - ECS * k[1]) / den, (ECS * k[0] - TCR) / den], axis=0)
 
 
+def ecs_tcr(q, d, F2x):
+    """q [2, ...] -> (ECS, TCR), the inverse of k_q:  ECS = F2x (q1 + q2),  TCR = F2x (q1 k1 + q2 k2).  NumPy rows, or torch
+    rows on their device and in their dtype."""
+    d = np.asarray(d, dtype=np.float64)
+    k = 1.0 - (d / 70.0) * (-np.expm1(-70.0 / d))
+    if not hasattr(q, "device"):
+        q = np.asarray(q, dtype=np.float64)
+    F2x = float(F2x)
+    return F2x * (q[0] + q[1]), F2x * (q[0] * float(k[0]) + q[1] * float(k[1]))
+
+
 # ------------------------------------------------------------------------------------
 # default parameter sets (shared values; r0/rC/rT/q here are the ensemble CENTRES)
 # ------------------------------------------------------------------------------------

@@ -687,6 +687,67 @@ int fiveeq_traj_metrics_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, i
                             int32_t n_windows, const int32_t *windows, double *fmet, int32_t *imet, int32_t first_call,
                             void *stream);
 
+/* new — JOINT STATISTICS: co-moments and conditional sums of per-member rows, for covariances, correlations, regression slopes
+ * and first-order variance-based sensitivity indices of outputs against parameters, under the integer weights of WEIGHTED
+ * SUMMARY — DESIGN.md section 3.14; host side: fiveeqscm_amd/joint.py, EnsembleEngine.drivers.  Additive: no symbol above
+ * changes, FIVEEQ_ABI_VERSION stays 13.
+ *
+ * x dev [n_x][ld_x], y dev [n_y][ld_y]: rows of the same n_members members, one element type per call, every value widened
+ * exactly to fp64.  weights dev [n_members] uint64, required, 0 <= w <= 2^32 (the contract of WEIGHTED SUMMARY); a member of
+ * weight 0 does not exist for either pass, whatever its values (NaN and +-inf included).  1 <= n_x, n_y <=
+ * fiveeq_max_joint_rows() (32); ld_x, ld_y >= n_members; 1 <= n_members < 2^31.  x, y, ld * sizeof(element) and weights aligned
+ * to 16 bytes get 16-byte loads, anything else element loads: the same bits either way.
+ *
+ * (a) CO-MOMENTS.  pivots dev [n_x + n_y] fp64 = (cx, then cy).  Per member with w > 0, one rounding per written operation:
+ *         wd = (double) w;   dx_i = x_i - cx_i;   dy_j = y_j - cy_j;   p_j = wd * dy_j;   px_i = wd * dx_i
+ *         co[i][j]      = fma(dx_i, p_j, co[i][j])
+ *         margins[r][0] = margins[r][0] + p_r;   margins[r][1] = fma(p_r, d_r, margins[r][1])      r: the x rows, then the y rows
+ *     co dev [n_x][n_y] fp64; margins dev [n_x + n_y][2] fp64; info dev [4] uint64 = (sum w, exact; the count of w > 0; flags; 0)
+ *     with flag bit 0: a NaN value with w > 0 in any row, bit 1: a weight above 2^32 — the caller's error; nanrows dev
+ *     [n_x + n_y] uint64 = the weight of the members with w > 0 whose value in that row is NaN.  A NaN propagates through the
+ *     fp64 sums of the rows it sits in, and through no others: pair (i, j) is NaN exactly when nanrows of x row i or y row j
+ *     is not 0 (or a sum overflows).
+ * (b) CONDITIONAL SUMS.  edges dev [n_x][n_bins - 1] fp64, non-decreasing per row (NULL allowed with n_bins == 1); 1 <= n_bins
+ *     <= fiveeq_max_cond_bins() (32); pivots dev [n_y] fp64 = cy.  THE BIN of member m under x row i:
+ *         b = #{ k : edges[i][k] < x_i }
+ *     — a value equal to an edge belongs to the LOWER bin, which is the bin an inverted-CDF percentile edge closes.  A NaN x_i
+ *     with w > 0 has no bin: its weight is added to xnan[i].
+ *         sums[i][b][j] = sums[i][b][j] + wd * (y_j - cy_j)          dev [n_x][n_bins][n_y] fp64
+ *         binw[i][b]   += w                                          dev [n_x][n_bins] uint64, exact
+ *         xnan[i]      += w                                          dev [n_x] uint64
+ * ORDER.  Every fp64 sum is taken in one fixed order — the lane-strided member order within a chunk of fiveeq_joint_tile(2)
+ * members, a fixed tree over the lanes and waves of the workgroup, chunk order in the fold — and there is no floating-point
+ * atomic: the bits depend on n_members, the values, the weights, the pivots and the edges only, not on ld, alignment, on how
+ * the rows are tiled over workgroups (a call over 32 x 32 rows gives the bits of the calls over its sub-blocks) or on
+ * repetition.  The integer outputs are exact.  All outputs are WRITTEN, not accumulated into.
+ * partial dev: workspace of fiveeq_joint_chunks(n_members) * W 8-byte words, W = fiveeq_joint_moments_words(n_x, n_y) for (a)
+ * and fiveeq_cond_sums_words(n_x, n_y, n_bins) for (b); it needs no initialisation.  The library allocates nothing and never
+ * synchronises.
+ * FIVEEQ_E_INVALID, before anything is launched and with fiveeq_last_error() naming the argument, for: n_members < 1 or
+ * >= 2^31; n_x, n_y or n_bins outside their limits; ld_x or ld_y < n_members; a NULL pointer; a pointer not aligned to its
+ * element (x, y; 8 bytes for everything else). */
+int32_t fiveeq_max_joint_rows(void);
+int32_t fiveeq_max_cond_bins(void);
+/* the kernels' shape — not part of the ABI; for tests that pick their sizes at its edges.  which = 0, 1: x rows, y rows per
+ * workgroup of (a); 2: members per chunk; 3, 4: members per lane and load of fp64, fp32 rows; 5, 6: bins, y rows per workgroup
+ * of (b); 7: lanes per workgroup; anything else: 0 */
+int32_t fiveeq_joint_tile(int32_t which);
+int64_t fiveeq_joint_chunks(int64_t n_members);
+int64_t fiveeq_joint_moments_words(int32_t n_x, int32_t n_y);
+int64_t fiveeq_cond_sums_words(int32_t n_x, int32_t n_y, int32_t n_bins);
+int fiveeq_joint_moments_f64(int64_t n_members, int32_t n_x, int64_t ld_x, const double *x, int32_t n_y, int64_t ld_y,
+                             const double *y, const uint64_t *weights, const double *pivots, double *partial, double *co,
+                             double *margins, uint64_t *info, uint64_t *nanrows, void *stream);
+int fiveeq_joint_moments_f32(int64_t n_members, int32_t n_x, int64_t ld_x, const float *x, int32_t n_y, int64_t ld_y,
+                             const float *y, const uint64_t *weights, const double *pivots, double *partial, double *co,
+                             double *margins, uint64_t *info, uint64_t *nanrows, void *stream);
+int fiveeq_cond_sums_f64(int64_t n_members, int32_t n_x, int64_t ld_x, const double *x, int32_t n_y, int64_t ld_y,
+                         const double *y, const uint64_t *weights, int32_t n_bins, const double *edges, const double *pivots,
+                         double *partial, double *sums, uint64_t *binw, uint64_t *xnan, void *stream);
+int fiveeq_cond_sums_f32(int64_t n_members, int32_t n_x, int64_t ld_x, const float *x, int32_t n_y, int64_t ld_y,
+                         const float *y, const uint64_t *weights, int32_t n_bins, const double *edges, const double *pivots,
+                         double *partial, double *sums, uint64_t *binw, uint64_t *xnan, void *stream);
+
 /* STREAMED HISTOGRAMS through a ring of BIN INDICES (round 3).  fiveeq_run_fused_bins_* is
  * fiveeq_run_fused_* (same arguments, same results, C_traj / T_traj / T_stats as there) that ALSO writes, for every step t of
  * the span and every member m, the histogram bin of T(t, m) — the rule of fiveeq_hist_rows_* with (hist_lo, hist_hi, n_bins),
