@@ -4,10 +4,13 @@
 The record is the synthetic one committed for the tests (tests/golden/obs_synthetic.csv, made by
 tests/golden/make_obs_synthetic.py: one known member plus 0.1 K noise over 1900..2069).  Needs an MI355X.
 
-    python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing]
+    python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing] [--co2-record]
 
 --forcing adds forcing uncertainty (EnsembleEngine(forcing=), fiveeqscm_amd/forcing.py): an aerosol-like cooling scaled per
 member, and the accepted range of ECS with a shared and with a sampled scale.
+--co2-record also makes a CO2 record the same way (one known member's stored concentration plus 1 ppm noise over the same
+years), scores the stored T and C rows against both records (EnsembleEngine.score) and prints the posterior spread of the
+carbon-cycle parameter r0 of CO2 with and without the CO2 record.
 """
 import argparse
 import os
@@ -29,6 +32,8 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--forcing", action="store_true",
                     help="also sample an aerosol scale per member and print the accepted range of ECS with and without it")
+    ap.add_argument("--co2-record", action="store_true",
+                    help="also score the stored CO2 rows against a synthetic CO2 record and print what it does to r0 of CO2")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -53,6 +58,34 @@ def main():
     eng.close()
     if a.forcing:
         forcing_uncertainty(p, N, n_steps, dtype, obs)
+    if a.co2_record:
+        co2_record(p, N, n_steps, dtype, obs, run_years, years)
+
+
+def co2_record(p, N, n_steps, dtype, obs, run_years, years, truth=12345, sigma_ppm=1.0):
+    """--co2-record: the run stores the rows of the observed years; member `truth`'s CO2 plus noise is the record.  T barely
+    constrains the carbon cycle, the observed concentration does: the weighted spread of r0 of CO2 narrows once its chi2 is
+    added to that of T."""
+    steps = np.searchsorted(run_years, years)
+    stored = sorted(set(int(t) for t in steps) | set(int(t) for t in obs.live_steps))
+    eng = EnsembleEngine(p, N, emissions.rcp_like_emissions(n_steps, 3), dtype=dtype, output_steps=stored, device="cuda:0")
+    eng.run(mode="auto")
+    row_of = {t: r for r, t in enumerate(eng.out_steps.tolist())}
+    truth %= N
+    series = eng.C[[row_of[int(t)] for t in steps], 0, truth].double().cpu().numpy()
+    noisy = series + np.random.default_rng(2017).normal(0.0, sigma_ppm, series.size)
+    co2 = constrain.Observations.absolute(run_years, years, noisy, sigma_ppm)
+    s = eng.score({"T": obs, 0: co2})
+    r0 = p["r0"][0].double()
+    order = torch.argsort(r0)
+    print(f"scored {s.n_obs['T']} T and {s.n_obs[0]} CO2 observations from the stored rows (mode {eng.last_mode}); r0 of CO2 of the "
+          f"known member: {float(r0[truth]):.2f}")
+    for label, chi2 in (("T record only", s.chi2["T"]), ("T and CO2 records", s.total)):
+        w = constrain.importance_weights(chi2)[order].double()
+        cdf = torch.cumsum(w, 0) / w.sum()
+        lo, mid, hi = (float(r0[order][int(torch.searchsorted(cdf, torch.tensor(q, dtype=cdf.dtype, device=cdf.device)))]) for q in (0.05, 0.5, 0.95))
+        print(f"  r0[CO2] {label:18s} 5/50/95 %: {lo:.2f} / {mid:.2f} / {hi:.2f}   (90 % width {hi - lo:.2f})")
+    eng.close()
 
 
 def forcing_uncertainty(p, N, n_steps, dtype, obs):

@@ -29,6 +29,11 @@ MAX_COND_BINS = 32
 # fiveeq_joint_tile(0..7): x rows, y rows per workgroup of the co-moment pass; members per chunk; members per lane and load of
 # fp64 / fp32 rows; bins, y rows per workgroup of the conditional sums; lanes per workgroup.  load() checks them.
 JOINT_TILE = (4, 4, 4096, 2, 4, 16, 4, 256)
+MAX_SCORE_Q = 4                     # fiveeq_max_score_quantities() of fiveeq_score_rows_* (fiveeq_score.hpp)
+SCORE_TILE_F64 = 512                # members per workgroup of score_rows_kernel: 256 lanes of 16 bytes of a row
+SCORE_TILE_F32 = 1024
+SCORE_UNROLL = 8                    # live rows whose loads its row loop issues before it uses the first (16-byte loads)
+SCORE_UNROLL_NARROW = 4             # the same on the element-load path; load() checks all five against the library
 JOINT_TILE_X, JOINT_TILE_Y, JOINT_CHUNK, JOINT_LANE_F64, JOINT_LANE_F32, COND_TILE_BINS, COND_TILE_Y, JOINT_BLOCK = JOINT_TILE
 
 OK = 0
@@ -177,6 +182,11 @@ SIGNATURES = {
     **{f"fiveeq_{name}_{sfx}": (ctypes.c_int, args) for sfx in ("f64", "f32") for name, args in (
         ("joint_moments", [_i64, _i32, _i64, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
         ("cond_sums", [_i64, _i32, _i64, _p, _i32, _i64, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]))},
+    "fiveeq_max_score_quantities": (_i32, []),
+    "fiveeq_score_tile": (_i32, [_i32]),
+    "fiveeq_score_unroll": (_i32, [_i32]),
+    "fiveeq_score_rows_f64": (ctypes.c_int, [_i32, _i32, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _i64, _p]),
+    "fiveeq_score_rows_f32": (ctypes.c_int, [_i32, _i32, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _i64, _p]),
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_wide_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_nt_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -190,7 +200,7 @@ _lib = None
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
-    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp")) + (
+    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 
@@ -245,6 +255,10 @@ def load(path=None):
     joint = tuple(lib.fiveeq_joint_tile(k) for k in range(len(JOINT_TILE))) + (lib.fiveeq_max_joint_rows(), lib.fiveeq_max_cond_bins())
     if joint != JOINT_TILE + (MAX_JOINT_ROWS, MAX_COND_BINS):
         raise ImportError(f"{lib_path}: the joint passes' tiles / limits are {joint}, the binding's constants say otherwise")
+    score = (lib.fiveeq_score_tile(8), lib.fiveeq_score_tile(4), lib.fiveeq_score_unroll(1), lib.fiveeq_score_unroll(0),
+             lib.fiveeq_max_score_quantities())
+    if score != (SCORE_TILE_F64, SCORE_TILE_F32, SCORE_UNROLL, SCORE_UNROLL_NARROW, MAX_SCORE_Q):
+        raise ImportError(f"{lib_path}: score_rows_kernel's tiles / unrolls / limit are {score}, the binding's constants say otherwise")
     # The library must have been compiled from the sources lying next to this file: a prebuilt .so that travelled to
     # another box, or survived a source edit, is refused instead of tested.  (FIVEEQ_ALLOW_STALE_LIB=1: experiment
     # variants built from patched sources, tools/ only.)

@@ -6,7 +6,9 @@ Each member is scored against the record while it is stepped: the kernels carry 
     A = A + b_t T_t;   d = T_t - o_t;   pd = p_t d;   U = U + pd;   V = V + pd d        (steps with p_t = b_t = 0 skipped)
 
 and the score of the baseline-corrected series is chi2 = V - 2 A U + A^2 P = sum_t p_t (T_t - mean_ref T - o_t)^2, P = sum_t p_t.
-Members are then kept by a threshold on chi2 or by rejection sampling, and the summaries are computed over the kept members
+A run that STORED its rows is scored after the fact, against records of T or of any gas's concentration and in every mode, pool
+layout and precision, by `score_rows` / EnsembleEngine.score (include/fiveeq.h, "SCORING STORED ROWS"): the same accumulators,
+bit for bit.  Members are then kept by a threshold on chi2 or by rejection sampling, and the summaries are computed over the kept members
 (EnsembleEngine.gather_summary(..., accepted=mask)).
 
     obs = Observations.from_years(run_years, obs_years, T_obs, sigma, baseline=(1850, 1900))
@@ -18,6 +20,7 @@ or every member is kept and weighted by its likelihood (include/fiveeq.h, "WEIGH
     w = importance_weights(eng.chi2(), group);  eng.gather_summary(steps, weights=w)
 """
 import hashlib
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -28,9 +31,11 @@ MAX_WEIGHTED_MEMBERS = 1 << 31      # fewer members than this over all ranks: ev
 
 class Observations:
     """The shared observation table obs [n_steps, 4] fp64: per step (o_t, p_t = 1/sigma_t^2 or 0, b_t = 1/n_ref inside the
-    reference period or 0, 0).  Build it with `from_years`; `table`, `P` (= sum p_t) and `sha256` (of the table's bytes)."""
+    reference period or 0, 0).  Build it with `from_years`; `table`, `P` (= sum p_t) and `sha256` (of the table's bytes).
+    anomaly=False: a record of ABSOLUTE values (an observed concentration; `absolute` builds it) — no reference period, so
+    every b_t must be 0; A then stays 0 and chi2 = V."""
 
-    def __init__(self, table):
+    def __init__(self, table, anomaly=True):
         t = np.array(table, dtype=np.float64, order="C")
         if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1:
             raise ValueError(f"observation table: shape {t.shape}, want [n_steps, 4]")
@@ -38,8 +43,15 @@ class Observations:
             raise ValueError("observation table: non-finite entries")
         if (t[:, 1] < 0).any() or (t[:, 2] < 0).any() or (t[:, 3] != 0).any():
             raise ValueError("observation table: weights must be >= 0 and column 3 zero")
-        if not t[:, 2].any():
-            raise ValueError("observation table: empty baseline period")
+        self.anomaly = bool(anomaly)
+        if self.anomaly:
+            if not t[:, 2].any():
+                raise ValueError("observation table: empty baseline period")
+        else:
+            if t[:, 2].any():
+                raise ValueError("observation table: anomaly=False takes no baseline period (every b_t must be 0)")
+            if not t[:, 1].any():
+                raise ValueError("observation table: no observation (every p_t is 0)")
         self.table = t
         self.table.setflags(write=False)
         self.P = float(np.sum(t[:, 1]))
@@ -52,19 +64,21 @@ class Observations:
     def n_steps(self):
         return int(self.table.shape[0])
 
-    @classmethod
-    def from_years(cls, run_years, obs_years, T_obs, sigma, baseline):
-        """Match observations to the run's steps by year.  run_years [n_steps]: the year of each step (T after step t is the
-        state at run_years[t]); obs_years / T_obs / sigma [n_obs]; baseline = (y0, y1), inclusive: the reference period
-        whose mean T is subtracted from each member's series before it is compared (b_t = 1/n_ref on its steps)."""
+    @property
+    def live_steps(self):
+        """The steps whose record is live (p_t != 0 or b_t != 0), increasing: the rows a score needs."""
+        return np.nonzero((self.table[:, 1] != 0) | (self.table[:, 2] != 0))[0]
+
+    @staticmethod
+    def _match_years(run_years, obs_years, values, sigma, what, extra=()):
+        """(run years, step of each observation, values, sigmas) after the checks from_years and absolute share."""
         ry = np.asarray(run_years, dtype=np.float64).reshape(-1)
         oy = np.asarray(obs_years, dtype=np.float64).reshape(-1)
-        To = np.asarray(T_obs, dtype=np.float64).reshape(-1)
+        To = np.asarray(values, dtype=np.float64).reshape(-1)
         sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), oy.shape).copy()
         if To.shape != oy.shape:
-            raise ValueError(f"T_obs has {To.size} values for {oy.size} years")
-        for name, v in (("run_years", ry), ("obs_years", oy), ("T_obs", To), ("sigma", sg), ("baseline", np.asarray(baseline,
-                                                                                                              dtype=float))):
+            raise ValueError(f"{what} has {To.size} values for {oy.size} years")
+        for name, v in (("run_years", ry), ("obs_years", oy), (what, To), ("sigma", sg)) + tuple(extra):
             if not np.isfinite(v).all():
                 raise ValueError(f"{name}: non-finite values")
         if (sg <= 0).any():
@@ -77,6 +91,15 @@ class Observations:
             raise ValueError(f"observation years {oy[~ok][:5].tolist()} are not steps of the run")
         if np.unique(idx).size != idx.size:
             raise ValueError("an observation year appears twice")
+        return ry, idx, To, sg
+
+    @classmethod
+    def from_years(cls, run_years, obs_years, T_obs, sigma, baseline):
+        """Match observations to the run's steps by year.  run_years [n_steps]: the year of each step (T after step t is the
+        state at run_years[t]); obs_years / T_obs / sigma [n_obs]; baseline = (y0, y1), inclusive: the reference period
+        whose mean T is subtracted from each member's series before it is compared (b_t = 1/n_ref on its steps)."""
+        ry, idx, To, sg = cls._match_years(run_years, obs_years, T_obs, sigma, "T_obs",
+                                           (("baseline", np.asarray(baseline, dtype=float)),))
         y0, y1 = (float(b) for b in baseline)
         ref = (ry >= y0) & (ry <= y1)
         n_ref = int(ref.sum())
@@ -87,6 +110,18 @@ class Observations:
         t[idx, 1] = 1.0 / (sg * sg)
         t[ref, 2] = 1.0 / n_ref
         return cls(t)
+
+    @classmethod
+    def absolute(cls, run_years, obs_years, values, sigma):
+        """A record of absolute values (an observed concentration), matched to the run's steps by year like from_years and
+        under its checks: no baseline, b_t = 0 everywhere (anomaly=False)."""
+        ry, idx, vals, sg = cls._match_years(run_years, obs_years, values, sigma, "values")
+        if idx.size == 0:
+            raise ValueError("values: no observation")
+        t = np.zeros((ry.size, 4), dtype=np.float64)
+        t[idx, 0] = vals
+        t[idx, 1] = 1.0 / (sg * sg)
+        return cls(t, anomaly=False)
 
 
 def misfit_numpy(T_rows, table, acc=None):
@@ -113,6 +148,102 @@ def chi2_from_misfit(misfit, P):
     """chi2 = V - 2 A U + A^2 P per member (NumPy array or torch tensor [3, N] -> [N])."""
     A, U, V = misfit[0], misfit[1], misfit[2]
     return V - 2.0 * A * U + A * A * P
+
+
+# ---- scoring STORED rows (include/fiveeq.h, "SCORING STORED ROWS"; csrc/fiveeq_score.hpp) -----------------------------------
+def _lib_and_stream(rows):
+    """(library, _capi, stream, device guard) for rows on a GPU.  (_score_host.host_passes() replaces this function and the
+    next.)"""
+    import ctypes
+
+    import torch
+
+    from . import _capi
+    lib = _capi.load()
+    return lib, _capi, ctypes.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream), torch.cuda.device(rows.device)
+
+
+def _passes_apply(rows):
+    import torch
+    return rows.is_cuda and rows.dtype in (torch.float32, torch.float64)
+
+
+def score_rows(rows, steps, observations, acc=None):
+    """The misfit accumulators of STORED rows against observed records — one streaming HIP pass, bit for bit what a run that
+    carries the record in-loop (EnsembleEngine(observations=)) leaves in `misfit`, for rows of any run.
+    rows [n_rows, N] with ONE Observations -> [3, N] fp64 (A, U, V);  rows [n_rows, n_q, N] with a sequence of n_q Observations
+    (tables of equal n_steps; quantity j of the rows against record j) -> [n_q, 3, N].  rows: fp32 / fp64 ON THE GPU, read in
+    place whenever the column stride is 1 (engine.T, engine.C and row / gas / member slices of them), copied otherwise.
+    steps [n_rows]: the model step each row holds, strictly increasing and inside the tables.  Rows whose record is dead
+    (p_t = b_t = 0) are neither read nor do their values matter.  acc: the result of an earlier call over EARLIER rows of the
+    same members — the call continues a copy of it, and the result is that of one call over all the rows.  chi2 of quantity
+    j: chi2_from_misfit(out[j], observations[j].P).  Runs on the current stream; there is no CPU path."""
+    import ctypes
+
+    import torch
+    single = isinstance(observations, Observations)
+    recs = [observations] if single else list(observations)
+    if not recs or not all(isinstance(o, Observations) for o in recs):
+        raise ValueError("observations: want an Observations or a non-empty sequence of them")
+    if not isinstance(rows, torch.Tensor) or rows.dim() != (2 if single else 3):
+        raise ValueError("rows: want a tensor [n_rows, N] with one Observations, [n_rows, n_q, N] with a sequence of them")
+    if not _passes_apply(rows):
+        raise TypeError(f"rows must be fp32 / fp64 rows on a GPU (got {rows.dtype} on {rows.device}): the score runs through the "
+                        "HIP kernel and has no CPU fallback")
+    x = rows.unsqueeze(1) if single else rows
+    K, Q, N = x.shape
+    from . import _capi
+    if Q != len(recs):
+        raise ValueError(f"rows hold {Q} quantities, observations {len(recs)}")
+    if not 1 <= Q <= _capi.MAX_SCORE_Q:
+        raise ValueError(f"{Q} quantities: at most {_capi.MAX_SCORE_Q} per call")
+    if N < 1:
+        raise ValueError("rows: no members")
+    n_steps = recs[0].n_steps
+    if any(o.n_steps != n_steps for o in recs):
+        raise ValueError(f"observations: tables of {[o.n_steps for o in recs]} steps, want equal n_steps")
+    st = np.asarray(steps)
+    if st.shape != (K,) or (K and not np.issubdtype(st.dtype, np.integer)):
+        raise ValueError(f"steps: want {K} integers, one per row")
+    st = st.astype(np.int64)
+    if K and np.any(np.diff(st) <= 0):
+        raise ValueError("steps: want strictly increasing model steps")
+    if K and (st[0] < 0 or st[-1] >= n_steps):
+        raise ValueError(f"steps: {int(st[0])}..{int(st[-1])} outside the tables' steps 0..{n_steps - 1}")
+    dev = rows.device
+    out_shape = (3, N) if single else (Q, 3, N)
+    if acc is None:
+        misfit = torch.zeros((Q, 3, N), dtype=torch.float64, device=dev)
+    else:
+        if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float64 or tuple(acc.shape) != out_shape or acc.device != dev:
+            raise ValueError(f"acc: want an fp64 tensor of shape {list(out_shape)} on {dev}")
+        misfit = acc.reshape(Q, 3, N).clone()
+    # rows the kernel walks in place: unit column stride, rows and quantities at least N apart (a row stride of 0 — an expanded
+    # view — is not)
+    if (N > 1 and x.stride(2) != 1) or (K > 1 and x.stride(0) < N) or (Q > 1 and abs(x.stride(1)) < N):
+        x = x.contiguous()
+    row_stride = int(x.stride(0)) if K > 1 else N
+    q_stride = int(x.stride(1)) if Q > 1 else N
+    lib, capi, stream, guard = _lib_and_stream(rows)
+    st32 = torch.from_numpy(st.astype(np.int32)).to(dev)
+    obs = torch.from_numpy(np.stack([o.table for o in recs])).to(dev)          # [Q, n_steps, 4]
+    fn = lib.fiveeq_score_rows_f64 if rows.dtype == torch.float64 else lib.fiveeq_score_rows_f32
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())                  # noqa: E731
+    with guard:
+        capi.check(lib, fn(Q, K, N, ptr(x) if K else None, row_stride, q_stride, ptr(st32) if K else None, ptr(obs), n_steps,
+                           ptr(misfit), N, stream))
+    return misfit[0] if single else misfit
+
+
+@dataclass
+class Score:
+    """What EnsembleEngine.score returns.  Per record key ("T" or a gas index): misfit[key] [3, N] fp64 (A, U, V), chi2[key] [N]
+    (chi2_from_misfit) and n_obs[key], the number of observations; total [N]: the chi2 added in the fixed order T, then the
+    gases ascending — what accept_*, importance_weights and resample take."""
+    misfit: dict
+    chi2: dict
+    total: object
+    n_obs: dict
 
 
 def accept_threshold(chi2, max_chi2):

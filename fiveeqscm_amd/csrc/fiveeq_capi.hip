@@ -1730,5 +1730,60 @@ int fiveeq_math_probe_f64(int32_t op, int64_t n, const double* x, double* y, voi
 int fiveeq_math_probe_f32(int32_t op, int64_t n, const float* x, float* y, void* stream) {
     return math_probe<float>(op, n, x, y, stream);
 }
+// ---- scoring stored rows against observed records (kernel 11) ----------------------------------------------------------------
+}  // extern "C"
+namespace {
+static_assert(fiveeq::SCORE_MAX_Q == FIVEEQ_MAX_SCORE_Q, "fiveeq_score.hpp and fiveeq.h disagree");
+template <typename T>
+int score_rows(int32_t n_q, int32_t n_rows, int64_t n, const T* rows, int64_t row_stride, int64_t q_stride, const int32_t* steps,
+               const double* obs, int32_t n_steps, double* misfit, int64_t ld_m, void* stream) {
+    if (n_q < 1 || n_q > FIVEEQ_MAX_SCORE_Q) return fail(FIVEEQ_E_INVALID, "n_q=%d outside 1..%d", n_q, FIVEEQ_MAX_SCORE_Q);
+    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
+    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
+    if (ld_m < n) return fail(FIVEEQ_E_INVALID, "ld_m=%lld < n_members=%lld", (long long)ld_m, (long long)n);
+    if (n_q > 1 && (q_stride < 0 ? -q_stride : q_stride) < n)
+        return fail(FIVEEQ_E_INVALID, "|q_stride|=%lld < n_members=%lld", (long long)(q_stride < 0 ? -q_stride : q_stride), (long long)n);
+    if (n_rows > 1 && row_stride < n) return fail(FIVEEQ_E_INVALID, "row_stride=%lld < n_members=%lld", (long long)row_stride, (long long)n);
+    if (n_steps < 1) return fail(FIVEEQ_E_INVALID, "n_steps=%d must be >= 1", n_steps);
+    if (n_rows > 0 && !rows) return fail(FIVEEQ_E_INVALID, "rows is NULL");
+    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
+    if (!obs) return fail(FIVEEQ_E_INVALID, "obs is NULL");
+    if (!misfit) return fail(FIVEEQ_E_INVALID, "misfit is NULL");
+    if (misaligned(rows, sizeof(T))) return fail(FIVEEQ_E_INVALID, "rows must be %d-byte aligned", (int)sizeof(T));
+    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
+    if (misaligned(obs, 8)) return fail(FIVEEQ_E_INVALID, "obs must be 8-byte aligned");
+    if (misaligned(misfit, 8)) return fail(FIVEEQ_E_INVALID, "misfit must be 8-byte aligned");
+    if (n_rows == 0) return FIVEEQ_OK;                         // nothing to fold into the accumulators
+    // 16-byte row loads where every lane's address rows + k row_stride + j q_stride + m (m a multiple of the lane's members) is
+    // aligned: the members [0, n_vec) in whole lanes; the ragged tail (fewer members than a lane's) and unaligned rows take the
+    // element loads, in a launch of their own on the columns from n_vec
+    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
+    const bool wide = !misaligned(rows, 16) && (n_rows == 1 || row_stride % per16 == 0) && (n_q == 1 || q_stride % per16 == 0);
+    const int64_t n_vec = wide ? n / per16 * per16 : 0;
+    const auto grid = [](int64_t members) { return dim3((unsigned)((members + fiveeq::SCORE_TILE<T> - 1) / fiveeq::SCORE_TILE<T>)); };
+    if (n_vec > 0)
+        hipLaunchKernelGGL((fiveeq::score_rows_kernel<T, true>), grid(n_vec), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_q, n_rows,
+                           (int)n_vec, rows, row_stride, q_stride, steps, obs, n_steps, misfit, ld_m);
+    if (n_vec < n)
+        hipLaunchKernelGGL((fiveeq::score_rows_kernel<T, false>), grid(n - n_vec), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_q, n_rows,
+                           (int)(n - n_vec), rows + n_vec, row_stride, q_stride, steps, obs, n_steps, misfit + n_vec, ld_m);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int32_t fiveeq_max_score_quantities(void) { return FIVEEQ_MAX_SCORE_Q; }
+int32_t fiveeq_score_tile(int32_t elem_bytes) {
+    return elem_bytes == 8 ? fiveeq::SCORE_TILE<double> : elem_bytes == 4 ? fiveeq::SCORE_TILE<float> : 0;
+}
+int32_t fiveeq_score_unroll(int32_t wide) { return wide ? fiveeq::SCORE_UNROLL : fiveeq::SCORE_UNROLL_NARROW; }
+int fiveeq_score_rows_f64(int32_t n_q, int32_t n_rows, int64_t n_members, const double* rows, int64_t row_stride, int64_t q_stride,
+                          const int32_t* steps, const double* obs, int32_t n_steps, double* misfit, int64_t ld_m, void* stream) {
+    return score_rows<double>(n_q, n_rows, n_members, rows, row_stride, q_stride, steps, obs, n_steps, misfit, ld_m, stream);
+}
+int fiveeq_score_rows_f32(int32_t n_q, int32_t n_rows, int64_t n_members, const float* rows, int64_t row_stride, int64_t q_stride,
+                          const int32_t* steps, const double* obs, int32_t n_steps, double* misfit, int64_t ld_m, void* stream) {
+    return score_rows<float>(n_q, n_rows, n_members, rows, row_stride, q_stride, steps, obs, n_steps, misfit, ld_m, stream);
+}
 
 }  // extern "C"

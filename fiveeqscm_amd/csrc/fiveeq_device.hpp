@@ -24,6 +24,7 @@
 //   fiveeq_metrics.hpp  9   traj_metrics_kernel per-member peak, level crossings and window sums of the stored rows, in one streaming pass
 //   fiveeq_joint.hpp    10  joint_moments_kernel, cond_sums_kernel and their folds: co-moments and conditional sums of per-member rows
 //   fiveeq_diag.hpp     stream_copy_kernel, stream_copy_wide_kernel, stream_copy_nt_kernel, math_probe_kernel, busy_kernel
+//   fiveeq_score.hpp    11  score_rows_kernel   the misfit accumulators of stored rows against observed records, live rows only
 // and what they share: fiveeq_math.hpp (the model struct, lane types, fe_* math), fiveeq_stats.hpp (per-wave statistics, the bin
 // rule), fiveeq_member.hpp (member_step(), the misfit update, the lane's member span and row access).
 // All model arithmetic is member_step(): every kernel that steps the model gives the same bits.
@@ -72,3 +73,4 @@ constexpr int DRIVE_STRIDE = 8;
 #include "fiveeq_metrics.hpp"
 #include "fiveeq_joint.hpp"
 #include "fiveeq_diag.hpp"
+#include "fiveeq_score.hpp"

@@ -978,6 +978,62 @@ class EnsembleEngine(CheckpointMixin):
         with torch.cuda.device(self.device):
             return trajectory_metrics(rows, self.out_steps, levels=levels, windows=windows, state=state)
 
+    def score(self, records, scenario=None):
+        """Score the STORED rows against observed records (constrain.score_rows; include/fiveeq.h, "SCORING STORED ROWS").
+        records: {"T": Observations, gas index: Observations, ...} — a record of warming against the stored T rows, a record of
+        a gas's concentration (Observations.absolute) against its stored C rows; every table over this run's steps.  Works
+        for every mode, pool layout and precision, since it only reads stored rows: one HIP pass over self.T, one over self.C
+        (the gases asked for, in place).  ValueError if a live step of a record is not a stored step (a partial chi2 would be
+        silent otherwise), for a gas record without stored concentrations, and with the scenario axis without scenario=.
+        Returns constrain.Score: misfit[key], chi2[key], n_obs[key] and total = the chi2 added in the order T, gases ascending
+        — which feeds accept_*, importance_weights and resample like chi2()."""
+        from .constrain import Observations, Score, chi2_from_misfit, score_rows
+        if not isinstance(records, dict) or not records:
+            raise ValueError('records: want a dict {"T" or a gas index: Observations}')
+        for g in records:
+            if g != "T" and (isinstance(g, (bool, str)) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) < self.n_gas):
+                raise ValueError(f'records: key {g!r}; want "T" or a gas index 0..{self.n_gas - 1}')
+        gases = sorted(k for k in records if k != "T")
+        order = (["T"] if "T" in records else []) + gases
+        for key in order:
+            if not isinstance(records[key], Observations):
+                raise ValueError(f"records[{key!r}]: want a constrain.Observations")
+            if records[key].n_steps != self.n_steps:
+                raise ValueError(f"records[{key!r}]: table of {records[key].n_steps} steps for a run of {self.n_steps}")
+        sc = self._scen(scenario)
+        if self.T is None:
+            raise ValueError("no stored rows to score: the engine was built with store_trajectory=False")
+        if gases and (self.C is None or self.concentration_driven):
+            raise ValueError(f"records of gases {[int(g) for g in gases]} need stored concentrations: this engine holds no C rows "
+                             "(store_concentrations=False, or a concentration-driven run whose rows are emissions)")
+        stored = set(int(t) for t in self.out_steps)
+        for key in order:
+            missing = [int(t) for t in records[key].live_steps if int(t) not in stored]
+            if missing:
+                raise ValueError(f"records[{key!r}]: {len(missing)} live steps of the record are not stored steps (out_steps), "
+                                 f"first {missing[:5]}: the score would silently cover part of the record")
+        if self._ps_unjoined:
+            self.join()
+        misfit = {}
+        if "T" in records:
+            misfit["T"] = score_rows(self.T if sc is None else self.T[sc], self.out_steps, records["T"])
+        if gases:
+            C = self.C if sc is None else self.C[sc]
+            g0, g1 = int(gases[0]), int(gases[-1])
+            step = (g1 - g0) // (len(gases) - 1) if len(gases) > 1 else 1
+            if list(range(g0, g1 + 1, step)) == [int(g) for g in gases]:
+                picked = C[:, g0:g1 + 1:step]                       # a view: the pass strides over the gases not asked for
+            else:
+                picked = C[:, [int(g) for g in gases]]
+            both = score_rows(picked, self.out_steps, [records[g] for g in gases])
+            for i, g in enumerate(gases):
+                misfit[g] = both[i]
+        chi2 = {key: chi2_from_misfit(misfit[key], records[key].P) for key in order}
+        total = chi2[order[0]]
+        for key in order[1:]:
+            total = total + chi2[key]
+        return Score(misfit, chi2, total, {key: records[key].n_obs for key in order})
+
     def parameter_rows(self, names=None):
         """(names, rows [K, N]) — this shard's per-member parameters as device rows in the engine's dtype, in the order r0[g],
         rC[g], rT[g] per gas, q[0], q[1], ECS, TCR (params.ecs_tcr of the q rows) and, with forcing=, f_scale[g] and

@@ -748,6 +748,49 @@ int fiveeq_cond_sums_f32(int64_t n_members, int32_t n_x, int64_t ld_x, const flo
                          const float *y, const uint64_t *weights, int32_t n_bins, const double *edges, const double *pivots,
                          double *partial, double *sums, uint64_t *binw, uint64_t *xnan, void *stream);
 
+/* new — SCORING STORED ROWS: the misfit of CONSTRAINED RUNS computed from the STORED rows of a run, against observed records of
+ * any stored quantity (T, the concentration of a gas) and for runs of every mode, pool layout and precision — DESIGN.md section
+ * 3.15; host side: fiveeqscm_amd/constrain.py score_rows, EnsembleEngine.score.  Additive: no symbol above changes,
+ * FIVEEQ_ABI_VERSION stays 13.
+ *
+ * ONE streaming pass.  The element of row k, quantity j, member m is rows[k * row_stride + j * q_stride + m]: the C rows
+ * [n_rows][G][ld] of a run are row_stride = G * ld, q_stride = ld; its T rows are n_q = 1 (q_stride is then not used; with
+ * n_rows == 1 row_stride is not).  1 <= n_q <= fiveeq_max_score_quantities() (FIVEEQ_MAX_SCORE_Q).  steps dev [n_rows] int32:
+ * entry k is the model step row k holds.  obs dev [n_q][n_steps][4] fp64: one table of CONSTRAINED RUNS per quantity, (o_t, p_t,
+ * b_t, 0) per step.  misfit dev [n_q][3][ld_m] fp64 = (A, U, V) per quantity, READ AND WRITTEN IN PLACE: the caller zeroes it
+ * (the contract of fiveeq_run_obs_*).  ld_m is independent of the row strides.
+ * DEFINITION.  For the rows in row order, t = steps[k], and for each quantity j with the record (o, p, b) = obs[j][t]:
+ *     if p == 0 && b == 0:  the accumulators of j are untouched, and the row's elements of j do not matter (NaN included: they
+ *                           are not read)
+ *     else, with Tw the element widened exactly to fp64, each operation rounded on its own (no fma):
+ *                           A = A + b * Tw;  d = Tw - o;  pd = p * d;  U = U + pd;  V = V + pd * d
+ * — the device function the stepping kernels call, so the pass gives, bit for bit, the misfit a run carrying the same record
+ * in-loop gives.  CONSEQUENCES: rows [0, k) in one call and rows [k, n) in a second give the bits of one call; any member
+ * sub-range gives the bits of the whole (shards exchange nothing); launch shape and alignment cannot change a bit (rows aligned
+ * to 16 bytes with strides a multiple of 16 bytes get 16-byte loads — an optimisation, not a contract); columns [n_members, ld_m)
+ * of misfit are never written; n_rows == 0 does nothing.  Rows whose record is dead are not streamed: the pass reads
+ * sizeof(element) * n_members per live row-quantity and 48 * n_members per quantity.
+ * THE CALLER OWES: steps strictly increasing within a call and across the calls of one misfit block, and every step inside
+ * [0, n_steps) (steps is device memory: the library cannot look; constrain.score_rows checks.  The kernel never reads outside
+ * the tables: a row whose step lies outside is skipped).
+ * FIVEEQ_E_INVALID, before anything is launched and with fiveeq_last_error() naming the argument, for: n_q outside
+ * 1..FIVEEQ_MAX_SCORE_Q; n_rows < 0; n_members < 1 or >= 2^31; ld_m < n_members; |q_stride| < n_members with n_q > 1;
+ * row_stride < n_members with n_rows > 1; n_steps < 1; a NULL pointer (rows and steps may be NULL with n_rows == 0); a
+ * pointer not aligned to its element (rows; steps 4; obs and misfit 8). */
+#define FIVEEQ_MAX_SCORE_Q  4
+int32_t fiveeq_max_score_quantities(void);
+/* the kernel's shape, for tests that pick their sizes at its edges: members per workgroup for rows of elem_bytes (8 or 4; 0
+ * for anything else), and the LIVE rows whose loads the row loop issues before it uses the first (wide != 0: the 16-byte
+ * loads; 0: the element loads) */
+int32_t fiveeq_score_tile(int32_t elem_bytes);
+int32_t fiveeq_score_unroll(int32_t wide);
+int fiveeq_score_rows_f64(int32_t n_q, int32_t n_rows, int64_t n_members, const double *rows, int64_t row_stride,
+                          int64_t q_stride, const int32_t *steps, const double *obs, int32_t n_steps, double *misfit,
+                          int64_t ld_m, void *stream);
+int fiveeq_score_rows_f32(int32_t n_q, int32_t n_rows, int64_t n_members, const float *rows, int64_t row_stride,
+                          int64_t q_stride, const int32_t *steps, const double *obs, int32_t n_steps, double *misfit,
+                          int64_t ld_m, void *stream);
+
 /* STREAMED HISTOGRAMS through a ring of BIN INDICES (round 3).  fiveeq_run_fused_bins_* is
  * fiveeq_run_fused_* (same arguments, same results, C_traj / T_traj / T_stats as there) that ALSO writes, for every step t of
  * the span and every member m, the histogram bin of T(t, m) — the rule of fiveeq_hist_rows_* with (hist_lo, hist_hi, n_bins),
