@@ -98,6 +98,7 @@ def _run_args(tail, scen=False, cumE=False):
 # the tails: stream; plan_out; (form, k_steps, stream); (obs, misfit); (fscale, fext, n_fext); (lo, hi, n_bins, bin_ring, ring_rows)
 _ST, _PLAN, _FORM, _OBS, _FORC = [_p], [ctypes.POINTER(_p)], [_i32, _i32, _p], [_p, _p], [_p, _p, _i32]
 _RING = [ctypes.c_double, ctypes.c_double, _i32, _p, _i32]
+_UNI = [ctypes.c_uint32, _p]        # (mask, values): the single-valued parameter rows, values on the host
 # the stepping entry points that come as _f64 and _f32: name -> _run_args(...)
 _RUNS = {
     "run": _run_args(_ST),
@@ -116,6 +117,8 @@ _RUNS = {
     "plan_create_forc": _run_args(_FORC + _OBS + _PLAN),
     "run_scen_forc": _run_args(_FORC + _FORM, scen=True),
     "plan_create_scen_forc": _run_args(_FORC + _PLAN, scen=True),
+    "run_uniform": _run_args(_UNI + _ST),
+    "plan_create_uniform": _run_args(_UNI + _PLAN),
 }
 # name -> (restype, argtypes); every symbol include/fiveeq.h declares
 SIGNATURES = {
@@ -187,6 +190,8 @@ SIGNATURES = {
     "fiveeq_score_unroll": (_i32, [_i32]),
     "fiveeq_score_rows_f64": (ctypes.c_int, [_i32, _i32, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _i64, _p]),
     "fiveeq_score_rows_f32": (ctypes.c_int, [_i32, _i32, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _i64, _p]),
+    "fiveeq_uniform_rows_f64": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, ctypes.POINTER(ctypes.c_uint32), _p, _p]),
+    "fiveeq_uniform_rows_f32": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, ctypes.POINTER(ctypes.c_uint32), _p, _p]),
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_wide_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
     "fiveeq_stream_copy_nt_f64": (ctypes.c_int, [_i64, _p, _p, _p]),

@@ -208,6 +208,7 @@ struct RunArgs : BaseArgs<T> {
     BinRing br;                  // the histogram forms' ring (else none)
     MisfitRows mf;               // the constrained forms' accumulators (else none)
     ForcRows<T> fc;              // the forcing forms' scale rows and table (else none)
+    UniformRows<T> uni{};        // the single-valued parameter rows of fiveeq_run_uniform (mask 0: every row is loaded)
 };
 
 // ---- packed fp32 lanes: two members per lane (fiveeq_math.hpp, "Lane value types") ----------------------------
@@ -264,6 +265,9 @@ constexpr bool misfit_packed_fused(int p0, int p1, int p2) { return p0 == 4 && p
 // the layouts with FORC instantiations: those that have the misfit form, with which it combines
 constexpr bool forcing_layout(int p0, int p1, int p2) { return misfit_layout(p0, p1, p2); }
 constexpr bool forcing_layout(int code) { return misfit_layout(code); }
+// the layouts with step_uniform_kernel instantiations: the same line again
+constexpr bool uniform_layout(int p0, int p1, int p2) { return misfit_layout(p0, p1, p2); }
+constexpr bool uniform_layout(int code) { return misfit_layout(code); }
 
 // ---- the two launchers: one step of the per-step kernel, one span [t_begin, t_end) of the time-fused kernel ----------------
 // The compile-time flags pick the kernel family; packing, the row policy and the pool layout are decided here per launch.
@@ -293,6 +297,9 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
                                a.br.ring_rows, a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit, a.fc.fscale, a.fc.fext,   \
                                a.fc.n_fext);                                                                                      \
     } while (0)
+#define FIVEEQ_UNIFORM_LAUNCH(V, p0, p1, p2, NT)                                                                            \
+    hipLaunchKernelGGL((step_uniform_kernel<V, p0, p1, p2, NT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, a.ld,    \
+                       a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.uni)
 #define X(p0, p1, p2)                                                                             \
     case (p0) * 100 + (p1) * 10 + (p2):                                                           \
         if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                     \
@@ -300,6 +307,19 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
         } else if constexpr (FORC && !forcing_layout(p0, p1, p2)) {                               \
             return no_forcing_form(a.code);                                                       \
         } else {                                                                                  \
+            /* the single-valued rows: plain launches of the layouts that carry the form (a.uni.mask is 0 elsewhere) */ \
+            if constexpr (!BINS && !MISFIT && !FORC && !SCEN && uniform_layout(p0, p1, p2)) {     \
+                if (a.uni.mask != 0) {                                                            \
+                    if (a.stream_rows) {                                                          \
+                        if (packed) FIVEEQ_UNIFORM_LAUNCH(P, p0, p1, p2, true);                   \
+                        else FIVEEQ_UNIFORM_LAUNCH(T, p0, p1, p2, true);                          \
+                    } else {                                                                      \
+                        if (packed) FIVEEQ_UNIFORM_LAUNCH(P, p0, p1, p2, false);                  \
+                        else FIVEEQ_UNIFORM_LAUNCH(T, p0, p1, p2, false);                         \
+                    }                                                                             \
+                    break;                                                                        \
+                }                                                                                 \
+            }                                                                                     \
             /* the streamed row form: plain and scenario launches only (the engine schedules misfit runs chunk-major) */ \
             if constexpr (!BINS && !MISFIT && !FORC) {                                                   \
                 if (a.stream_rows) {                                                              \
@@ -314,6 +334,7 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
         break;
         FIVEEQ_LAYOUTS(X)
 #undef X
+#undef FIVEEQ_UNIFORM_LAUNCH
 #undef FIVEEQ_STEP_LAUNCH
         default:
             return no_kernel(a.code);
@@ -450,6 +471,19 @@ int check_forcing(RunArgs<T>& a, const T* fscale, const T* fext, int32_t n_fext)
     return FIVEEQ_OK;
 }
 
+// the single-valued parameter rows (step_uniform_kernel): the caller's mask over the 3G rows of r and the 2 of q, and their
+// values (host).  A layout without the form keeps mask 0 and launches what the plain call launches.
+template <typename T>
+int check_uniform(RunArgs<T>& a, uint32_t mask, const T* values) {
+    const int n_rows = 3 * a.n_gas + 2;
+    if (mask >> n_rows) return fail(FIVEEQ_E_INVALID, "uniform mask 0x%x has bits at or above %d (3 n_gas + 2 rows)", mask, n_rows);
+    if (mask != 0 && !values) return fail(FIVEEQ_E_INVALID, "uniform values is NULL with mask 0x%x", mask);
+    if (mask == 0 || !uniform_layout(a.code)) return FIVEEQ_OK;
+    a.uni.mask = mask;
+    for (int k = 0; k < n_rows; ++k) a.uni.val[k] = (mask >> k) & 1u ? values[k] : T(0);
+    return FIVEEQ_OK;
+}
+
 // the scenario axis: one parameter ensemble under n_scen emission scenarios (step_scen_kernel, fused_kernel<.., SCEN>)
 constexpr int MAX_SCENARIOS = 64;
 int check_scen(int32_t n_scen) {
@@ -479,11 +513,15 @@ struct Features {
     ForcRows<T> fc;
     Use misfit = ABSENT;
     MisfitRows mf;
+    bool uniform = false;        // fiveeq_run_uniform / fiveeq_plan_create_uniform: mask and values are the caller's
+    uint32_t mask = 0;
+    const T* values = nullptr;   // host, 3G + 2
 };
 
 // Every check of a forward call but its last (the form of a run, the range of a plan), in the ONE order every family reports
 // in (tests/test_forward_precedence_cpu.py): the scenario count, [a plan: plan_out, cleared before anything else,] the base
-// arguments, the forcing rows, obs and misfit given together, the misfit rows.
+// arguments, the forcing rows, obs and misfit given together, the misfit rows; the single-valued rows of the plain family's
+// uniform twins come right behind the base arguments.
 template <typename T>
 int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan = false, void** plan_out = nullptr) {
     if (plan_out) *plan_out = nullptr;
@@ -491,6 +529,7 @@ int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan
     if (plan && !plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
     if (int rc = make_args(a, b, f.n_scen)) return rc;
     a.scen = f.scen;
+    if (int rc = f.uniform ? check_uniform(a, f.mask, f.values) : FIVEEQ_OK) return rc;
     if (int rc = f.forc ? check_forcing(a, f.fc.fscale, f.fc.fext, f.fc.n_fext) : FIVEEQ_OK) return rc;
     if (f.misfit == OPTIONAL && (f.mf.obs == nullptr) != (f.mf.misfit == nullptr))
         return fail(FIVEEQ_E_INVALID, "obs and misfit go together: both NULL (no misfit) or both set (obs=%p misfit=%p)",
@@ -630,6 +669,43 @@ int run_small(const BaseArgs<T>& b, int32_t lanes, void* stream) {
     }
 #undef FIVEEQ_SMALL_ARGS
     HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+
+// ---- the scan for single-valued parameter rows (uniform_rows_kernel): one device pass, synchronous ------------------------
+template <typename T>
+int uniform_rows(int64_t n, int64_t ld, int32_t n_r, const T* r, const T* q, uint32_t* mask_out, T* values_out, void* stream) {
+    using U = typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type;
+    constexpr int MAX_ROWS = 3 * MAX_GAS + 2;
+    if (n < 1) return fail(FIVEEQ_E_INVALID, "n_members=%lld must be >= 1", (long long)n);
+    if (ld < n) return fail(FIVEEQ_E_INVALID, "ld=%lld < n_members=%lld", (long long)ld, (long long)n);
+    if (n_r < 3 || n_r > 3 * MAX_GAS || n_r % 3) return fail(FIVEEQ_E_INVALID, "n_r_rows=%d: 3 rows per gas, 1..%d gases", n_r, MAX_GAS);
+    if (!r || !q) return fail(FIVEEQ_E_INVALID, "NULL device pointer (r=%p q=%p)", (const void*)r, (const void*)q);
+    if ((((uintptr_t)r) | ((uintptr_t)q)) & (sizeof(T) - 1)) return fail(FIVEEQ_E_INVALID, "r and q must be %d-byte aligned", (int)sizeof(T));
+    if (!mask_out || !values_out)
+        return fail(FIVEEQ_E_INVALID, "NULL output pointer (mask_out=%p values_out=%p)", (void*)mask_out, (void*)values_out);
+    const int rows = n_r + 2;
+    struct Out {
+        U first[MAX_ROWS];
+        unsigned int differs;
+    } host;
+    Out* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, sizeof(Out)));
+    hipStream_t st = (hipStream_t)stream;
+    int64_t bx = (n + (int64_t)FIVEEQ_BLOCK * 8 - 1) / ((int64_t)FIVEEQ_BLOCK * 8);        // >= 8 members per lane, at most 1024
+    if (bx > 1024) bx = 1024;                                                              // workgroups per row
+    hipError_t e = hipMemsetAsync(dev, 0, sizeof(Out), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((uniform_rows_kernel<U>), dim3((unsigned)bx, (unsigned)rows), dim3(FIVEEQ_BLOCK), 0, st, n, ld, (int)n_r,
+                           (const U*)r, (const U*)q, &dev->differs, dev->first);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&host, dev, sizeof(Out), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(FIVEEQ_E_HIP, "the scan for single-valued rows failed: %s (%d)", hipGetErrorString(e), (int)e);
+    *mask_out = ~host.differs & ((1u << rows) - 1u);
+    std::memcpy(values_out, host.first, (size_t)rows * sizeof(T));
     return FIVEEQ_OK;
 }
 
@@ -801,6 +877,41 @@ int fiveeq_plan_create_f32(const fiveeq_model* model, int64_t n_members, int64_t
                            float* S, float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, void** plan_out) {
     return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
                               {}, plan_out);
+}
+
+int fiveeq_uniform_rows_f64(int64_t n_members, int64_t ld, int32_t n_r_rows, const double* r, const double* q, uint32_t* mask_out,
+                            double* values_out, void* stream) {
+    return uniform_rows<double>(n_members, ld, n_r_rows, r, q, mask_out, values_out, stream);
+}
+int fiveeq_uniform_rows_f32(int64_t n_members, int64_t ld, int32_t n_r_rows, const float* r, const float* q, uint32_t* mask_out,
+                            float* values_out, void* stream) {
+    return uniform_rows<float>(n_members, ld, n_r_rows, r, q, mask_out, values_out, stream);
+}
+int fiveeq_run_uniform_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                           int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
+                           double* T_traj, int32_t n_rows, double* T_stats, uint32_t mask, const double* values, void* stream) {
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {false, 1, false, {}, ABSENT, {}, true, mask, values}, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
+}
+int fiveeq_run_uniform_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                           int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
+                           float* T_traj, int32_t n_rows, double* T_stats, uint32_t mask, const float* values, void* stream) {
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {false, 1, false, {}, ABSENT, {}, true, mask, values}, FIVEEQ_FORM_PER_STEP, 0, 0, stream);
+}
+int fiveeq_plan_create_uniform_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                                   int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S,
+                                   double* C_traj, double* T_traj, int32_t n_rows, double* T_stats, uint32_t mask,
+                                   const double* values, void** plan_out) {
+    return plan_create<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                               {false, 1, false, {}, ABSENT, {}, true, mask, values}, plan_out);
+}
+int fiveeq_plan_create_uniform_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                                   int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S,
+                                   float* C_traj, float* T_traj, int32_t n_rows, double* T_stats, uint32_t mask,
+                                   const float* values, void** plan_out) {
+    return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                              {false, 1, false, {}, ABSENT, {}, true, mask, values}, plan_out);
 }
 
 int fiveeq_run_inverse_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,

@@ -43,25 +43,37 @@ namespace fiveeq {
 // scale rows fscale [G + n_fext][ld] (gas rows first) — issued with the other row loads, before the staging barrier — and
 // the step's record fext [t][0 .. MAX_FEXT) is wave-uniform and read with scalar loads, like the obs record.  w (G + K) bytes
 // more per member-step; combines with MISFIT, not with BINS; default row policy; the {4} and 4 + 1 + 1 layouts.
-template <typename V, int P0, int P1, int P2, bool BINS = false, bool NT = false, bool MISFIT = false, bool FORC = false>
-__global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kernel(
-    const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
+// UNI = true: the single-valued parameter rows (step_uniform_kernel below).  Row k of r (k < 3G) with bit k of uni.mask set,
+// row j of q with bit 3G + j set, is NOT loaded: the lane takes uni.val[k] — wave-uniform, from the kernel arguments (scalar
+// registers), splat into both members of a packed lane — behind one scalar branch per row.  The loads that remain are still
+// all issued before the staging barrier; everything after them is the same member_step() and the same stores: the same bits.
+template <typename T>
+struct UniformRows {
+    uint32_t mask;
+    T val[3 * MAX_GAS + 2];
+};
+// The body of step_kernel and step_uniform_kernel (force-inlined: step_kernel's code is what it was when it spelt this out,
+// profiles/r16/uniform_rows_isa.txt).
+template <typename V, int P0, int P1, int P2, bool BINS, bool NT, bool MISFIT, bool FORC, bool UNI>
+__device__ __forceinline__ void step_body(
+    const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
     const int64_t n, const int64_t ld,
     const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
     typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
-    typename Lane<V>::S* __restrict__ C_traj /* [n_rows][G][ld] or nullptr */,
-    typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
-    const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
-    unsigned short* __restrict__ bin_ring /* BINS: [ring_rows][ld], row t mod ring_rows */, const int ring_rows,
+    typename Lane<V>::S* __restrict__ C_traj, typename Lane<V>::S* __restrict__ T_traj,
+    const int n_rows, double* __restrict__ stats,
+    unsigned short* __restrict__ bin_ring, const int ring_rows,
     const double hist_lo, const double hist_inv_w, const int n_bins,
-    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */,
-    const typename Lane<V>::S* __restrict__ fscale /* FORC: [G + n_fext][ld] */,
-    const typename Lane<V>::S* __restrict__ fext /* FORC: [n_steps][MAX_FEXT] */, const int n_fext) {
+    const double* __restrict__ obs, double* __restrict__ misfit,
+    const typename Lane<V>::S* __restrict__ fscale,
+    const typename Lane<V>::S* __restrict__ fext, const int n_fext,
+    const UniformRows<typename Lane<V>::S>& uni) {
     using L = Layout<P0, P1, P2>;
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     constexpr bool NTT = true;                    // the stored C / T rows: written once, never read by a stepping kernel
     static_assert(!FORC || (!BINS && !NT), "the forcing scales: no histogram ring, default row policy");
+    static_assert(!UNI || (!BINS && !MISFIT && !FORC), "the single-valued rows: the plain forward form only");
     __shared__ T drv[DRIVE_STRIDE];
     // idle tail lanes load a valid (aligned) member and store nothing
     const auto [m, active, full, mm] = lane_span<W, FIVEEQ_STEP_BLOCK, PARK_LAST>(n);
@@ -83,10 +95,23 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
     for (int k = 0; k < L::SP; ++k) Rv[k] = load_row<V, NT>(R + k * ld + mm);
 #pragma unroll
     for (int k = 0; k < 2; ++k) Sv[k] = load_row<V, NT>(S + k * ld + mm);
+    if constexpr (UNI) {
 #pragma unroll
-    for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_row<V, NT>(r + k * ld + mm);
+        for (int k = 0; k < 3 * L::G; ++k) {
+            if (uni.mask & (1u << k)) rr[k] = (V)uni.val[k];
+            else rr[k] = load_row<V, NT>(r + k * ld + mm);
+        }
 #pragma unroll
-    for (int k = 0; k < 2; ++k) qq[k] = load_row<V, NT>(q + k * ld + mm);
+        for (int k = 0; k < 2; ++k) {
+            if (uni.mask & (1u << (3 * L::G + k))) qq[k] = (V)uni.val[3 * L::G + k];
+            else qq[k] = load_row<V, NT>(q + k * ld + mm);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_row<V, NT>(r + k * ld + mm);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) qq[k] = load_row<V, NT>(q + k * ld + mm);
+    }
     V fs[FORC ? L::G + MAX_FEXT : 1];             // FORC: the lane's scales, gas rows first (rows past n_fext are never read)
     if constexpr (FORC) {
 #pragma unroll
@@ -134,6 +159,61 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
                            2 * wave + 1 < n_rec ? stats + ((2 * wave + 1) * n_steps + t) * 4 : nullptr);
         }
     }
+}
+
+template <typename V, int P0, int P1, int P2, bool BINS = false, bool NT = false, bool MISFIT = false, bool FORC = false>
+__global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kernel(
+    const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
+    const int64_t n, const int64_t ld,
+    const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
+    typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
+    typename Lane<V>::S* __restrict__ C_traj /* [n_rows][G][ld] or nullptr */,
+    typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
+    const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
+    unsigned short* __restrict__ bin_ring /* BINS: [ring_rows][ld], row t mod ring_rows */, const int ring_rows,
+    const double hist_lo, const double hist_inv_w, const int n_bins,
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */,
+    const typename Lane<V>::S* __restrict__ fscale /* FORC: [G + n_fext][ld] */,
+    const typename Lane<V>::S* __restrict__ fext /* FORC: [n_steps][MAX_FEXT] */, const int n_fext) {
+    step_body<V, P0, P1, P2, BINS, NT, MISFIT, FORC, false>(drive, n_steps, t, n, ld, r, q, R, S, C_traj, T_traj, n_rows, stats,
+                                                            bin_ring, ring_rows, hist_lo, hist_inv_w, n_bins, obs, misfit, fscale,
+                                                            fext, n_fext, UniformRows<typename Lane<V>::S>{});
+}
+
+// Kernel 1u — step_kernel<V, P0, P1, P2, false, NT> WITHOUT the loads of the parameter rows the caller declared single-valued
+// (UNI above; fiveeq_run_uniform_*, include/fiveeq.h "SINGLE-VALUED PARAMETER ROWS").  w bytes less per member-step and masked
+// row.  The {4} and 4 + 1 + 1 layouts, both row policies, the plain forward form.
+template <typename V, int P0, int P1, int P2, bool NT = false>
+__global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_uniform_kernel(
+    const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
+    const int64_t n, const int64_t ld,
+    const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
+    typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
+    typename Lane<V>::S* __restrict__ C_traj /* [n_rows][G][ld] or nullptr */,
+    typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
+    const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
+    const UniformRows<typename Lane<V>::S> uni) {
+    step_body<V, P0, P1, P2, false, NT, false, false, true>(drive, n_steps, t, n, ld, r, q, R, S, C_traj, T_traj, n_rows, stats,
+                                                            nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0, uni);
+}
+
+// The scan behind fiveeq_uniform_rows_*: row k of rows_r [n_r][ld] (k < n_r), row j of rows_q [2][ld] as row n_r + j.  A row
+// is single-valued iff every one of its n members has the BITS of its first (+0.0 and -0.0 differ; one NaN pattern is one
+// value); ld padding is not read.  blockIdx.y is the row, the workgroups of a row stride over its members; a wave that saw
+// another bit pattern ORs the row's bit into *differs (zeroed by the host), and the row's first workgroup stores the first
+// member's bits into first[row].
+template <typename U>
+__global__ __launch_bounds__(FIVEEQ_BLOCK) void uniform_rows_kernel(const int64_t n, const int64_t ld, const int n_r,
+                                                                    const U* __restrict__ rows_r, const U* __restrict__ rows_q,
+                                                                    unsigned int* __restrict__ differs, U* __restrict__ first) {
+    const int row = blockIdx.y;
+    const U* p = row < n_r ? rows_r + (int64_t)row * ld : rows_q + (int64_t)(row - n_r) * ld;
+    const U v0 = p[0];
+    U diff = 0;
+    for (int64_t i = (int64_t)blockIdx.x * FIVEEQ_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * FIVEEQ_BLOCK)
+        diff |= p[i] ^ v0;
+    if (__ballot(diff != 0) != 0 && (threadIdx.x & 63) == 0) atomicOr(differs, 1u << row);
+    if (blockIdx.x == 0 && threadIdx.x == 0) first[row] = v0;
 }
 
 // ---------------------------------------------------------------------------------

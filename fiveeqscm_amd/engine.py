@@ -100,7 +100,8 @@ class EnsembleEngine(CheckpointMixin):
                  device=None, store_trajectory=True, output_steps=None, store_concentrations=True,
                  collect_stats=False, hist=None, hist_ring_steps="auto", concentration_driven=False,
                  chunk_members="auto", per_step_streams="auto", fused_span="auto", small_lanes="auto", compensated=False,
-                 R0=None, S0=None, lib_path=None, observations=None, scenario_names=None, forcing=None):
+                 R0=None, S0=None, lib_path=None, observations=None, scenario_names=None, forcing=None,
+                 uniform_rows="auto"):
         """store_trajectory / output_steps: True stores C, T of every step; a list of step indices
         stores only those (rows in increasing step order, see `out_steps`); False stores nothing.
         store_concentrations=False keeps only the T rows (a 100M-member fp32 run then stores 4 B instead
@@ -167,7 +168,16 @@ class EnsembleEngine(CheckpointMixin):
         WITH THE SCENARIO AXIS forcing= is a forcing.ScenarioForcings — one table per scenario, [S, n_steps, K], its
         n_scenarios the emissions' S — and the f_scale / fx_scale rows are shared by the scenarios: member-scenario (m, s) is bit
         for bit member m of a single-scenario forcing= engine on scenario s's emissions, F_ext and table, in every mode.  (One
-        ExternalForcings table with several scenarios is refused: say ScenarioForcings.shared(fx, S) if that is what is meant.)"""
+        ExternalForcings table with several scenarios is refused: say ScenarioForcings.shared(fx, S) if that is what is meant.)
+        uniform_rows: "auto" (the default) scans the parameter rows `r` [3G, N] and `q` [2, N] ONCE, here, for rows whose N
+        members all hold the same bits (a parameter the study does not perturb; the structural zeros of the multi-gas
+        defaults), and the plain per-step launches (modes 'per_step' and 'graph', step()) then take such a row's value from
+        the kernel arguments instead of loading it at every step (include/fiveeq.h "SINGLE-VALUED PARAMETER ROWS"): w bytes
+        less per member-step and row, the same bits.  `uniform_rows` names what was found, e.g. ("rC[1]", "rC[2]", "rT[2]").
+        `r` and `q` are READ-ONLY after construction: nothing in the package writes into them (checkpoints restore state
+        only, resampled() builds a new engine); a caller who overwrites them anyway calls refresh_uniform_rows() afterwards.
+        False keeps every load.  Pool layouts without the form ({4} and 4 + 1 + 1 have it) and the other families (scenario
+        axis, observations=, forcing=, hist=) report the rows and run as before."""
         if dtype not in _DTYPES:
             raise ValueError("dtype must be torch.float64 or torch.float32")
         self.lib = _capi.load(lib_path)    # raises if the HIP library is not built
@@ -351,8 +361,31 @@ class EnsembleEngine(CheckpointMixin):
         self.last_mode = None               # the mode the last run() used after resolving 'auto'
         self.reset_state()
         self._plans = {}
+        if uniform_rows not in ("auto", False):
+            raise ValueError("uniform_rows must be 'auto' or False")
+        self._uniform_auto = uniform_rows == "auto"
+        self.refresh_uniform_rows()
         with torch.cuda.device(self.device):
             self.probe_streams()            # construction is synchronous anyway: the one place the probe may clock streams
+
+    def refresh_uniform_rows(self):
+        """Scan `r` and `q` again for single-valued rows (fiveeq_uniform_rows_*: one device pass, synchronous) — for a caller
+        who wrote into them after construction.  Drops the captured plans, which carry the old rows.  Returns `uniform_rows`;
+        () with uniform_rows=False."""
+        self.close()
+        G = self.n_gas
+        self._uniform_mask = 0
+        self._uniform_values = ((ctypes.c_double if self._w == 8 else ctypes.c_float) * (3 * G + 2))()
+        if self._uniform_auto:
+            mask = ctypes.c_uint32(0)
+            with torch.cuda.device(self.device):
+                rc = self._fn("uniform_rows")(self.n_members, self.n_members, 3 * G, self._ptr(self.r), self._ptr(self.q),
+                                              ctypes.byref(mask), self._uniform_values, self._stream())
+            _capi.check(self.lib, rc)
+            self._uniform_mask = int(mask.value)
+        names = [f"{k}[{g}]" for g in range(G) for k in ("r0", "rC", "rT")] + ["q[0]", "q[1]"]
+        self.uniform_rows = tuple(name for i, name in enumerate(names) if self._uniform_mask >> i & 1)
+        return self.uniform_rows
 
     def _initial_state(self, x, K, name):
         """R0 / S0 as a host fp64 array: [K, N], or with the scenario axis [S, K, N] (a [K, N] state broadcast to every
@@ -566,10 +599,18 @@ class EnsembleEngine(CheckpointMixin):
             def fused(t, t1, k, s):
                 return run(*args(t, t1), _capi.FORM_FUSED, int(k), self._stream(s))
         else:
-            run, run_fused, ksteps, plan = self._fn("run"), self._fn("run_fused"), self._fn("run_ksteps"), self._fn("plan_create")
+            run_fused, ksteps = self._fn("run_fused"), self._fn("run_ksteps")
+            # the per-step call and its plan: the uniform twins, which skip the loads of the single-valued rows (mask 0:
+            # today's launches); uniform_rows=False keeps today's calls
+            uni = (self._uniform_mask, self._uniform_values) if self._uniform_auto else ()
+            run = self._fn("run_uniform" if uni else "run")
+            create = self._fn("plan_create_uniform" if uni else "plan_create")
 
             def per_step(t, t1, m0, n, s):
-                return run(*args(t, t1, m0, n), self._stream(s))
+                return run(*args(t, t1, m0, n), *uni, self._stream(s))
+
+            def plan(*a):
+                return create(*a[:-1], *uni, a[-1])
 
             def fused(t, t1, k, s):                             # k < 1 (an empty range): run_ksteps would refuse it
                 return ksteps(*args(t, t1), int(k), self._stream(s)) if k >= 1 else run_fused(*args(t, t1), self._stream(s))
@@ -1137,7 +1178,11 @@ class EnsembleEngine(CheckpointMixin):
 
     # -- accounting ----------------------------------------------------------------------
     def bytes_per_member_step(self, mode="per_step", k_steps=None):
-        """ALGORITHMIC HBM bytes per member-timestep:
+        """ALGORITHMIC HBM bytes per member-timestep — every parameter row counted as loaded: a plain
+        per_step / graph run with single-valued rows (`uniform_rows`) moves w x len(uniform_rows) FEWER bytes per member-step
+        than this count, and bench.py --full's roofline.frac, priced on this count, then prices bytes the kernel no longer
+        moves.
+
         per_step:        w (2 SP + 4 G + 7)   [R,S read+write; r,q read; C,T write];
         fused / small:   w (G + 1) + w (2 SP + 3 G + 6) / steps per launch (n_steps; fused: fused_span, or with hist= the
                          ring length);

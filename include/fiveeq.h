@@ -791,6 +791,47 @@ int fiveeq_score_rows_f32(int32_t n_q, int32_t n_rows, int64_t n_members, const 
                           int64_t q_stride, const int32_t *steps, const double *obs, int32_t n_steps, double *misfit,
                           int64_t ld_m, void *stream);
 
+/* new — SINGLE-VALUED PARAMETER ROWS: the per-step form without the loads of the parameter rows whose members all hold one value
+ * — DESIGN.md section 3.16; host side: EnsembleEngine(uniform_rows=).  Additive: no symbol above changes, FIVEEQ_ABI_VERSION
+ * stays 13, fiveeq_sizeof_model() stays 448.
+ *
+ * The rows are numbered as the kernels read them: row k of r (k < 3 n_gas; gas-major r0, rC, rT) is bit k, row j of q is bit
+ * 3 n_gas + j; values [3 n_gas + 2] is indexed the same way.
+ *
+ * fiveeq_uniform_rows_*: ONE device pass over r dev [n_r_rows][ld] (n_r_rows = 3 n_gas) and q dev [2][ld].  A row is
+ * single-valued iff all n_members of its members are BITWISE equal to its first: a row of +0.0 with one -0.0 is not, a row of
+ * one NaN bit pattern is.  Columns [n_members, ld) are not examined.  The call SYNCHRONISES stream and returns, in HOST memory,
+ * *mask_out (the bits of the single-valued rows) and values_out [n_r_rows + 2] (the first member of EVERY row, single-valued or
+ * not).  FIVEEQ_E_INVALID for n_members < 1, ld < n_members, n_r_rows not 3, 6 or 9, a NULL or misaligned pointer.
+ *
+ * fiveeq_run_uniform_* / fiveeq_plan_create_uniform_*: fiveeq_run_* / fiveeq_plan_create_* (same arguments, same results bit for
+ * bit) plus (mask, values).  THE MASK IS THE CALLER'S PROMISE: a row whose bit is set is NEVER READ — every member takes
+ * values[k] — so the contents of its device memory are irrelevant (r and q themselves must still be valid pointers).  values is
+ * host memory, copied during the call; entries of rows whose bit is clear are not looked at.  mask == 0, or a pool layout
+ * without the form (it is compiled for pools {4} and 4 + 1 + 1, fp64 and fp32 packed or not, both row policies), launches
+ * exactly what fiveeq_run_* launches.  FIVEEQ_E_INVALID for bits at or above 3 n_gas + 2, and for a non-zero mask with values
+ * NULL (checked right behind the base arguments).  Per member-step the launch moves sizeof(element) bytes less per masked row. */
+int fiveeq_uniform_rows_f64(int64_t n_members, int64_t ld, int32_t n_r_rows, const double *r, const double *q,
+                            uint32_t *mask_out, double *values_out, void *stream);
+int fiveeq_uniform_rows_f32(int64_t n_members, int64_t ld, int32_t n_r_rows, const float *r, const float *q,
+                            uint32_t *mask_out, float *values_out, void *stream);
+int fiveeq_run_uniform_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                           const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                           const double *r, const double *q, double *R, double *S, double *C_traj, double *T_traj,
+                           int32_t n_rows, double *T_stats, uint32_t mask, const double *values /* host, 3G+2 */, void *stream);
+int fiveeq_run_uniform_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                           const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                           const float *r, const float *q, float *R, float *S, float *C_traj, float *T_traj,
+                           int32_t n_rows, double *T_stats, uint32_t mask, const float *values /* host, 3G+2 */, void *stream);
+int fiveeq_plan_create_uniform_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                   const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                   const double *r, const double *q, double *R, double *S, double *C_traj, double *T_traj,
+                                   int32_t n_rows, double *T_stats, uint32_t mask, const double *values, void **plan_out);
+int fiveeq_plan_create_uniform_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                   const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                   const float *r, const float *q, float *R, float *S, float *C_traj, float *T_traj,
+                                   int32_t n_rows, double *T_stats, uint32_t mask, const float *values, void **plan_out);
+
 /* STREAMED HISTOGRAMS through a ring of BIN INDICES (round 3).  fiveeq_run_fused_bins_* is
  * fiveeq_run_fused_* (same arguments, same results, C_traj / T_traj / T_stats as there) that ALSO writes, for every step t of
  * the span and every member m, the histogram bin of T(t, m) — the rule of fiveeq_hist_rows_* with (hist_lo, hist_hi, n_bins),

@@ -7,7 +7,10 @@ corrections of /opt/skills/guides/MI355X_MICROARCH.md (HBM section):
     byte count: n*8 read, n*8 written, buffers far beyond the 256 MiB Infinity Cache) IN THE SAME PASS
     and scale the step kernel's counters by (known bytes / counted bytes) of the copy.
 
-    python tools/pmc_traffic.py <fetch_pass_dir> <write_pass_dir> <copy_elems> <key> [out.json] [step|fused]
+    python tools/pmc_traffic.py <fetch_pass_dir> <write_pass_dir> <copy_elems> <key> [out.json] [step|fused|uniform]
+
+step (the default) is fiveeq::step_kernel, every parameter row loaded; uniform is fiveeq::step_uniform_kernel, the same step
+without the loads of the single-valued rows (tools/pmc_workload.py runs both).
 """
 import csv
 import glob
@@ -60,7 +63,8 @@ def reduce(fetch_dir, write_dir, copy_elems, kernel=None):
 def main():
     fetch_dir, write_dir, copy_elems, key = sys.argv[1], sys.argv[2], int(sys.argv[3]), sys.argv[4]
     out_path = sys.argv[5] if len(sys.argv) > 5 else None
-    rec = reduce(fetch_dir, write_dir, copy_elems, "fiveeq::fused_kernel" if len(sys.argv) > 6 and sys.argv[6] == "fused" else None)
+    which = sys.argv[6] if len(sys.argv) > 6 else "step"
+    rec = reduce(fetch_dir, write_dir, copy_elems, {"fused": "fiveeq::fused_kernel", "uniform": "fiveeq::step_uniform_kernel"}.get(which))
     print(json.dumps({key: rec}, indent=1))
     if out_path:
         doc = {}
