@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--resample", type=int, default=0, metavar="M", help="project only M resampled equal-weight members")
     ap.add_argument("--metrics", default="", metavar="LEVELS", help="comma-separated warming levels (K): also print, per scenario, "
                     "peak warming, P(exceed level) and the crossing year, from one pass over the stored rows")
+    ap.add_argument("--forcing-rows", action="store_true", help="also print, per scenario, the percentiles of the forcing F and the "
+                    "energy imbalance N at the last summary year (diagnosed from the stored rows: the projection then stores C too)")
     ap.add_argument("--drivers", action="store_true", help="rank the parameters by the share of the spread of T they explain")
     a = ap.parse_args()
     n_steps, N = 750, a.members
@@ -92,7 +94,7 @@ def main():
             else constrain.resample(keep, a.resample, seed=constrain.ACCEPT_SEED)
         (p_proj, R0, S0), n_proj, how = hist.resampled(plan), plan.n_members, {}
         print(f"resampled {N} members into {n_proj} equal-weight ones ({int(torch.unique(plan.src).numel())} distinct sources)")
-    proj = EnsembleEngine(p_proj, n_proj, E_s, R0=R0, S0=S0, output_steps=out_steps, store_concentrations=False,
+    proj = EnsembleEngine(p_proj, n_proj, E_s, R0=R0, S0=S0, output_steps=out_steps, store_concentrations=a.forcing_rows,
                           scenario_names=list(SCENARIOS), forcing=sf, device="cuda:0")
     proj.run(t_branch, n_steps, mode="auto")
     pct = (5.0, 50.0, 95.0)
@@ -130,6 +132,18 @@ def main():
                     c = metrics.crossing_summary(first[l], run_years, pct, weights=w)["percentiles"][0].tolist()
                     line += f"; first stored year at or above, among those that cross, 5/50/95 %: {c[0]:.0f} / {c[1]:.0f} / {c[2]:.0f}"
                 print(line)
+    if a.forcing_rows:
+        from fiveeqscm_amd.distributed import gather_summary, gather_weighted_summary
+        res = proj.forcing_rows(want=("F", "N"))                # every scenario; F and N need no consecutive steps
+        w = how.get("weights")
+        for s, name in enumerate(proj.scenario_names):
+            for what, rows, unit in (("F", res.F[s], "W m-2"), ("N", res.N[s], "W m-2")):
+                row = rows[-1:].contiguous()
+                if w is not None:
+                    q = gather_weighted_summary(row, w, pct)["percentiles"][0].tolist()
+                else:
+                    q = gather_summary(row[:, how["accepted"]].contiguous() if "accepted" in how else row, pct)["percentiles"][0].tolist()
+                print(f"  {name:5s} {what}({int(run_years[-1])}) 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} {unit}")
     if a.drivers:
         names = proj.parameter_rows()[0]
         peak = proj.trajectory_metrics().peak

@@ -120,6 +120,9 @@ _RUNS = {
     "run_uniform": _run_args(_UNI + _ST),
     "plan_create_uniform": _run_args(_UNI + _PLAN),
 }
+# fiveeq_forcing_rows_*: (model, n_rows, n_members, ld, C_rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive,
+# n_steps, q, fscale, n_fext, fext, F, F_gas, N, H, ld_out, H_io, S_io, n_mismatch, stream)
+_FORCROWS = [_mp, _i32, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]
 # name -> (restype, argtypes); every symbol include/fiveeq.h declares
 SIGNATURES = {
     "fiveeq_abi_version": (ctypes.c_int, []),
@@ -190,6 +193,9 @@ SIGNATURES = {
     "fiveeq_score_unroll": (_i32, [_i32]),
     "fiveeq_score_rows_f64": (ctypes.c_int, [_i32, _i32, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _i64, _p]),
     "fiveeq_score_rows_f32": (ctypes.c_int, [_i32, _i32, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _i64, _p]),
+    "fiveeq_forcing_rows_tile": (_i32, [_i32]),
+    "fiveeq_forcing_rows_f64": (ctypes.c_int, _FORCROWS),
+    "fiveeq_forcing_rows_f32": (ctypes.c_int, _FORCROWS),
     "fiveeq_uniform_rows_f64": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, ctypes.POINTER(ctypes.c_uint32), _p, _p]),
     "fiveeq_uniform_rows_f32": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, ctypes.POINTER(ctypes.c_uint32), _p, _p]),
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -205,7 +211,7 @@ _lib = None
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
-    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp")) + (
+    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

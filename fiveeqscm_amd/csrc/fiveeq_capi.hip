@@ -1896,5 +1896,105 @@ int fiveeq_score_rows_f32(int32_t n_q, int32_t n_rows, int64_t n_members, const 
                           const int32_t* steps, const double* obs, int32_t n_steps, double* misfit, int64_t ld_m, void* stream) {
     return score_rows<float>(n_q, n_rows, n_members, rows, row_stride, q_stride, steps, obs, n_steps, misfit, ld_m, stream);
 }
+// ---- forcing, energy imbalance and heat uptake from stored rows (kernel 12) --------------------------------------------------
+}  // extern "C"
+namespace {
+template <typename T>
+int forcing_rows(const fiveeq_model* model, int32_t n_rows, int64_t n, int64_t ld, const T* C, int64_t c_row, int64_t c_gas, const T* Trows,
+                 int64_t t_row, const int32_t* steps, const T* drive, int32_t n_steps, const T* q, const T* fscale, int32_t n_fext,
+                 const T* fext, T* F, T* Fg, T* Nout, double* H, int64_t ld_out, double* H_io, T* S_io, uint64_t* n_mismatch,
+                 void* stream) {
+    if (int rc = check_model(model)) return rc;
+    const int G = model->n_gas;
+    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
+    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
+    if (ld < n) return fail(FIVEEQ_E_INVALID, "ld=%lld < n_members=%lld", (long long)ld, (long long)n);
+    if ((F || Fg || Nout || H) && ld_out < n) return fail(FIVEEQ_E_INVALID, "ld_out=%lld < n_members=%lld", (long long)ld_out, (long long)n);
+    if (n_rows > 1 && c_row < n) return fail(FIVEEQ_E_INVALID, "c_row_stride=%lld < n_members=%lld", (long long)c_row, (long long)n);
+    if (G > 1 && (c_gas < 0 ? -c_gas : c_gas) < n)
+        return fail(FIVEEQ_E_INVALID, "|c_gas_stride|=%lld < n_members=%lld", (long long)(c_gas < 0 ? -c_gas : c_gas), (long long)n);
+    if (Trows && n_rows > 1 && t_row < n) return fail(FIVEEQ_E_INVALID, "t_row_stride=%lld < n_members=%lld", (long long)t_row, (long long)n);
+    if (!Trows && (Nout || H || H_io)) return fail(FIVEEQ_E_INVALID, "N / H / H_io need T_rows: T_rows is NULL");
+    if (!Trows && S_io) return fail(FIVEEQ_E_INVALID, "S_io (the replay) needs T_rows: T_rows is NULL");
+    if (S_io && !n_mismatch) return fail(FIVEEQ_E_INVALID, "S_io (the replay) needs n_mismatch: n_mismatch is NULL");
+    if (n_fext < 0 || n_fext > fiveeq::MAX_FEXT) return fail(FIVEEQ_E_INVALID, "n_fext=%d outside 0..%d", n_fext, fiveeq::MAX_FEXT);
+    if (n_fext > 0 && fscale && !fext) return fail(FIVEEQ_E_INVALID, "fscale with n_fext=%d categories needs fext: fext is NULL", n_fext);
+    if (n_fext > 0 && fext && !fscale) return fail(FIVEEQ_E_INVALID, "fext with n_fext=%d categories needs fscale: fscale is NULL", n_fext);
+    if (n_fext > 0 && !fscale) return fail(FIVEEQ_E_INVALID, "n_fext=%d without fscale and fext", n_fext);
+    if (n_steps < 1) return fail(FIVEEQ_E_INVALID, "n_steps=%d must be >= 1", n_steps);
+    if (n_rows > 0 && !C) return fail(FIVEEQ_E_INVALID, "C_rows is NULL");
+    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
+    if (!drive) return fail(FIVEEQ_E_INVALID, "drive is NULL");
+    if (!q) return fail(FIVEEQ_E_INVALID, "q is NULL");
+    const void* elem[] = {C, Trows, drive, q, fscale, fext, F, Fg, Nout, S_io};
+    for (const void* p : elem)
+        if (misaligned(p, sizeof(T))) return fail(FIVEEQ_E_INVALID, "a row pointer (%p) is not %d-byte aligned", p, (int)sizeof(T));
+    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
+    if (misaligned(H, 8) || misaligned(H_io, 8) || misaligned(n_mismatch, 8))
+        return fail(FIVEEQ_E_INVALID, "H, H_io and n_mismatch must be 8-byte aligned");
+    if (n_rows == 0) return FIVEEQ_OK;                         // no row: no output row, and the carried state stays what it is
+    const bool seq = H || H_io || S_io;
+    fiveeq::ForcRowsArgs<T> a;
+    a.n_gas = G, a.n_rows = n_rows, a.n = 0, a.n_steps = n_steps, a.n_fext = fscale ? n_fext : 0;
+    a.C = C, a.c_row = n_rows > 1 ? c_row : 0, a.c_gas = G > 1 ? c_gas : 0;
+    a.Trows = Nout || seq ? Trows : nullptr, a.t_row = n_rows > 1 ? t_row : 0;       // the T rows are read only when something needs them
+    a.steps = steps, a.drive = drive, a.q = q, a.fs = fscale, a.X = fscale ? fext : nullptr, a.ld = ld;
+    a.F = F, a.Fg = Fg, a.N = Nout, a.H = H, a.ld_out = ld_out, a.H_io = H_io, a.S_io = S_io;
+    a.n_mismatch = reinterpret_cast<unsigned long long*>(n_mismatch), a.dt = model->dt;
+    // 16-byte accesses where every lane's address of every row read or written (m a multiple of the lane's members) is aligned:
+    // the members [0, n_vec) in whole lanes; the ragged tail (fewer members than a lane's) and unaligned rows take the element
+    // accesses, in a launch of their own on the columns from n_vec
+    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
+    const bool outs = F || Fg || Nout || H;
+    const bool wide = !misaligned(C, 16) && !misaligned(a.Trows, 16) && !misaligned(F, 16) && !misaligned(Fg, 16) &&
+                      !misaligned(Nout, 16) && !misaligned(H, 16) && a.c_row % per16 == 0 && a.c_gas % per16 == 0 &&
+                      (!a.Trows || a.t_row % per16 == 0) && (!outs || ld_out % per16 == 0);
+    const int64_t n_vec = wide ? n / per16 * per16 : 0;
+    const KModel<T> km = make_kmodel<T>(model);
+    const unsigned gy = seq ? 1u : (unsigned)((n_rows + fiveeq::FORCROWS_YROWS - 1) / fiveeq::FORCROWS_YROWS);
+    if (gy > 65535u) return fail(FIVEEQ_E_INVALID, "n_rows=%d too many for one row-parallel launch: at most %d", n_rows, 65535 * fiveeq::FORCROWS_YROWS);
+    const auto launch = [&](auto vec, int64_t m0, int64_t members) {
+        fiveeq::ForcRowsArgs<T> b = a;
+        b.n = (int)members;
+        b.C += m0, b.q += m0;
+        if (b.Trows) b.Trows += m0;
+        if (b.fs) b.fs += m0;
+        if (b.F) b.F += m0;
+        if (b.Fg) b.Fg += m0;
+        if (b.N) b.N += m0;
+        if (b.H) b.H += m0;
+        if (b.H_io) b.H_io += m0;
+        if (b.S_io) b.S_io += m0;
+        const dim3 grid((unsigned)((members + fiveeq::FORCROWS_TILE<T> - 1) / fiveeq::FORCROWS_TILE<T>), gy);
+        constexpr bool VEC = decltype(vec)::value;
+        if (seq) hipLaunchKernelGGL((fiveeq::forcing_rows_kernel<T, VEC, true>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
+        else hipLaunchKernelGGL((fiveeq::forcing_rows_kernel<T, VEC, false>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
+    };
+    if (n_vec > 0) launch(std::true_type{}, 0, n_vec);
+    if (n_vec < n) launch(std::false_type{}, n_vec, n - n_vec);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int32_t fiveeq_forcing_rows_tile(int32_t elem_bytes) {
+    return elem_bytes == 8 ? fiveeq::FORCROWS_TILE<double> : elem_bytes == 4 ? fiveeq::FORCROWS_TILE<float> : 0;
+}
+int fiveeq_forcing_rows_f64(const fiveeq_model* model, int32_t n_rows, int64_t n_members, int64_t ld, const double* C_rows,
+                            int64_t c_row_stride, int64_t c_gas_stride, const double* T_rows, int64_t t_row_stride, const int32_t* steps,
+                            const double* drive, int32_t n_steps, const double* q, const double* fscale, int32_t n_fext,
+                            const double* fext, double* F, double* F_gas, double* N, double* H, int64_t ld_out, double* H_io,
+                            double* S_io, uint64_t* n_mismatch, void* stream) {
+    return forcing_rows<double>(model, n_rows, n_members, ld, C_rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive, n_steps,
+                                q, fscale, n_fext, fext, F, F_gas, N, H, ld_out, H_io, S_io, n_mismatch, stream);
+}
+int fiveeq_forcing_rows_f32(const fiveeq_model* model, int32_t n_rows, int64_t n_members, int64_t ld, const float* C_rows,
+                            int64_t c_row_stride, int64_t c_gas_stride, const float* T_rows, int64_t t_row_stride, const int32_t* steps,
+                            const float* drive, int32_t n_steps, const float* q, const float* fscale, int32_t n_fext, const float* fext,
+                            float* F, float* F_gas, float* N, double* H, int64_t ld_out, double* H_io, float* S_io,
+                            uint64_t* n_mismatch, void* stream) {
+    return forcing_rows<float>(model, n_rows, n_members, ld, C_rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive, n_steps,
+                               q, fscale, n_fext, fext, F, F_gas, N, H, ld_out, H_io, S_io, n_mismatch, stream);
+}
 
 }  // extern "C"

@@ -32,6 +32,26 @@ namespace fiveeq {
 //     not the state, is what bounds T in fp32.
 // Against 50-digit arithmetic over the 24 golden members: C 2.9e-6 -> 1.4e-7, T 1.7e-5 -> 7e-7 (profiles/r06/fp32_compensated.txt).
 // It is its own arithmetic: NOT bit-identical to the default forms, and the per-step kernels (state in HBM) do not have it.
+// THE FORCING OF ONE GAS from its concentration (step_forc): f2 (C - C0), then the f1 log and the f3 sqrt term, each behind a
+// wave-uniform test of its coefficient (terms whose coefficient is zero are skipped) and the C > 0 guard — for C <= 0 and NaN the
+// log term is dropped and sqrt C reads 0.  Written ONCE: gas_step() below calls it for every non-compensated form, and the
+// forcing-rows pass (fiveeq_forcrows.hpp) recomputes a run's forcing from its stored C rows with it, so the two cannot drift
+// apart.  Scalar lanes and packed lanes spell the selects differently and give the same bits per member.
+template <typename V>
+__device__ __forceinline__ V gas_forcing(const KGas<typename Lane<V>::S>& kg, const V Cg) {
+    using S = typename Lane<V>::S;
+    const auto pos = fe_gt0(Cg);
+    V Fg = kg.f2 * (Cg - kg.C0);
+    if constexpr (Lane<V>::W == 1) {
+        if (kg.f1 != S(0)) Fg = pos ? fe_fma(kg.f1, fe_log(pos ? Cg * kg.inv_C0 : S(1)), Fg) : Fg;
+        if (kg.f3 != S(0)) Fg = fe_fma(kg.f3, (pos ? fe_sqrt(pos ? Cg : S(1)) : S(0)) - kg.sqrtC0, Fg);
+    } else {
+        if (kg.f1 != S(0)) Fg = fe_sel(pos, fma3<V>(kg.f1, fe_log(fe_sel(pos, Cg * kg.inv_C0, (V)S(1))), Fg), Fg);
+        if (kg.f3 != S(0)) Fg = fma3<V>(kg.f3, fe_sel(pos, fe_sqrt(fe_sel(pos, Cg, (V)S(1))), (V)S(0)) - kg.sqrtC0, Fg);
+    }
+    return Fg;
+}
+
 template <typename V, typename L, int g, bool INV, bool COMP = false>
 __device__ __forceinline__ V gas_step(const KModel<typename Lane<V>::S>& km, const KGas<typename Lane<V>::S>& kg,
                                       const typename Lane<V>::S* __restrict__ drv, const V (&rr)[3 * L::G], const V T_old,
@@ -92,11 +112,10 @@ __device__ __forceinline__ V gas_step(const KModel<typename Lane<V>::S>& km, con
     }
     const V Cg = kg.C0 + sumN;
     if constexpr (!INV) out[g] = Cg;
-    // --- step_forc (terms whose coefficient is zero are skipped: wave-uniform branch) ---
-    const auto pos = fe_gt0(Cg);
-    V Fg = kg.f2 * (Cg - kg.C0);
+    // --- step_forc: gas_forcing() above; the compensated form takes it from the excess sumN instead ---
     if constexpr (COMP) {
-        Fg = kg.f2 * sumN;
+        const auto pos = fe_gt0(Cg);
+        V Fg = kg.f2 * sumN;
         if (kg.f1 != S(0)) {
             const V x = sumN * kg.inv_C0;                                          // C / C0 - 1, to the precision of the excess
             const V u = fe_sel(pos, (V)S(1) + x, (V)S(1));
@@ -107,14 +126,10 @@ __device__ __forceinline__ V gas_step(const KModel<typename Lane<V>::S>& km, con
             const V den = fe_sqrt(fe_sel(pos, Cg, (V)S(1))) + kg.sqrtC0;
             Fg = fma3<V>(kg.f3, fe_sel(pos, sumN * fe_rcp(den), (V)(-kg.sqrtC0)), Fg);
         }
-    } else if constexpr (Lane<V>::W == 1) {
-        if (kg.f1 != S(0)) Fg = pos ? fe_fma(kg.f1, fe_log(pos ? Cg * kg.inv_C0 : S(1)), Fg) : Fg;
-        if (kg.f3 != S(0)) Fg = fe_fma(kg.f3, (pos ? fe_sqrt(pos ? Cg : S(1)) : S(0)) - kg.sqrtC0, Fg);
+        return Fg;
     } else {
-        if (kg.f1 != S(0)) Fg = fe_sel(pos, fma3<V>(kg.f1, fe_log(fe_sel(pos, Cg * kg.inv_C0, (V)S(1))), Fg), Fg);
-        if (kg.f3 != S(0)) Fg = fma3<V>(kg.f3, fe_sel(pos, fe_sqrt(fe_sel(pos, Cg, (V)S(1))), (V)S(0)) - kg.sqrtC0, Fg);
+        return gas_forcing<V>(kg, Cg);
     }
-    return Fg;
 }
 
 // FORC = true (round 8) is the form with PER-MEMBER FORCING SCALES: the member carries G + K factors, sg_g per gas and sx_k per

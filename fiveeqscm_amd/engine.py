@@ -1075,6 +1075,68 @@ class EnsembleEngine(CheckpointMixin):
             total = total + chi2[key]
         return Score(misfit, chi2, total, {key: records[key].n_obs for key in order})
 
+    def forcing_rows(self, want=("F",), rows=None, scenario=None, replay=False):
+        """The effective radiative forcing F, its split by gas F_gas, the energy imbalance N = F - T / (q0 + q1) and the
+        cumulated heat uptake H (W yr m-2; diagnose.W_YR_M2_TO_ZJ converts) of the STORED rows — diagnose.forcing_rows wired to
+        this engine's C, T, out_steps, q, fscale, the scenario's drive and category table, dt and the initial box temperatures
+        (include/fiveeq.h, "FORCING ROWS").  One streaming HIP pass that recomputes F with the device function the stepping
+        kernels call: for every mode and precision, F is bit for bit what the run formed and dropped.
+        want: any of "F", "F_gas", "N", "H".  rows: a slice of the stored rows (default: all).  With the scenario axis,
+        scenario=None covers every scenario (one launch each) and the results carry a leading [S] axis (replay_mismatches: a
+        list of S counts); an index covers that scenario.
+        replay=True also repeats the thermal step on the diagnosed F from the initial box temperatures and returns
+        replay_mismatches, the number of (row, member) whose replayed T differs in bits from the stored T (NaN equal to NaN), and
+        S_end: 0 mismatches prove that the diagnosed F is the stepping kernel's F, and tell a user that stored rows belong to
+        these parameters.  It needs every step from 0 stored.  "H" needs stored rows of consecutive steps (ValueError
+        otherwise: a partial integral would be silent).
+        Where the rows go: constrain.score_rows(res.H, steps, Observations...) against a heat-content record (res.F against an
+        assessed forcing range alike); res.F[k:k + 1] into gather_summary / gather_weighted_summary; any row into drivers().
+        ValueError without stored concentrations, for a concentration-driven engine (its C rows are emissions) and for
+        compensated=True.  Joins unjoined per-step streams first.  Reads the engine; writes nothing into it.  Returns
+        diagnose.ForcingRows."""
+        from .diagnose import ForcingRows, forcing_rows
+        if self.concentration_driven:
+            raise ValueError("forcing_rows: a concentration-driven engine stores the diagnosed EMISSIONS in its C rows, not "
+                             "concentrations; the forcing of its target concentrations is not diagnosed here")
+        if self.compensated:
+            raise ValueError("forcing_rows: compensated=True takes its forcing from the UNROUNDED excess C - C0, which is not stored; "
+                             "the stored C rows cannot reproduce that F")
+        if self.C is None or self.T is None or self.n_rows == 0:
+            raise ValueError("forcing_rows: no stored concentrations (store_concentrations=False or no output_steps): F is "
+                             "recomputed from the stored C rows")
+        sel = slice(None) if rows is None else rows
+        if not isinstance(sel, slice) or sel.step not in (None, 1):
+            raise ValueError("rows: want a slice of the stored rows with step 1 (or None for all)")
+        steps = self.out_steps[sel]
+        if replay and (steps.size == 0 or steps[0] != 0 or np.any(np.diff(steps) != 1)):
+            raise ValueError("forcing_rows(replay=True) repeats the run from its initial state: it needs every step from 0 stored "
+                             f"and rows from the first (stored steps {steps[:3].tolist()}..: output_steps is a subset, or rows= "
+                             "starts later)")
+        if self._ps_unjoined:
+            self.join()
+
+        def one(sc):
+            pick = (lambda t: t) if sc is None else (lambda t: t[sc])
+            S0 = None
+            if replay:
+                S0 = torch.zeros((2, self.n_members), dtype=self.dtype, device=self.device)
+                if self._S0 is not None:
+                    S0.copy_(torch.from_numpy(np.ascontiguousarray(self._S0 if sc is None else self._S0[sc])).to(self.dtype))
+            with torch.cuda.device(self.device):
+                return forcing_rows(pick(self.C)[sel], steps, self.params, q=self.q, F_ext=pick(self.drive), dt=self.dt,
+                                    T_rows=pick(self.T)[sel], fscale=self.fscale,
+                                    X=None if self.fext is None else pick(self.fext), want=want, S_begin=S0)
+
+        if not self.scenario_axis:
+            return one(None)
+        if scenario is not None:
+            return one(self._scen(scenario))
+        parts = [one(s) for s in range(self.n_scenarios)]
+        stack = lambda name: (None if getattr(parts[0], name) is None                                    # noqa: E731
+                              else torch.stack([getattr(p, name) for p in parts]))
+        return ForcingRows(stack("F"), stack("F_gas"), stack("N"), stack("H"), stack("S_end"),
+                           [p.replay_mismatches for p in parts] if replay else None)
+
     def parameter_rows(self, names=None):
         """(names, rows [K, N]) — this shard's per-member parameters as device rows in the engine's dtype, in the order r0[g],
         rC[g], rT[g] per gas, q[0], q[1], ECS, TCR (params.ecs_tcr of the q rows) and, with forcing=, f_scale[g] and

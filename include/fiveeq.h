@@ -791,6 +791,58 @@ int fiveeq_score_rows_f32(int32_t n_q, int32_t n_rows, int64_t n_members, const 
                           int64_t q_stride, const int32_t *steps, const double *obs, int32_t n_steps, double *misfit,
                           int64_t ld_m, void *stream);
 
+/* new — FORCING ROWS: the effective radiative forcing F, its split by gas F_g, the top-of-atmosphere energy imbalance N and the
+ * cumulated heat uptake H of a run, DIAGNOSED FROM ITS STORED ROWS, for runs of every mode and precision — DESIGN.md section
+ * 3.17; host side: fiveeqscm_amd/diagnose.py forcing_rows, EnsembleEngine.forcing_rows.  Additive: no symbol above changes,
+ * FIVEEQ_ABI_VERSION stays 13, fiveeq_sizeof_model() stays 448.
+ *
+ * ONE streaming pass.  The concentration of row k, gas g, member m is C_rows[k * c_row_stride + g * c_gas_stride + m] (the C
+ * rows [n_rows][G][ld] of a run: c_row_stride = G * ld, c_gas_stride = ld), the warming T_rows[k * t_row_stride + m].  steps dev
+ * [n_rows] int32: entry k is the model step row k holds.  drive dev [n_steps][8] as in the stepping entry points (F_ext at
+ * [6]).  q dev [2][ld].  fscale dev [G + n_fext][ld] (gas rows first) and fext dev [n_steps][fiveeq_max_fext()] as in FORCING
+ * SCALES; both NULL (n_fext 0) for a run without forcing scales.  All in the precision of the entry point.
+ * DEFINITION.  For the rows in row order, t = steps[k], per member, every operation rounded on its own in the rows' precision:
+ *     F_g = f2 (C_g - C0) + f1 ln(C_g / C0) + f3 (sqrt C_g - sqrt C0)      the device function the stepping kernels call: the
+ *                                                                         same coefficient tests, the same C > 0 guard
+ *     F   = F_ext[t];  F = fma(sx_k, X[t][k], F), k < n_fext;  F = fma(sg_g, F_g, F)     with fscale;    F = F + F_g   without
+ *     N   = F - T / (q0 + q1)                 IEEE division.  The two-box model's equilibrium is T = (q0 + q1) F: its feedback
+ *                                             parameter is 1 / (q0 + q1), and N its top-of-atmosphere imbalance
+ *     H   = H + dt * (double)N                fp64 in both precisions, W yr m-2; no fma
+ *     S_j = fma(em1_d[j], fma(-q_j, F, S_j), S_j);  T' = S_0 + S_1               THE REPLAY, with S_io only
+ * — so F is, bit for bit, the F the run's stepping kernel formed at that step (every non-compensated, emission-driven form),
+ * and the replay proves it: *n_mismatch is INCREASED by the number of (row, member) whose T' differs in bits from the stored T
+ * (NaN equal to NaN; the caller zeroes it).
+ * OUTPUTS, each nullable, written for columns [0, n_members) only: F [n_rows][ld_out], F_gas [n_rows][G][ld_out], N
+ * [n_rows][ld_out] in the rows' precision, H [n_rows][ld_out] fp64 (H after row k).  CARRIED STATE, in / out and nullable: H_io
+ * [ld] fp64 (H before the first row; NULL with H: 0, and nothing is handed back) and S_io [2][ld] (the boxes before the first
+ * row; asks for the replay, needs n_mismatch).  H and the replay take the rows as consecutive model steps: THE CALLER OWES
+ * that, and steps inside [0, n_steps) (steps is device memory: diagnose.forcing_rows checks; the kernel clamps a step into the
+ * tables and never reads outside them).
+ * CONSEQUENCES: rows [0, k) in one call and rows [k, n) in a second with H_io / S_io carried give the bits of one call; any
+ * member sub-range gives the bits of the whole; launch shape, strides and alignment cannot change a bit (rows and outputs
+ * aligned to 16 bytes with strides a multiple of 16 bytes get 16-byte accesses — an optimisation, not a contract).  Without H,
+ * H_io and S_io the rows are independent and are spread over the grid; with one of them a lane carries its members through
+ * all rows.  Nothing is allocated, nothing synchronises.  The pass moves sizeof(element) * (G + [T read]) + the outputs asked
+ * for per member-row; the T rows are read only for N, H, H_io or S_io.
+ * FIVEEQ_E_UNSUPPORTED for a pool layout outside fiveeq_layout_supported.  FIVEEQ_E_INVALID, before anything is launched and
+ * with fiveeq_last_error() naming the argument, for: an invalid model; n_rows < 0; n_members < 1 or >= 2^31; ld < n_members;
+ * ld_out < n_members with an output; c_row_stride < n_members with n_rows > 1; |c_gas_stride| < n_members with G > 1;
+ * t_row_stride < n_members with T_rows and n_rows > 1; N, H, H_io or S_io without T_rows; S_io without n_mismatch; n_fext
+ * outside 0..fiveeq_max_fext(); fscale without fext or fext without fscale when n_fext > 0; n_fext > 0 with neither; n_steps < 1;
+ * a NULL C_rows, steps, drive or q (C_rows and steps may be NULL with n_rows == 0); a pointer not aligned to its element. */
+/* members per workgroup for rows of elem_bytes (8 or 4; 0 for anything else), for tests that pick their sizes at its edges */
+int32_t fiveeq_forcing_rows_tile(int32_t elem_bytes);
+int fiveeq_forcing_rows_f64(const fiveeq_model *model, int32_t n_rows, int64_t n_members, int64_t ld, const double *C_rows,
+                            int64_t c_row_stride, int64_t c_gas_stride, const double *T_rows, int64_t t_row_stride,
+                            const int32_t *steps, const double *drive, int32_t n_steps, const double *q, const double *fscale,
+                            int32_t n_fext, const double *fext, double *F, double *F_gas, double *N, double *H, int64_t ld_out,
+                            double *H_io, double *S_io, uint64_t *n_mismatch, void *stream);
+int fiveeq_forcing_rows_f32(const fiveeq_model *model, int32_t n_rows, int64_t n_members, int64_t ld, const float *C_rows,
+                            int64_t c_row_stride, int64_t c_gas_stride, const float *T_rows, int64_t t_row_stride,
+                            const int32_t *steps, const float *drive, int32_t n_steps, const float *q, const float *fscale,
+                            int32_t n_fext, const float *fext, float *F, float *F_gas, float *N, double *H, int64_t ld_out,
+                            double *H_io, float *S_io, uint64_t *n_mismatch, void *stream);
+
 /* new — SINGLE-VALUED PARAMETER ROWS: the per-step form without the loads of the parameter rows whose members all hold one value
  * — DESIGN.md section 3.16; host side: EnsembleEngine(uniform_rows=).  Additive: no symbol above changes, FIVEEQ_ABI_VERSION
  * stays 13, fiveeq_sizeof_model() stays 448.
