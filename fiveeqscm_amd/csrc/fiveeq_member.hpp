@@ -139,13 +139,26 @@ __device__ __forceinline__ V gas_step(const KModel<typename Lane<V>::S>& km, con
 // K = 0 (or an all-zero table) give the bits of the plain step.  Scale j of the lane is fs[j * fs_stride] (gas rows first:
 // registers with stride 1, or a lane-private LDS slot), xr the step's table record (wave-uniform), n_fext = K is
 // wave-uniform: the category loop is scalar branches.  Nothing else of the step differs; FORC = false is the code as it was.
+// AFTER-GAS HOOK (round 18): after_gas(GasTag<g>{}) is called once gas g's pools R[off(g) ..], its out[g] and its share of F
+// are final and before the next gas's arithmetic starts — the per-step kernels store that gas's rows there (step_body).  The
+// hook touches no value of the step: the arithmetic, its order and its roundings are those of the unhooked call, and the
+// default NoGasHook compiles to nothing (every kernel that does not pass one keeps its machine code).
 constexpr int MAX_FEXT = 4;
-template <typename V, typename L, bool INV, bool COMP, bool FORC = false>
+template <int g>
+struct GasTag {
+    static constexpr int value = g;
+};
+struct NoGasHook {
+    template <int g>
+    __device__ __forceinline__ void operator()(GasTag<g>) const {}
+};
+template <typename V, typename L, bool INV, bool COMP, bool FORC = false, typename Hook = NoGasHook>
 __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& km, const typename Lane<V>::S* __restrict__ drv,
                                             const V (&rr)[3 * L::G], const V (&qq)[2],
                                             V (&R)[L::SP], V (&S)[2], V (&out)[L::G], V& Tnew, V (&cum)[L::G],
                                             V (&Rlo)[L::SP], const V* fs = nullptr, const int fs_stride = 1,
-                                            const typename Lane<V>::S* xr = nullptr, const int n_fext = 0) {
+                                            const typename Lane<V>::S* xr = nullptr, const int n_fext = 0,
+                                            const Hook after_gas = Hook{}) {
     static_assert(!FORC || (!INV && !COMP), "the forcing scales are carried by the plain forward form only");
     const V T_old = S[0] + S[1];
     V F = (V)drv[6];
@@ -161,17 +174,20 @@ __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& k
     const V F0 = gas_step<V, L, 0, INV, COMP>(km, km.gas[0], drv, rr, T_old, R, out, cum, Rlo);
     if constexpr (FORC) F = fe_fma(fs[0 * fs_stride], F0, F);
     else F += F0;
+    after_gas(GasTag<0>{});
     if constexpr (L::G > 1) {
         asm volatile("" ::: "memory");
         const V F1 = gas_step<V, L, 1, INV, COMP>(km, km.gas[1], drv, rr, T_old, R, out, cum, Rlo);
         if constexpr (FORC) F = fe_fma(fs[1 * fs_stride], F1, F);
         else F += F1;
+        after_gas(GasTag<1>{});
     }
     if constexpr (L::G > 2) {
         asm volatile("" ::: "memory");
         const V F2 = gas_step<V, L, 2, INV, COMP>(km, km.gas[2], drv, rr, T_old, R, out, cum, Rlo);
         if constexpr (FORC) F = fe_fma(fs[2 * fs_stride], F2, F);
         else F += F2;
+        after_gas(GasTag<2>{});
     }
     // --- step_temp: S + em1_d (S - q F) ------------------------------------------------
 #pragma unroll

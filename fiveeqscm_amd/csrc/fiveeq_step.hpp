@@ -72,13 +72,19 @@ __device__ __forceinline__ void step_body(
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     constexpr bool NTT = true;                    // the stored C / T rows: written once, never read by a stepping kernel
+    // SPREAD (round 18): the fp64 kernels load their rows in order of use and store each row as soon as its value is final
+    // (below).  The fp32 kernels keep the block schedule — all loads, all arithmetic, all stores: with the spread one they
+    // measured 7.1 % SLOWER per step at 1M members (profiles/r18/step_schedule_ab.txt, section B).
+    constexpr bool SPREAD = sizeof(T) == 8;
     static_assert(!FORC || (!BINS && !NT), "the forcing scales: no histogram ring, default row policy");
     static_assert(!UNI || (!BINS && !MISFIT && !FORC), "the single-valued rows: the plain forward form only");
     __shared__ T drv[DRIVE_STRIDE];
     // idle tail lanes load a valid (aligned) member and store nothing
-    const auto [m, active, full, mm] = lane_span<W, FIVEEQ_STEP_BLOCK, PARK_LAST>(n);
+    const LaneSpan span = lane_span<W, FIVEEQ_STEP_BLOCK, PARK_LAST>(n);
+    const int64_t m = span.m, mm = span.mm;       // (plain locals: the row lambdas below capture them)
+    const bool active = span.active, full = span.full;
     // Issue order matters for the workgroup's critical path: first the (tiny) shared loads, then
-    // all 19 row loads, and only then the LDS writes + barrier, so the staging round trip is
+    // all row loads, and only then the LDS writes + barrier, so the staging round trip is
     // overlapped with the row round trip instead of preceding it (+1.3 % at 1M members, neutral
     // elsewhere: profiles/r01/ab_variants.txt).
     __shared__ KModel<T> km_s;
@@ -91,53 +97,84 @@ __device__ __forceinline__ void step_body(
     const KModel<T>& kmr = km_s;
 
     V rr[3 * L::G], qq[2], Rv[L::SP], Sv[2], Cv[L::G];
+    V fs[FORC ? L::G + MAX_FEXT : 1];             // FORC: the lane's scales, gas rows first (rows past n_fext are never read)
+    // one parameter row: the load, or (UNI, bit set) the single value from the kernel arguments
+    const auto par_row = [&](const T* __restrict__ rows, const int k, const int bit) -> V {
+        if constexpr (UNI) {
+            if (uni.mask & (1u << bit)) return (V)uni.val[bit];
+        }
+        return load_row<V, NT>(rows + k * ld + mm);
+    };
+    if constexpr (SPREAD) {
+        // In order of use: S (T_old), [FORC: the category scales, which open F], per gas its pools, its r0 / rC / rT and [FORC] its
+        // scale, q last — so that gas 0 can start when ITS rows have landed, behind a partial vmcnt wait, with the later rows in flight.
 #pragma unroll
-    for (int k = 0; k < L::SP; ++k) Rv[k] = load_row<V, NT>(R + k * ld + mm);
+        for (int k = 0; k < 2; ++k) Sv[k] = load_row<V, NT>(S + k * ld + mm);
+        if constexpr (FORC) {
 #pragma unroll
-    for (int k = 0; k < 2; ++k) Sv[k] = load_row<V, NT>(S + k * ld + mm);
-    if constexpr (UNI) {
-#pragma unroll
-        for (int k = 0; k < 3 * L::G; ++k) {
-            if (uni.mask & (1u << k)) rr[k] = (V)uni.val[k];
-            else rr[k] = load_row<V, NT>(r + k * ld + mm);
+            for (int k = L::G; k < L::G + MAX_FEXT; ++k) fs[k] = k < L::G + n_fext ? load_row<V, NT>(fscale + k * ld + mm) : (V)T(0);
         }
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (uni.mask & (1u << (3 * L::G + k))) qq[k] = (V)uni.val[3 * L::G + k];
-            else qq[k] = load_row<V, NT>(q + k * ld + mm);
+        for (int g = 0; g < L::G; ++g) {
+#pragma unroll
+            for (int i = 0; i < L::pools(g); ++i) Rv[L::off(g) + i] = load_row<V, NT>(R + (L::off(g) + i) * ld + mm);
+#pragma unroll
+            for (int k = 3 * g; k < 3 * g + 3; ++k) rr[k] = par_row(r, k, k);
+            if constexpr (FORC) fs[g] = load_row<V, NT>(fscale + g * ld + mm);
         }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) qq[k] = par_row(q, k, 3 * L::G + k);
     } else {
 #pragma unroll
-        for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_row<V, NT>(r + k * ld + mm);
+        for (int k = 0; k < L::SP; ++k) Rv[k] = load_row<V, NT>(R + k * ld + mm);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) qq[k] = load_row<V, NT>(q + k * ld + mm);
-    }
-    V fs[FORC ? L::G + MAX_FEXT : 1];             // FORC: the lane's scales, gas rows first (rows past n_fext are never read)
-    if constexpr (FORC) {
+        for (int k = 0; k < 2; ++k) Sv[k] = load_row<V, NT>(S + k * ld + mm);
 #pragma unroll
-        for (int k = 0; k < L::G + MAX_FEXT; ++k) fs[k] = k < L::G + n_fext ? load_row<V, NT>(fscale + k * ld + mm) : (V)T(0);
+        for (int k = 0; k < 3 * L::G; ++k) rr[k] = par_row(r, k, k);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) qq[k] = par_row(q, k, 3 * L::G + k);
+        if constexpr (FORC) {
+#pragma unroll
+            for (int k = 0; k < L::G + MAX_FEXT; ++k) fs[k] = k < L::G + n_fext ? load_row<V, NT>(fscale + k * ld + mm) : (V)T(0);
+        }
     }
 
     if (threadIdx.x < NW) reinterpret_cast<T*>(&km_s)[threadIdx.x] = stage_v;
     if (threadIdx.x < DRIVE_STRIDE) drv[threadIdx.x] = drv_v;
     __syncthreads();
 
-    V Tn = (V)T(0);
-    if constexpr (FORC) {
-        V no_cum[L::G], no_Rlo[L::SP];            // never touched: INV = COMP = false
-        member_step<V, L, false, false, true>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, 1,
-                                              fext + (int64_t)t * MAX_FEXT, n_fext);
-    } else {
-        member_step<V, L>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn);
-    }
-    if (active) {
+    const int row = __builtin_amdgcn_readfirstlane((int)drv[7]);         // wave-uniform: scalar test + offsets
+    const bool stored = row >= 0 && row < n_rows;
+    // A row is stored AS SOON AS ITS VALUE IS FINAL: gas g's pools and, on a stored step, its C row right after gas g
+    // (member_step's after-gas hook), before the next gas's arithmetic — the wave's writes are spread over its lifetime and
+    // the registers die early (fp64 4 + 1 + 1: 72 -> 68 VGPRs).  With the loads in order of use: ratio 0.9869 (-1.3 %) per step
+    // at 1M fp64 members, ranges disjoint; either half alone (0.994, 1.002) does not separate from the run-to-run spread
+    // (profiles/r18/step_schedule_ab.txt, sections A and C).
+    const auto store_gas = [&](auto gas) {
+        constexpr int g = decltype(gas)::value;
+        if (active) {
 #pragma unroll
-        for (int k = 0; k < L::SP; ++k) store_row<NT>(R + k * ld + m, Rv[k], full);
+            for (int i = 0; i < L::pools(g); ++i) store_row<NT>(R + (L::off(g) + i) * ld + m, Rv[L::off(g) + i], full);
+            if (stored && C_traj != nullptr) store_row<NTT>(C_traj + ((int64_t)row * L::G + g) * ld + m, Cv[g], full);
+        }
+    };
+    V Tn = (V)T(0);
+    V no_cum[L::G], no_Rlo[L::SP];                // never touched: INV = COMP = false
+    if constexpr (SPREAD)
+        member_step<V, L, false, false, FORC>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, 1,
+                                              FORC ? fext + (int64_t)t * MAX_FEXT : nullptr, n_fext, store_gas);
+    else
+        member_step<V, L, false, false, FORC>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, 1,
+                                              FORC ? fext + (int64_t)t * MAX_FEXT : nullptr, n_fext);
+    if (active) {
+        if constexpr (!SPREAD) {
+#pragma unroll
+            for (int k = 0; k < L::SP; ++k) store_row<NT>(R + k * ld + m, Rv[k], full);
+        }
 #pragma unroll
         for (int k = 0; k < 2; ++k) store_row<NT>(S + k * ld + m, Sv[k], full);
-        const int row = __builtin_amdgcn_readfirstlane((int)drv[7]);     // wave-uniform: scalar test + offsets
-        if (row >= 0 && row < n_rows) {
-            if (C_traj != nullptr) {
+        if (stored) {
+            if (!SPREAD && C_traj != nullptr) {
                 T* c = C_traj + (int64_t)row * L::G * ld + m;
 #pragma unroll
                 for (int g = 0; g < L::G; ++g) store_row<NTT>(c + g * ld, Cv[g], full);
