@@ -72,7 +72,8 @@ struct Layout {
 //   x = k ln2 + r, |r| <= ln2/2 ;  expm1(x) = 2^k (expm1 r) + (2^k - 1)
 // with expm1(r) = r + r^2 Q(r), Q a degree-10 near-minimax polynomial (8.5e-19 relative).  For
 // k = 0 the result is expm1(r) itself, so small arguments (the tau ~ 1e6 yr pool: x ~ -1e-6)
-// keep full RELATIVE accuracy.
+// keep full RELATIVE accuracy.  A NaN argument: fmax / fmin return their other operand, so expm1 and exp (both precisions)
+// evaluate at a clamp (expm1: -1, exp: exp of the lower clamp); log, sqrt and rcp return NaN.
 // ---------------------------------------------------------------------------------
 // expm1(r) on |r| <= ln2/2 as r + r^2 Q(r): shared by fe_expm1_neg and fe_exp.  Q is the degree-10
 // interpolant of (expm1(r) - r)/r^2 at the Chebyshev nodes of the interval (computed in 60-digit
@@ -116,7 +117,8 @@ __device__ __forceinline__ double fe_expm1_neg(double x) {
 //     v_rndne / v_cvt / v_ldexp; the argument is clamped at -87 so that 2^k stays a normal float (expm1 is -1 below -17);
 //   * exp (the alpha closure) uses the hardware 2^t (v_exp_f32, 1 ulp) on t = x log2(e) with the product's rounding
 //     error and the low part of log2(e) folded back in: exp(x) = 2^t (1 + lo ln2), six instructions instead of fourteen.
-// All within 2 ulp(float) of libm over the model's ranges (tests/test_engine_gpu.py, through fiveeq_math_probe_f32).
+// All within 2 ulp(float) of the exact value over the model's ranges (tests/test_engine_gpu.py on random draws and
+// tests/test_math_edges_gpu.py at every reduction tie, split, clamp and range end, through fiveeq_math_probe_f32).
 __device__ __forceinline__ float fe_expm1_reduced(float r) {
     float q = 0x1.6d10fcp-10f;
     q = __builtin_fmaf(q, r, 0x1.120b62p-7f);
