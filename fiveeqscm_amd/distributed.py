@@ -15,13 +15,21 @@ The summary is four HIP passes over device rows (include/fiveeq.h "END-OF-RUN SU
 device ranges, selection with ballot counts and LDS compaction, radix pick) with the small bookkeeping between them done
 on the host in NumPy — the rows are read three times at memory speed and nothing else of their size exists.  Rows on the
 host are refused: there is no CPU path (a torch-ops restatement for tests: oracle/summary_host.py).
+The unweighted summary (_device_summary) and the weighted one (gather_weighted_summary) are two short drivers over the same
+stages, each a function below that a CPU test can call on its own: _histogram_stage, _selection_plan (with _pack_bin_mask),
+_upload_plan, _select_and_pick (with _candidates_to_root), _first_lost and _fix_up.
 `torch.distributed` backend "nccl" is RCCL on ROCm; tests/test_distributed.py runs the same host logic over gloo with the
 passes replaced by their NumPy restatement.  The reference has no distributed code at all.
 """
+import contextlib
+import ctypes
 import os
+from fractions import Fraction
 
 import numpy as np
 import torch
+
+from . import _capi            # (importing it binds nothing: the library is opened by _capi.load(), in _lib_and_stream)
 
 
 def shard_bounds(n_total, rank, world):
@@ -194,9 +202,6 @@ def exact_percentiles(rows, percentiles, gmin, gmax, n_total, dst=0, group=None,
 def _lib_and_stream(rows):
     """(library, _capi, ctypes, stream) for rows on a GPU.  (tests/test_distributed.py replaces this function to run the host
     side of the summary on CPU tensors against the NumPy restatement of the passes, oracle/summary_passes.py.)"""
-    import ctypes
-
-    from . import _capi
     lib = _capi.load()
     return lib, _capi, ctypes, ctypes.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
 
@@ -207,8 +212,12 @@ def _passes_apply(rows):
 
 
 def _on(device):
-    import contextlib
     return torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+
+
+def _ptr(t, off=0):
+    """Tensor `t`'s address plus `off` bytes, as the C ABI takes it."""
+    return ctypes.c_void_p(t.data_ptr() + off)
 
 
 def _all_reduce(dist, group, x, op):
@@ -233,6 +242,9 @@ def _all_gather_np(dist, group, world, arr, device):
     return torch.stack(parts).cpu().numpy()
 
 
+_EMPTY_ROW_SUMS = (0.0, 0.0, float("inf"), float("-inf"))    # (sum, sum of squares, min, max) of a row without members
+
+
 def device_row_sums(rows, out=None):
     """rows [K, n] on the GPU -> device tensor [K, 4] fp64 = (sum, sum of squares, min, max) per row: ONE pass of
     fiveeq_row_moments_* (16-byte loads, fixed summation order: the same bits every run).  min / max ignore NaNs, the sums
@@ -242,7 +254,7 @@ def device_row_sums(rows, out=None):
     if n == 0:                                         # an empty shard (fewer members than ranks): the neutral record
         if out is None:
             out = torch.empty((K, 4), dtype=torch.float64, device=rows.device)
-        out.copy_(torch.tensor([0.0, 0.0, float("inf"), float("-inf")], dtype=torch.float64).expand(K, 4))
+        out.copy_(torch.tensor(_EMPTY_ROW_SUMS, dtype=torch.float64).expand(K, 4))
         return out
     chunks = int(lib.fiveeq_row_moments_chunks(K, n))
     work = torch.empty((K * chunks + (K if out is None else 0)) * 4, dtype=torch.float64, device=rows.device)
@@ -255,6 +267,236 @@ def device_row_sums(rows, out=None):
     return out
 
 
+# ---- the stages both summaries are made of -----------------------------------------------------------------------------
+class _Run:
+    """What the stages of ONE summary call share: the process group as _dist sees it, the library behind the switch
+    (_lib_and_stream, looked up here, at call time), the rows' device, and the pass family ("" unweighted, "w" weighted)
+    and dtype suffix that name its entry points."""
+
+    def __init__(self, rows, group, family):
+        self.dist, self.rank, self.world, self.exchange = _dist(group)
+        self.lib, self.capi, _, self.st = _lib_and_stream(rows)
+        self.group, self.dev, self.family = group, rows.device, family
+        self.sfx = "f64" if rows.dtype == torch.float64 else "f32"
+        self.host_wire = self.exchange and self.dist.get_backend(group) == "gloo"
+
+    def launch(self, name, *args):
+        """fiveeq_<family><name>_<f64|f32>(*args, stream); a failed pass raises.  (The caller is inside _on(self.dev).)"""
+        self.capi.check(self.lib, getattr(self.lib, f"fiveeq_{self.family}{name}_{self.sfx}")(*args, self.st))
+
+    def all_gather_np(self, arr):
+        return _all_gather_np(self.dist, self.group, self.world, arr, self.dev)
+
+
+def _alloc_head(K, n_bins, rec_words, dev):
+    """ONE zeroed device buffer for everything that comes back after the histogram: the per-bin counts [K, n_bins] int64, then
+    the moments pass's records [K, rec_words] of 8-byte words.  Returns (head, counts, records), the last two views."""
+    head = torch.zeros(K * n_bins + K * rec_words, dtype=torch.int64, device=dev)
+    return head, head[:K * n_bins].view(K, n_bins), head[K * n_bins:].view(K, rec_words)
+
+
+def _histogram_stage(run, rows, weights, ranges, head, counts, stats):
+    """Pass 2 and what follows it at once: the ranged histogram of this rank's rows into `counts` (the weight per bin when
+    `weights` is given: integer sums, so the all-reduce is exact), the SUM all-reduce over the ranks, THE device-to-host copy
+    of the summary's first half (`head`: counts and records together), and the initial `stats`.  Returns (counts [K, n_bins]
+    int64, records [K, rec_words] int64) as NumPy views of that one copy."""
+    K, n_bins = counts.shape
+    n_local = rows.shape[1]
+    if n_local > 0:
+        with _on(run.dev):
+            run.launch("hist_rows_ranged", K, n_local, rows.stride(0), _ptr(rows), *(() if weights is None else (_ptr(weights),)),
+                       _ptr(ranges), n_bins, _ptr(counts))
+    if run.exchange:
+        _all_reduce(run.dist, run.group, counts, run.dist.ReduceOp.SUM)
+    head_np = head.cpu().numpy()
+    if stats is not None:
+        stats["bytes_to_root"], stats["allreduce_bytes"] = 0, (counts.numel() * 8 if run.exchange else 0)
+        stats["bytes_to_root_per_rank"] = [0] * run.world
+    return head_np[:K * n_bins].reshape(K, n_bins), head_np[K * n_bins:].reshape(K, -1)
+
+
+def _pack_bin_mask(marked):
+    """marked [K, n_bins] bool -> [K, ceil(n_bins / 32)] uint32, bin b in bit b % 32 of word b // 32: what the selection
+    passes read."""
+    K, n_bins = marked.shape
+    words = (n_bins + 31) // 32
+    bits = np.zeros((K, words * 32), dtype=np.uint8)
+    bits[:, :n_bins] = marked
+    return np.packbits(bits.reshape(K, words, 32), axis=2, bitorder="little").view(np.uint32).reshape(K, words)
+
+
+def _selection_plan(counts, cum, want, side, skip, fill):
+    """The host step between the histogram and the selection.  counts / cum [K, n_bins] int64: members (or weight) per bin
+    over all ranks and the running sum; want [Q] (shared) or [K, Q]: cumulative positions to find; skip [K]: rows that need
+    no selection.  Position v lies in the first bin b with cum[b] > v (side "right": v is a 0-based member index) or with
+    cum[b] >= v (side "left": v is a cumulative weight to reach); the last bin if there is none.  Those bins are marked and
+    their members are the CANDIDATES.  Returns (pos [K, Q] int64: each position counted among the candidates alone — what
+    the marked bins below b hold, plus v less what ALL bins below b hold —, `fill` in a skipped row; n_cand [K]: what the
+    marked bins hold; the packed mask of _pack_bin_mask; a skipped row marks nothing)."""
+    K, n_bins = counts.shape
+    want = np.asarray(want)
+    bb = np.stack([np.searchsorted(cum[k], want[k] if want.ndim == 2 else want, side=side) for k in range(K)])
+    bb = bb.clip(max=n_bins - 1)                                                            # [K, Q]
+    bb[skip] = 0
+    rk = np.arange(K)[:, None]
+    marked = np.zeros((K, n_bins), dtype=bool)
+    marked[rk, bb] = True
+    marked[skip] = False
+    zero = np.zeros((K, 1), dtype=np.int64)
+    held = counts * marked
+    below_bin = np.concatenate([zero, cum[:, :-1]], axis=1)                                 # in bins < b
+    cand_below = np.concatenate([zero, np.cumsum(held, axis=1)[:, :-1]], axis=1)            # in MARKED bins < b
+    pos = cand_below[rk, bb] + (want - below_bin[rk, bb])
+    pos[skip] = fill
+    return pos.astype(np.int64), held.sum(axis=1), _pack_bin_mask(marked)
+
+
+def _upload_plan(pos, binmask, dev):
+    """THE upload of a summary: the positions [K, Q] int64, then the bin masks [K, words] uint32, in one device buffer.
+    Returns (buffer, byte offset of the masks)."""
+    up = torch.from_numpy(np.concatenate([pos.reshape(-1).view(np.uint8), binmask.reshape(-1).view(np.uint8)])).to(dev)
+    return up, pos.size * 8
+
+
+def _candidates_to_root(run, cands, cand_n, cap, cand_bytes, dst, stats):
+    """Several ranks: the candidates travel to rank `dst` (a few thousand values out of the ensemble).  cands: this rank's
+    candidate tensors [Kb, cap] (values; then their weights), cand_n [Kb] how many of each row it found.  The counts are
+    all-gathered, every tensor is cut or zero-padded to the widest row of any rank and gathered, one collective per tensor in
+    list order; `stats` counts cand_bytes per candidate that is not the root's own.  Returns (all_n [world, Kb], width, and
+    on `dst` — else None, None — the pools [Kb, world, width], one per tensor, and seg_n [Kb, world], on the device)."""
+    Kb = cand_n.shape[0]
+    all_n = run.all_gather_np(cand_n)
+    width = max(int(all_n.max()), 1)
+    send = []
+    for t in cands:
+        t = t[:, :min(width, cap)]
+        if t.shape[1] < width:
+            t = torch.cat([t, t.new_zeros((Kb, width - t.shape[1]))], dim=1)
+        t = t.contiguous()
+        send.append(t.cpu() if run.host_wire else t)
+    recv = [[torch.empty_like(t) for _ in range(run.world)] if run.rank == dst else None for t in send]
+    for t, r in zip(send, recv):
+        run.dist.gather(t, r, dst=dst, group=run.group)
+    if stats is not None:
+        per_rank = [0 if r == dst else int(all_n[r].sum()) * cand_bytes for r in range(run.world)]
+        stats["bytes_to_root"] += sum(per_rank)
+        stats["bytes_to_root_per_rank"] = [a + b for a, b in zip(stats["bytes_to_root_per_rank"], per_rank)]
+    if run.rank != dst:
+        return all_n, width, None, None
+    pools = [torch.stack(r, dim=1).to(run.dev).contiguous() for r in recv]
+    return all_n, width, pools, torch.from_numpy(np.ascontiguousarray(all_n.T)).to(run.dev)
+
+
+def _select_and_pick(run, rows, weights, ranges, up, t_off, m_off, k0, k1, n_targets, n_bins, cap, dst, stats):
+    """Passes 3 and 4 for rows k0..k1: the selection pass compacts this rank's members of the marked bins (with their weights
+    when `weights` is given) into candidate buffers of `cap` per row; one rank: the pick pass selects the wanted positions
+    among them; several: the candidates travel (_candidates_to_root) and the root's pick pass runs over one segment per rank.
+    up / t_off / m_off: the uploaded plan and the byte offsets of these rows' positions and masks in it.  Ends with the
+    device-to-host copy of tail = [cand_n Kb (uint64) | picked Kb * n_targets (fp64)].  Returns (candidates found per row over
+    all ranks [Kb], picked [Kb, n_targets] fp64) as NumPy arrays — (None, None) on a rank that is not `dst`."""
+    Kb, n_local, ld, w_el = k1 - k0, rows.shape[1], rows.stride(0), rows.element_size()
+    wts = () if weights is None else (_ptr(weights),)
+    tail = torch.zeros(Kb + Kb * n_targets, dtype=torch.int64, device=run.dev)
+    cands = [torch.empty((Kb, cap), dtype=dt, device=run.dev) for dt in (rows.dtype, torch.int64)[:1 + len(wts)]]
+    with _on(run.dev):
+        if n_local > 0:
+            run.launch("select_bins", Kb, n_local, ld, _ptr(rows, k0 * ld * w_el), *wts, _ptr(ranges, k0 * 16), n_bins,
+                       _ptr(up, m_off), *map(_ptr, cands), cap, _ptr(tail))
+        if not run.exchange:
+            run.launch("select_pick", Kb, 1, cap, *map(_ptr, cands), _ptr(tail), n_targets, _ptr(up, t_off), _ptr(tail, Kb * 8))
+    if run.exchange:
+        all_n, width, pools, seg_n = _candidates_to_root(run, cands, tail[:Kb].cpu().numpy(), cap, w_el + 8 * len(wts), dst, stats)
+        if pools is None:
+            return None, None
+        with _on(run.dev):
+            run.launch("select_pick", Kb, run.world, width, *map(_ptr, pools), _ptr(seg_n), n_targets, _ptr(up, t_off),
+                       _ptr(tail, Kb * 8))
+    tail_np = tail.cpu().numpy()                          # one rank: THE second (and last) device-to-host copy
+    return all_n.sum(axis=0) if run.exchange else tail_np[:Kb], tail_np[Kb:].view(np.float64).reshape(Kb, n_targets)
+
+
+def _first_lost(cols, lo, hi, skip):
+    """The sanity check of the pick: in every row that went through the selection, lo <= cols[0] <= cols[1] <= ... <= hi must
+    hold (cols: [K, P] arrays of picked values; a NaN fails).  Returns (row, column) of the first failure, or None."""
+    chain = [lo[:, None], *cols, hi[:, None]]
+    with np.errstate(invalid="ignore"):
+        good = chain[0] <= chain[1]
+        for a, b in zip(chain[1:], chain[2:]):
+            good &= a <= b
+    good |= skip[:, None]
+    return None if good.all() else tuple(int(v) for v in np.argwhere(~good)[0])
+
+
+def _fix_up(values, lo, nan_row, flat):
+    """The rows the selection skipped: a row holding a NaN is NaN (like np.percentile), a constant row is its one value."""
+    return np.where(nan_row[:, None], np.nan, np.where(flat[:, None], np.broadcast_to(lo[:, None], values.shape), values))
+
+
+# ---- the unweighted summary ---------------------------------------------------------------------------------------------
+def _merge_sum_records(parts):
+    """parts [R, K, 5]: per rank and row (member count, sum, sum of squares, min, max) -> [K, 5] fp64 (count, mean, M2, min,
+    max) over the ranks, merged in rank order (merge_moments).  Ranks whose shard is empty take no part."""
+    rec = parts[parts[:, 0, 0] > 0]                          # (a copy: the sums become mean and M2 in place)
+    if rec.shape[0] == 0:
+        raise ValueError("gather_summary: no members on any rank")
+    cnt, mean_r = rec[:, :, 0], rec[:, :, 1]
+    mean_r /= cnt
+    with np.errstate(invalid="ignore", over="ignore"):       # a row with an infinite member: its moments are inf / nan, quietly
+        rec[:, :, 2] = np.maximum(rec[:, :, 2] - cnt * mean_r * mean_r, 0.0)
+    return rec[0] if rec.shape[0] == 1 else merge_moments(torch.from_numpy(rec)).numpy()      # (one record: nothing to merge)
+
+
+def _with_count(n_local, sums):
+    """sums [K, 4] NumPy -> this rank's record [K, 5] for _merge_sum_records."""
+    return np.concatenate([np.full((sums.shape[0], 1), float(n_local)), sums], axis=1)
+
+
+def _moments_and_ranges(run, rows, sums_dev, local_sums, gmin, gmax, n_total, want_moments):
+    """Pass 1 of the unweighted summary: this rank's (sum, sum of squares, min, max) into sums_dev [K, 4] — from local_sums
+    when the caller has them, not at all when it brought the extrema and wants no moments — and the histogram's ranges.
+    Several ranks all-gather and merge the records here; one rank leaves them on the device (they come back with the
+    histogram) unless the extrema were handed in.  Returns (mom [K, 5] or None, lo [K] or None, hi [K] or None, ranges [K, 2]
+    fp64 on the device, the member count over all ranks); lo is None exactly when moments and extrema are still to come."""
+    K, n_local = rows.shape
+    have_sums = gmin is None or want_moments
+    if have_sums:
+        if local_sums is not None:
+            sums_dev.copy_(local_sums.to(device=run.dev, dtype=torch.float64))
+        else:
+            device_row_sums(rows, out=sums_dev)
+    if not run.exchange and gmin is None:
+        return None, None, None, sums_dev[:, 2:4].contiguous(), n_local      # the extrema never leave the device before the histogram
+    mom = None
+    if have_sums:
+        mine = _with_count(n_local, sums_dev.cpu().numpy())
+        mom = _merge_sum_records(run.all_gather_np(mine) if run.exchange else mine[None])
+    if gmin is None:
+        lo, hi, n_tot = mom[:, 3].copy(), mom[:, 4].copy(), int(round(float(mom[0, 0])))
+    else:
+        lo, hi = (np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(K).copy()
+                  for v in (gmin, gmax))
+        n_tot = int(n_total)
+    return mom, lo, hi, torch.from_numpy(np.stack([lo, hi], axis=1)).to(run.dev), n_tot
+
+
+def _summary_in_halves(rows, percentiles, dst, group, stats, lo, hi, n_tot, n_bins):
+    """One row with heavy ties would size the candidate buffer of EVERY row: the rows are summarised in two halves (the
+    decision rests on the all-reduced histogram, so every rank takes it alike), each through _device_summary with the extrema
+    and the member count handed in; a half may halve again.  Returns pct [K, P] on `dst`, None elsewhere."""
+    K = rows.shape[0]
+    h = K // 2
+    half_stats = [None if stats is None else {} for _ in range(2)]
+    halves = [_device_summary(rows[a:b], percentiles, dst, group, st_h, gmin=lo[a:b], gmax=hi[a:b], n_total=n_tot,
+                              want_moments=False, n_bins=n_bins)[1] for (a, b), st_h in zip(((0, h), (h, K)), half_stats)]
+    if stats is not None:
+        # what travelled is what the halves sent (each half all-reduces its own histogram again: counted too)
+        stats["split_rows"] = True
+        stats["bytes_to_root"] = sum(st_h["bytes_to_root"] for st_h in half_stats)
+        stats["allreduce_bytes"] += sum(st_h["allreduce_bytes"] for st_h in half_stats)
+        stats["bytes_to_root_per_rank"] = [sum(v) for v in zip(*(st_h["bytes_to_root_per_rank"] for st_h in half_stats))]
+    return None if halves[0] is None else np.concatenate(halves, axis=0)
+
+
 def _device_summary(rows, percentiles, dst, group, stats, local_sums=None, gmin=None, gmax=None, n_total=None,
                     want_moments=True, n_bins=None):
     """Moments + exact percentiles of device rows [K, n_local] over all ranks.  Returns (mom [K, 5] NumPy fp64 =
@@ -265,182 +507,54 @@ def _device_summary(rows, percentiles, dst, group, stats, local_sums=None, gmin=
 
     The histogram between the global extrema holds EXACT counts and its bin rule is monotone in the value, so the order
     statistic of global index i is the (i - cdf[b-1])-th smallest member of the bin b with cdf[b-1] <= i < cdf[b].  Hence:
-    moments pass -> histogram pass (one rank: ranges straight from the moments, on the device) -> ONE device-to-host copy
-    (moments + counts) -> the host marks the bins that hold wanted order statistics and computes each statistic's rank among
-    the members of marked bins -> ONE upload -> selection pass (members of marked bins, compacted) -> pick pass (radix
-    selection of those ranks) -> ONE copy back.  Several ranks add the exchanges where the text below says so."""
-    dist, rank, world, exchange = _dist(group)
-    lib, _capi, ctypes, st = _lib_and_stream(rows)
+    _moments_and_ranges (moments pass; one rank: ranges straight from the moments, on the device) -> _histogram_stage
+    (histogram pass and ONE device-to-host copy, moments + counts) -> _selection_plan (the host marks the bins that hold wanted
+    order statistics and computes each statistic's rank among the members of marked bins; past SELECT_CAND_BYTES of
+    candidates: _summary_in_halves) -> _upload_plan (ONE upload) -> _select_and_pick (selection pass: members of marked
+    bins, compacted; pick pass: radix selection of those ranks; ONE copy back) -> _first_lost, _fix_up.  Several ranks add
+    the exchanges where those stages say so."""
+    run = _Run(rows, group, "")
     n_bins = SELECT_BINS if n_bins is None else int(n_bins)
     K, n_local = rows.shape
     P = len(percentiles)
-    Q = 2 * P
-    dev = rows.device
-    f64 = rows.dtype == torch.float64
-    w = rows.element_size()
-    sfx = "f64" if f64 else "f32"
-    ptr = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)      # noqa: E731
     if P < 1:
         raise ValueError("no percentiles asked for")
-    ld = rows.stride(0)
-    host_wire = exchange and dist.get_backend(group) == "gloo"
-
-    # one device buffer for everything that comes back after the histogram: counts [K, n_bins] int64, then sums [K, 4] fp64
-    head = torch.zeros(K * n_bins + K * 4, dtype=torch.int64, device=dev)
-    counts = head[:K * n_bins].view(K, n_bins)
-    sums_dev = head[K * n_bins:].view(torch.float64).view(K, 4)
-
-    # ---- pass 1: moments (unless the caller brought them), and with them the global extrema ---------------------------
-    mom = None
-    have_sums = gmin is None or want_moments
-    if have_sums:
-        if local_sums is not None:
-            sums_dev.copy_(local_sums.to(device=dev, dtype=torch.float64))
-        else:
-            device_row_sums(rows, out=sums_dev)
-    lo_np = hi_np = None
-    if exchange or gmin is not None:
-        if have_sums:
-            mine = np.concatenate([np.full((K, 1), float(n_local)), sums_dev.cpu().numpy()], axis=1)      # [K, 5]
-            parts = _all_gather_np(dist, group, world, mine, dev) if exchange else mine[None]
-            cnt, s1 = parts[:, :, 0], parts[:, :, 1]
-            keep = cnt[:, 0] > 0                                 # ranks whose shard is empty take no part in the merge
-            parts, cnt, s1 = parts[keep], cnt[keep], s1[keep]
-            if parts.shape[0] == 0:
-                raise ValueError("gather_summary: no members on any rank")
-            mean_r = s1 / cnt
-            with np.errstate(invalid="ignore", over="ignore"):
-                m2_r = np.maximum(parts[:, :, 2] - cnt * mean_r * mean_r, 0.0)
-            mom = merge_moments(torch.from_numpy(np.stack([cnt, mean_r, m2_r, parts[:, :, 3], parts[:, :, 4]], axis=2))).numpy()
-        if gmin is None:
-            lo_np, hi_np, n_tot = mom[:, 3].copy(), mom[:, 4].copy(), int(round(float(mom[0, 0])))
-        else:
-            lo_np = np.asarray(gmin.detach().cpu() if isinstance(gmin, torch.Tensor) else gmin, dtype=np.float64).reshape(K).copy()
-            hi_np = np.asarray(gmax.detach().cpu() if isinstance(gmax, torch.Tensor) else gmax, dtype=np.float64).reshape(K).copy()
-            n_tot = int(n_total)
-        ranges = torch.from_numpy(np.stack([lo_np, hi_np], axis=1)).to(dev)
-    else:
-        ranges = sums_dev[:, 2:4].contiguous()          # one rank: the extrema never leave the device before the histogram
-        n_tot = n_local
-
-    # ---- pass 2: histograms between the global extrema ------------------------------------------------------------------
-    if n_local > 0:
-        with _on(dev):
-            _capi.check(lib, getattr(lib, f"fiveeq_hist_rows_ranged_{sfx}")(K, n_local, ld, ptr(rows), ptr(ranges), n_bins,
-                                                                            ptr(counts), st))
-    if exchange:
-        _all_reduce(dist, group, counts, dist.ReduceOp.SUM)
-    head_np = head.cpu().numpy()                          # THE device-to-host copy of a one-rank summary's first half
-    counts_np = head_np[:K * n_bins].reshape(K, n_bins)
+    head, counts, rec_dev = _alloc_head(K, n_bins, 4, run.dev)
+    mom, lo_np, hi_np, ranges, n_tot = _moments_and_ranges(run, rows, rec_dev.view(torch.float64), local_sums, gmin, gmax,
+                                                           n_total, want_moments)
+    counts_np, rec_np = _histogram_stage(run, rows, None, ranges, head, counts, stats)
     if lo_np is None:
-        sums_np = head_np[K * n_bins:].view(np.float64).reshape(K, 4)
-        cnt = np.full(K, float(n_local))
-        mean_r = sums_np[:, 0] / cnt
-        with np.errstate(invalid="ignore", over="ignore"):       # a row with an infinite member: its moments are inf / nan, quietly
-            mom = np.stack([cnt, mean_r, np.maximum(sums_np[:, 1] - cnt * mean_r * mean_r, 0.0), sums_np[:, 2], sums_np[:, 3]], axis=1)
-        lo_np, hi_np = sums_np[:, 2].copy(), sums_np[:, 3].copy()
+        mom = _merge_sum_records(_with_count(n_local, rec_np.view(np.float64))[None])
+        lo_np, hi_np = mom[:, 3].copy(), mom[:, 4].copy()
     cdf = np.cumsum(counts_np, axis=1)
     # a NaN member has no bin: a row whose counts do not add up to the member count holds one, and np.percentile of it is NaN
     nan_row = cdf[:, -1] != n_tot
-    if stats is not None:
-        stats["bytes_to_root"], stats["allreduce_bytes"] = 0, (counts.numel() * 8 if exchange else 0)
-        stats["bytes_to_root_per_rank"] = [0] * world
-
-    # ---- host: the bins that hold the wanted order statistics, and each statistic's rank among the members of marked bins ---
     if n_tot < 1:
         raise ValueError("gather_summary: no members on any rank")
     i0, i1, frac = linear_positions(n_tot, percentiles)
-    want = np.concatenate([i0, i1])                                                     # [2P] global order-statistic indices
-    bb = np.stack([np.searchsorted(cdf[k], want, side="right") for k in range(K)]).clip(max=n_bins - 1)     # [K, 2P]
     flat = ~(hi_np > lo_np)                              # a constant row: every member IS the answer, nothing to select
     skip = nan_row | flat
-    bb[skip] = 0
-    rk = np.arange(K)[:, None]
-    marked = np.zeros((K, n_bins), dtype=bool)
-    marked[rk, bb] = True
-    marked[skip] = False
-    below_bin = np.concatenate([np.zeros((K, 1), dtype=np.int64), cdf[:, :-1]], axis=1)                      # members in bins < b
-    cand_below = np.concatenate([np.zeros((K, 1), dtype=np.int64), np.cumsum(counts_np * marked, axis=1)[:, :-1]], axis=1)
-    ranks = cand_below[rk, bb] + (want[None, :] - below_bin[rk, bb])                    # [K, 2P]
-    ranks[skip] = -1
-    n_cand = (counts_np * marked).sum(axis=1)                                            # candidates per row over ALL ranks
-    if K > 1 and K * int(n_cand.max()) * w > SELECT_CAND_BYTES:
-        # one row with heavy ties would size the candidate buffer of EVERY row: summarise the rows in two halves (the decision
-        # rests on the all-reduced histogram, so every rank takes it alike); the extrema and the member count are known
-        h = K // 2
-        half_stats = [None if stats is None else {} for _ in range(2)]
-        halves = [_device_summary(rows[a:b], percentiles, dst, group, st_h, gmin=lo_np[a:b], gmax=hi_np[a:b], n_total=n_tot,
-                                  want_moments=False, n_bins=n_bins)[1] for (a, b), st_h in zip(((0, h), (h, K)), half_stats)]
-        if stats is not None:
-            # what travelled is what the halves sent (each half all-reduces its own histogram again: counted too)
-            stats["split_rows"] = True
-            stats["bytes_to_root"] = sum(st_h["bytes_to_root"] for st_h in half_stats)
-            stats["allreduce_bytes"] += sum(st_h["allreduce_bytes"] for st_h in half_stats)
-            stats["bytes_to_root_per_rank"] = [sum(v) for v in zip(*(st_h["bytes_to_root_per_rank"] for st_h in half_stats))]
-        out = None if halves[0] is None else np.concatenate(halves, axis=0)
-        return mom, out
+    ranks, n_cand, binmask = _selection_plan(counts_np, cdf, np.concatenate([i0, i1]), "right", skip, -1)     # [K, 2P]
+    if K > 1 and K * int(n_cand.max()) * rows.element_size() > SELECT_CAND_BYTES:
+        return mom, _summary_in_halves(rows, percentiles, dst, group, stats, lo_np, hi_np, n_tot, n_bins)
     cap = max(1, int(min(n_local, n_cand.max())))
-    words = (n_bins + 31) // 32
-    bits = np.zeros((K, words * 32), dtype=np.uint8)
-    bits[:, :n_bins] = marked
-    binmask = np.packbits(bits.reshape(K, words, 32), axis=2, bitorder="little").view(np.uint32).reshape(K, words)
-
-    # ---- ONE upload: ranks [K, 2P] int64, then the bin masks [K, words] uint32 ------------------------------------------
-    up = torch.from_numpy(np.concatenate([ranks.astype(np.int64).reshape(-1).view(np.uint8), binmask.reshape(-1).view(np.uint8)])).to(dev)
-    o_mask = K * Q * 8
-
-    # ---- pass 3: selection; pass 4: pick.  tail = [cand_n K (uint64) | picked K*2P (fp64)] ----------------------------------
-    select = getattr(lib, f"fiveeq_select_bins_{sfx}")
-    pick = getattr(lib, f"fiveeq_select_pick_{sfx}")
-    tail = torch.zeros(K + K * Q, dtype=torch.int64, device=dev)
-    cand = torch.empty((K, cap), dtype=rows.dtype, device=dev)
-    with _on(dev):
-        if n_local > 0:
-            _capi.check(lib, select(K, n_local, ld, ptr(rows), ptr(ranges), n_bins, ptr(up, o_mask), ptr(cand), cap, ptr(tail), st))
-        if not exchange:
-            _capi.check(lib, pick(K, 1, cap, ptr(cand), ptr(tail), Q, ptr(up), ptr(tail, K * 8), st))
-    tail_np = tail.cpu().numpy()                          # one rank: THE second (and last) device-to-host copy
-    cand_n = tail_np[:K]
-    tot_c = cand_n
-    if exchange:
-        # several ranks: the candidates travel to the root (a few thousand values out of the ensemble) and the root's pick
-        # pass runs over one segment per rank
-        all_n = _all_gather_np(dist, group, world, cand_n, dev)                             # [world, K]
-        width = max(int(all_n.max()), 1)
-        send = cand[:, :min(width, cap)]
-        if send.shape[1] < width:
-            send = torch.cat([send, send.new_zeros((K, width - send.shape[1]))], dim=1)
-        send = send.contiguous()
-        if host_wire:
-            send = send.cpu()
-        recv = [torch.empty_like(send) for _ in range(world)] if rank == dst else None
-        dist.gather(send, recv, dst=dst, group=group)
-        if stats is not None:
-            stats["bytes_to_root"] = int(all_n.sum() - all_n[dst].sum()) * w
-            stats["bytes_to_root_per_rank"] = [0 if r == dst else int(all_n[r].sum()) * w for r in range(world)]
-        if rank != dst:
-            return mom, None
-        pool = torch.stack(recv, dim=1).to(dev).contiguous()                           # [K, world, width]
-        seg_n = torch.from_numpy(np.ascontiguousarray(all_n.T)).to(dev)                # [K, world]
-        with _on(dev):
-            _capi.check(lib, pick(K, world, width, ptr(pool), ptr(seg_n), Q, ptr(up), ptr(tail, K * 8), st))
-        tail_np = tail.cpu().numpy()
-        tot_c = all_n.sum(axis=0)
-    picked = tail_np[K:].view(np.float64).reshape(K, Q)
+    up, o_mask = _upload_plan(ranks, binmask, run.dev)
+    tot_c, picked = _select_and_pick(run, rows, None, ranges, up, 0, o_mask, 0, K, 2 * P, n_bins, cap, dst, stats)
+    if picked is None:
+        return mom, None
     c0, c1 = picked[:, :P], picked[:, P:]
     # the selection pass must have found exactly the members the histogram counted in the marked bins (same rule, same ranges)
     if not np.array_equal(tot_c[~skip], n_cand[~skip]):
         k = int(np.argwhere((tot_c != n_cand) & ~skip)[0, 0])
         raise RuntimeError(f"percentile selection: row {k} has {int(tot_c[k])} candidates where the histogram counts {int(n_cand[k])}")
+    lost = _first_lost((c0, c1), lo_np, hi_np, skip)
+    if lost is not None:
+        k, j = lost
+        raise RuntimeError(f"percentile selection lost its order statistic (row {k}, p={percentiles[j]}): ranks "
+                           f"{int(ranks[k, j])},{int(ranks[k, j + P])} of {int(tot_c[k])} candidates, values {c0[k, j]}, {c1[k, j]}")
     with np.errstate(invalid="ignore"):
-        good = skip[:, None] | ((c0 <= c1) & (c0 >= lo_np[:, None]) & (c1 <= hi_np[:, None]))
-        if not good.all():
-            k, j = [int(v) for v in np.argwhere(~good)[0]]
-            raise RuntimeError(f"percentile selection lost its order statistic (row {k}, p={percentiles[j]}): ranks "
-                               f"{int(ranks[k, j])},{int(ranks[k, j + P])} of {int(tot_c[k])} candidates, values {c0[k, j]}, {c1[k, j]}")
         out = lerp(c0, c1, frac[None, :])
-    out = np.where(nan_row[:, None], np.nan, np.where(flat[:, None], np.broadcast_to(lo_np[:, None], (K, P)), out))
-    return mom, out
+    return mom, _fix_up(out, lo_np, nan_row, flat)
 
 
 def gather_summary(rows, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, local_sums=None):
@@ -465,10 +579,16 @@ def gather_summary(rows, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats
 WMOM_WORDS = 8                   # 8-byte words per row record of fiveeq_wrow_moments_* (layout: include/fiveeq.h)
 
 
+def _empty_weighted_records(K):
+    """[K, WMOM_WORDS] int64: the neutral record of a shard without members (sums 0, min +inf, max -inf, no flags)."""
+    rec = np.zeros((K, WMOM_WORDS), dtype=np.int64)
+    rec[:, 3:5] = np.array([np.inf, -np.inf]).view(np.int64)
+    return rec
+
+
 def weighted_rank(p, weight_sum):
     """k_p = max(1, ceil(p / 100 * W)): the cumulative weight percentile p must reach, in exact rational arithmetic on the
     exact value of p (Fraction(p)) — a Python int."""
-    from fractions import Fraction
     f = Fraction(p)
     if not 0 <= f <= 100:
         raise ValueError(f"percentile {p} outside [0, 100]")
@@ -481,34 +601,18 @@ def _weighted_plan(counts_np, cumw, W, percentiles, skip):
     bin over all ranks and its running sum; W their total; skip [K]: rows that need no selection.  Returns (targets [K, P]
     int64, binmask [K, ceil(n_bins / 32)] uint32): per row the bins that hold a k_p, marked, and per percentile the
     cumulative weight to reach AMONG THE CANDIDATES (the members of marked bins, ascending): the weight of the marked bins
-    below its bin plus k_p minus the weight of all bins below it — at least 1; 0 for a skipped row."""
-    K, n_bins = counts_np.shape
+    below its bin plus k_p minus the weight of all bins below it — at least 1; 0 for a skipped row.  (_selection_plan with
+    the k_p of weighted_rank as the positions.)"""
     kp = np.array([weighted_rank(p, W) for p in percentiles], dtype=np.int64)               # [P]
-    bb = np.stack([np.searchsorted(cumw[k], kp, side="left") for k in range(K)]).clip(max=n_bins - 1)      # [K, P]
-    bb[skip] = 0
-    rk = np.arange(K)[:, None]
-    marked = np.zeros((K, n_bins), dtype=bool)
-    marked[rk, bb] = True
-    marked[skip] = False
-    zero = np.zeros((K, 1), dtype=np.int64)
-    below_bin = np.concatenate([zero, cumw[:, :-1]], axis=1)                                # weight in bins < b
-    cand_below = np.concatenate([zero, np.cumsum(counts_np * marked, axis=1)[:, :-1]], axis=1)
-    targets = cand_below[rk, bb] + (kp[None, :] - below_bin[rk, bb])
-    targets[skip] = 0
-    words = (n_bins + 31) // 32
-    bits = np.zeros((K, words * 32), dtype=np.uint8)
-    bits[:, :n_bins] = marked
-    binmask = np.packbits(bits.reshape(K, words, 32), axis=2, bitorder="little").view(np.uint32).reshape(K, words)
-    return targets.astype(np.int64), binmask
+    targets, _, binmask = _selection_plan(counts_np, cumw, kp, "left", skip, 0)
+    return targets, binmask
 
 
 def _weighted_moments_dev(lib, _capi, ctypes, st, rows, weights, out):
     """fiveeq_wrow_moments_* of this rank's rows into `out` (a [K, 8] view of 8-byte words on the rows' device)."""
     K, n = rows.shape
     if n == 0:                                             # an empty shard: the neutral record
-        rec = np.zeros((K, WMOM_WORDS), dtype=np.int64)
-        rec[:, 3:5] = np.array([np.inf, -np.inf]).view(np.int64)
-        out.copy_(torch.from_numpy(rec))
+        out.copy_(torch.from_numpy(_empty_weighted_records(K)))
         return
     chunks = int(lib.fiveeq_wrow_moments_chunks(K, n))
     work = torch.empty(K * chunks * WMOM_WORDS, dtype=torch.float64, device=rows.device)
@@ -518,73 +622,30 @@ def _weighted_moments_dev(lib, _capi, ctypes, st, rows, weights, out):
                             ctypes.c_void_p(work.data_ptr()), ctypes.c_void_p(out.data_ptr()), st))
 
 
-def gather_weighted_summary(rows, weights, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, n_bins=None):
-    """rows [K, n_local] ON THE GPU with this rank's integer weights [n_local] (int64 on the same device, 0..2^32 each:
-    constrain.importance_weights, or the caller's own).  Collective over `group`.  The definition is include/fiveeq.h's
-    "WEIGHTED SUMMARY": percentile p = the smallest x whose cumulative weight reaches k_p = weighted_rank(p, W) — exact, and
-    the same bits for every world size and shard split, because every sum that decides it is an integer sum.
-    Returns on every rank a dict: count (members with w > 0), mean, var, std, min, max ([K] fp64 host tensors), weight_sum
-    (Python int), ess (float), method; on rank `dst` also 'percentiles' [K, P] fp64 (None elsewhere).
-    Flow: moments pass -> all-gather and merge of the records -> weighted histogram between the global extrema -> all-reduce
-    SUM (int64) -> the host marks the bins holding each k_p -> selection of (value, weight) pairs -> gather to `dst` -> pick.
-    A rank whose members all weigh 0, or that has none, takes part in every collective."""
-    if rows.dim() != 2:
-        raise ValueError("rows: want [K, n_local]")
-    if rows.shape[1] > 0 and (rows.stride(1) != 1 or rows.stride(0) < rows.shape[1]):      # rows of a wider buffer are read in place
-        rows = rows.contiguous()
-    _need_device_rows(rows)
-    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or weights.device != rows.device \
-            or tuple(weights.shape) != (rows.shape[1],):
-        raise ValueError(f"weights: want an int64 tensor of shape [{rows.shape[1]}] on {rows.device}")
-    weights = weights.contiguous()
-    P = len(percentiles)
-    if P < 1:
-        raise ValueError("no percentiles asked for")
-    for p in percentiles:
-        weighted_rank(p, 1)                               # the range check, before anything is launched
-    dist, rank, world, exchange = _dist(group)
-    lib, _capi, ctypes, st = _lib_and_stream(rows)
-    n_bins = SELECT_BINS if n_bins is None else int(n_bins)
+def _weighted_records_and_ranges(run, rows, weights, rec_dev):
+    """Pass 1 of the weighted summary: this rank's records into rec_dev [K, WMOM_WORDS], and with them the extrema over the
+    members that carry weight.  Several ranks all-gather the records (with the member count behind them).  Returns (every
+    rank's records [world, K, WMOM_WORDS] int64 — None for one rank: they come back with the histogram —, members per rank,
+    the histogram's ranges [K, 2] fp64 on the device)."""
     K, n_local = rows.shape
-    dev, ld, w_el = rows.device, rows.stride(0), rows.element_size()
-    sfx = "f64" if rows.dtype == torch.float64 else "f32"
-    ptr = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)      # noqa: E731
-    host_wire = exchange and dist.get_backend(group) == "gloo"
+    _weighted_moments_dev(run.lib, run.capi, ctypes, run.st, rows, weights, rec_dev)
+    if not run.exchange:
+        # one rank: the extrema never leave the device here
+        return None, np.array([n_local], dtype=np.int64), rec_dev[:, 3:5].view(torch.float64).contiguous()
+    mine = np.concatenate([rec_dev.cpu().numpy().reshape(-1), np.array([n_local], dtype=np.int64)])
+    got = run.all_gather_np(mine)                                                           # [world, K * 8 + 1]
+    parts = got[:, :-1].reshape(run.world, K, WMOM_WORDS)
+    f = parts[:, :, :5].view(np.float64)
+    ranges = torch.from_numpy(np.ascontiguousarray(np.stack([f[:, :, 3].min(axis=0), f[:, :, 4].max(axis=0)], axis=1)))
+    return parts, got[:, -1], ranges.to(run.dev)
 
-    # one device buffer for what comes back after the histogram: weight per bin [K, n_bins] int64, then the records [K, 8]
-    head = torch.zeros(K * n_bins + K * WMOM_WORDS, dtype=torch.int64, device=dev)
-    counts = head[:K * n_bins].view(K, n_bins)
-    rec_dev = head[K * n_bins:].view(K, WMOM_WORDS)
 
-    # ---- pass 1: moments, and with them the extrema over the members that carry weight ------------------------------------
-    _weighted_moments_dev(lib, _capi, ctypes, st, rows, weights, rec_dev)
-    parts = None
-    if exchange:
-        mine = np.concatenate([rec_dev.cpu().numpy().reshape(-1), np.array([n_local], dtype=np.int64)])
-        got = _all_gather_np(dist, group, world, mine, dev)                                 # [world, K * 8 + 1]
-        parts, n_each = got[:, :-1].reshape(world, K, WMOM_WORDS), got[:, -1]
-        f = parts[:, :, :5].view(np.float64)
-        ranges = torch.from_numpy(np.ascontiguousarray(np.stack([f[:, :, 3].min(axis=0), f[:, :, 4].max(axis=0)], axis=1))).to(dev)
-    else:
-        ranges = rec_dev[:, 3:5].view(torch.float64).contiguous()      # one rank: the extrema never leave the device here
-        n_each = np.array([n_local], dtype=np.int64)
-
-    # ---- pass 2: weight per bin between the global extrema; integer sums, so the all-reduce is exact -----------------------
-    if n_local > 0:
-        with _on(dev):
-            _capi.check(lib, getattr(lib, f"fiveeq_whist_rows_ranged_{sfx}")(K, n_local, ld, ptr(rows), ptr(weights), ptr(ranges),
-                                                                             n_bins, ptr(counts), st))
-    if exchange:
-        _all_reduce(dist, group, counts, dist.ReduceOp.SUM)
-    head_np = head.cpu().numpy()
-    counts_np = head_np[:K * n_bins].reshape(K, n_bins)
-    if parts is None:
-        parts = head_np[K * n_bins:].reshape(1, K, WMOM_WORDS)
-    if stats is not None:
-        stats["bytes_to_root"], stats["allreduce_bytes"] = 0, (counts.numel() * 8 if exchange else 0)
-        stats["bytes_to_root_per_rank"] = [0] * world
-
-    # ---- host: the merged record (rank order: the same bits every run), the integer ranks ----------------------------------
+def _merge_weighted_records(parts, n_each):
+    """parts [R, K, WMOM_WORDS] int64: every rank's records; n_each [R]: its members.  The argument checks that need all
+    ranks (member count, weight range, weight sum), then the merge, in rank order: the same bits every run.  Returns (the
+    summary's dict without percentiles, W the weight sum, n_pos [R] members with w > 0 per rank, lo [K], hi [K], nan_row
+    [K])."""
+    K = parts.shape[1]
     n_total = int(n_each.sum())
     if n_total >= (1 << 31):
         raise ValueError(f"weighted summary: {n_total} members over all ranks; integer weights need fewer than 2^31")
@@ -609,6 +670,42 @@ def gather_weighted_summary(rows, weights, percentiles=(5.0, 50.0, 95.0), dst=0,
            "var": torch.from_numpy(var), "std": torch.from_numpy(np.sqrt(var)), "min": torch.from_numpy(lo_np.copy()),
            "max": torch.from_numpy(hi_np.copy()), "weight_sum": W, "ess": float(W) * float(W) / sw2,
            "method": "weighted_inverted_cdf", "percentiles": None}
+    return out, W, n_pos, lo_np, hi_np, nan_row
+
+
+def gather_weighted_summary(rows, weights, percentiles=(5.0, 50.0, 95.0), dst=0, group=None, stats=None, n_bins=None):
+    """rows [K, n_local] ON THE GPU with this rank's integer weights [n_local] (int64 on the same device, 0..2^32 each:
+    constrain.importance_weights, or the caller's own).  Collective over `group`.  The definition is include/fiveeq.h's
+    "WEIGHTED SUMMARY": percentile p = the smallest x whose cumulative weight reaches k_p = weighted_rank(p, W) — exact, and
+    the same bits for every world size and shard split, because every sum that decides it is an integer sum.
+    Returns on every rank a dict: count (members with w > 0), mean, var, std, min, max ([K] fp64 host tensors), weight_sum
+    (Python int), ess (float), method; on rank `dst` also 'percentiles' [K, P] fp64 (None elsewhere).
+    Flow: _weighted_records_and_ranges (moments pass, all-gather of the records) -> _histogram_stage (weighted histogram
+    between the global extrema, all-reduce SUM int64, the one download) -> _merge_weighted_records -> _weighted_plan (the host
+    marks the bins holding each k_p) -> _upload_plan -> per block of rows _select_and_pick (selection of (value, weight)
+    pairs, gather to `dst`, pick) -> _first_lost, _fix_up.
+    A rank whose members all weigh 0, or that has none, takes part in every collective."""
+    if rows.dim() != 2:
+        raise ValueError("rows: want [K, n_local]")
+    if rows.shape[1] > 0 and (rows.stride(1) != 1 or rows.stride(0) < rows.shape[1]):      # rows of a wider buffer are read in place
+        rows = rows.contiguous()
+    _need_device_rows(rows)
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or weights.device != rows.device \
+            or tuple(weights.shape) != (rows.shape[1],):
+        raise ValueError(f"weights: want an int64 tensor of shape [{rows.shape[1]}] on {rows.device}")
+    weights = weights.contiguous()
+    P = len(percentiles)
+    if P < 1:
+        raise ValueError("no percentiles asked for")
+    for p in percentiles:
+        weighted_rank(p, 1)                               # the range check, before anything is launched
+    run = _Run(rows, group, "w")
+    n_bins = SELECT_BINS if n_bins is None else int(n_bins)
+    K = rows.shape[0]
+    head, counts, rec_dev = _alloc_head(K, n_bins, WMOM_WORDS, run.dev)
+    parts, n_each, ranges = _weighted_records_and_ranges(run, rows, weights, rec_dev)
+    counts_np, rec_np = _histogram_stage(run, rows, weights, ranges, head, counts, stats)
+    out, W, n_pos, lo_np, hi_np, nan_row = _merge_weighted_records(rec_np[None] if parts is None else parts, n_each)
 
     cumw = np.cumsum(counts_np, axis=1)                                                     # int64: W < 2^63
     flat = ~(hi_np > lo_np)                               # one value carries all the weight: it IS every percentile
@@ -617,69 +714,26 @@ def gather_weighted_summary(rows, weights, percentiles=(5.0, 50.0, 95.0), dst=0,
         k = int(np.argwhere((cumw[:, -1] != W) & ~nan_row)[0, 0])
         raise RuntimeError(f"weighted summary: row {k}'s histogram weighs {int(cumw[k, -1])} where the weights sum to {W}")
     targets, binmask = _weighted_plan(counts_np, cumw, W, percentiles, skip)
-    words = binmask.shape[1]
+    up, o_mask = _upload_plan(targets, binmask, run.dev)
 
-    # ---- ONE upload: targets [K, P] int64, then the bin masks [K, words] uint32 -------------------------------------------
-    up = torch.from_numpy(np.concatenate([targets.astype(np.int64).reshape(-1).view(np.uint8), binmask.reshape(-1).view(np.uint8)])).to(dev)
-    o_mask = K * P * 8
-
-    # ---- pass 3: selection; pass 4: pick.  The weighted histogram does not count members, so a row's candidate buffer is
-    # sized by this rank's members with w > 0 (most members of a tightly constrained ensemble weigh 0); rows go in blocks
-    # while rows x that bound (the largest over the ranks: every rank blocks alike) exceeds SELECT_CAND_BYTES ------------------
-    select = getattr(lib, f"fiveeq_wselect_bins_{sfx}")
-    pick = getattr(lib, f"fiveeq_wselect_pick_{sfx}")
-    cap = max(1, int(n_pos[rank if exchange else 0]))
-    block = max(1, min(K, SELECT_CAND_BYTES // (max(1, int(n_pos.max())) * (w_el + 8))))
+    # The weighted histogram does not count members, so a row's candidate buffer is sized by this rank's members with w > 0
+    # (most members of a tightly constrained ensemble weigh 0); rows go in blocks while rows x that bound (the largest over
+    # the ranks: every rank blocks alike) exceeds SELECT_CAND_BYTES
+    cap = max(1, int(n_pos[run.rank if run.exchange else 0]))
+    block = max(1, min(K, SELECT_CAND_BYTES // (max(1, int(n_pos.max())) * (rows.element_size() + 8))))
     picked = np.full((K, P), np.nan)
     for k0 in range(0, K, block):
         k1 = min(K, k0 + block)
-        Kb = k1 - k0
-        tail = torch.zeros(Kb + Kb * P, dtype=torch.int64, device=dev)                       # [cand_n Kb (uint64) | picked Kb * P (fp64)]
-        cand = torch.empty((Kb, cap), dtype=rows.dtype, device=dev)
-        candw = torch.empty((Kb, cap), dtype=torch.int64, device=dev)
-        t_off, m_off = k0 * P * 8, o_mask + k0 * words * 4
-        with _on(dev):
-            if n_local > 0:
-                _capi.check(lib, select(Kb, n_local, ld, ptr(rows, k0 * ld * w_el), ptr(weights), ptr(ranges, k0 * 16), n_bins,
-                                        ptr(up, m_off), ptr(cand), ptr(candw), cap, ptr(tail), st))
-            if not exchange:
-                _capi.check(lib, pick(Kb, 1, cap, ptr(cand), ptr(candw), ptr(tail), P, ptr(up, t_off), ptr(tail, Kb * 8), st))
-        if exchange:
-            cand_n = tail[:Kb].cpu().numpy()
-            all_n = _all_gather_np(dist, group, world, cand_n, dev)                         # [world, Kb]
-            width = max(int(all_n.max()), 1)
-
-            def padded(t):
-                t = t[:, :min(width, cap)]
-                if t.shape[1] < width:
-                    t = torch.cat([t, t.new_zeros((Kb, width - t.shape[1]))], dim=1)
-                return t.cpu().contiguous() if host_wire else t.contiguous()
-
-            send_x, send_w = padded(cand), padded(candw)
-            recv_x = [torch.empty_like(send_x) for _ in range(world)] if rank == dst else None
-            recv_w = [torch.empty_like(send_w) for _ in range(world)] if rank == dst else None
-            dist.gather(send_x, recv_x, dst=dst, group=group)
-            dist.gather(send_w, recv_w, dst=dst, group=group)
-            if stats is not None:
-                per_rank = [0 if r == dst else int(all_n[r].sum()) * (w_el + 8) for r in range(world)]
-                stats["bytes_to_root"] += sum(per_rank)
-                stats["bytes_to_root_per_rank"] = [a + b for a, b in zip(stats["bytes_to_root_per_rank"], per_rank)]
-            if rank != dst:
-                continue
-            pool = torch.stack(recv_x, dim=1).to(dev).contiguous()                          # [Kb, world, width]
-            poolw = torch.stack(recv_w, dim=1).to(dev).contiguous()
-            seg_n = torch.from_numpy(np.ascontiguousarray(all_n.T)).to(dev)                 # [Kb, world]
-            with _on(dev):
-                _capi.check(lib, pick(Kb, world, width, ptr(pool), ptr(poolw), ptr(seg_n), P, ptr(up, t_off), ptr(tail, Kb * 8), st))
-        picked[k0:k1] = tail.cpu().numpy()[Kb:].view(np.float64).reshape(Kb, P)
-    if exchange and rank != dst:
+        _, got = _select_and_pick(run, rows, weights, ranges, up, k0 * P * 8, o_mask + k0 * binmask.shape[1] * 4, k0, k1, P,
+                                  n_bins, cap, dst, stats)
+        if got is not None:
+            picked[k0:k1] = got
+    if run.exchange and run.rank != dst:
         return out
-    with np.errstate(invalid="ignore"):
-        good = skip[:, None] | ((picked >= lo_np[:, None]) & (picked <= hi_np[:, None]))
-    if not good.all():
-        k, j = [int(v) for v in np.argwhere(~good)[0]]
+    lost = _first_lost((picked,), lo_np, hi_np, skip)
+    if lost is not None:
+        k, j = lost
         raise RuntimeError(f"weighted selection lost its percentile (row {k}, p={percentiles[j]}): target {int(targets[k, j])}, "
                            f"picked {picked[k, j]}")
-    pct = np.where(nan_row[:, None], np.nan, np.where(flat[:, None], np.broadcast_to(lo_np[:, None], (K, P)), picked))
-    out["percentiles"] = torch.from_numpy(pct)
+    out["percentiles"] = torch.from_numpy(_fix_up(picked, lo_np, nan_row, flat))
     return out
