@@ -29,6 +29,8 @@ MAX_COND_BINS = 32
 # fiveeq_joint_tile(0..7): x rows, y rows per workgroup of the co-moment pass; members per chunk; members per lane and load of
 # fp64 / fp32 rows; bins, y rows per workgroup of the conditional sums; lanes per workgroup.  load() checks them.
 JOINT_TILE = (4, 4, 4096, 2, 4, 16, 4, 256)
+MAX_PULSES = 3                      # fiveeq_max_pulses() / fiveeq_max_horizons() of fiveeq_pulse_response_* (fiveeq_pulse.hpp)
+MAX_HORIZONS = 8
 MAX_SCORE_Q = 4                     # fiveeq_max_score_quantities() of fiveeq_score_rows_* (fiveeq_score.hpp)
 SCORE_TILE_F64 = 512                # members per workgroup of score_rows_kernel: 256 lanes of 16 bytes of a row
 SCORE_TILE_F32 = 1024
@@ -123,6 +125,12 @@ _RUNS = {
 # fiveeq_forcing_rows_*: (model, n_rows, n_members, ld, C_rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive,
 # n_steps, q, fscale, n_fext, fext, F, F_gas, N, H, ld_out, H_io, S_io, n_mismatch, stream)
 _FORCROWS = [_mp, _i32, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]
+# fiveeq_pulse_response_*: (model, n_scen, n_rows, n_members, ld, C_rows, c_scen_stride, c_row_stride, c_gas_stride, T_rows,
+# t_scen_stride, t_row_stride, steps, drive, n_steps, fscale, n_fext, fext, base, n_pulses, pulse_scen, pulse_gas, n_horizons,
+# horizons, row0, out, ld_out, io, stream); pulse_scen, pulse_gas and horizons are HOST arrays of int32
+_i32p = ctypes.POINTER(_i32)
+_PULSE = [_mp, _i32, _i32, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32p, _i32p, _i32,
+          _i32p, _i32, _p, _i64, _p, _p]
 # name -> (restype, argtypes); every symbol include/fiveeq.h declares
 SIGNATURES = {
     "fiveeq_abi_version": (ctypes.c_int, []),
@@ -196,6 +204,10 @@ SIGNATURES = {
     "fiveeq_forcing_rows_tile": (_i32, [_i32]),
     "fiveeq_forcing_rows_f64": (ctypes.c_int, _FORCROWS),
     "fiveeq_forcing_rows_f32": (ctypes.c_int, _FORCROWS),
+    "fiveeq_max_pulses": (_i32, []),
+    "fiveeq_max_horizons": (_i32, []),
+    "fiveeq_pulse_response_f64": (ctypes.c_int, _PULSE),
+    "fiveeq_pulse_response_f32": (ctypes.c_int, _PULSE),
     "fiveeq_uniform_rows_f64": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, ctypes.POINTER(ctypes.c_uint32), _p, _p]),
     "fiveeq_uniform_rows_f32": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, ctypes.POINTER(ctypes.c_uint32), _p, _p]),
     "fiveeq_stream_copy_f64": (ctypes.c_int, [_i64, _p, _p, _p]),
@@ -211,7 +223,7 @@ _lib = None
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
-    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp")) + (
+    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 
@@ -270,6 +282,9 @@ def load(path=None):
              lib.fiveeq_max_score_quantities())
     if score != (SCORE_TILE_F64, SCORE_TILE_F32, SCORE_UNROLL, SCORE_UNROLL_NARROW, MAX_SCORE_Q):
         raise ImportError(f"{lib_path}: score_rows_kernel's tiles / unrolls / limit are {score}, the binding's constants say otherwise")
+    pulse = (lib.fiveeq_max_pulses(), lib.fiveeq_max_horizons())
+    if pulse != (MAX_PULSES, MAX_HORIZONS):
+        raise ImportError(f"{lib_path}: pulse_response_kernel's limits are {pulse}, the binding's constants say otherwise")
     # The library must have been compiled from the sources lying next to this file: a prebuilt .so that travelled to
     # another box, or survived a source edit, is refused instead of tested.  (FIVEEQ_ALLOW_STALE_LIB=1: experiment
     # variants built from patched sources, tools/ only.)

@@ -1996,5 +1996,120 @@ int fiveeq_forcing_rows_f32(const fiveeq_model* model, int32_t n_rows, int64_t n
     return forcing_rows<float>(model, n_rows, n_members, ld, C_rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive, n_steps,
                                q, fscale, n_fext, fext, F, F_gas, N, H, ld_out, H_io, S_io, n_mismatch, stream);
 }
+// ---- the response to emission pulses from the stored rows of a scenario engine (kernel 13) -----------------------------------
+}  // extern "C"
+namespace {
+template <typename T>
+int pulse_response(const fiveeq_model* model, int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, const T* C, int64_t c_scen,
+                   int64_t c_row, int64_t c_gas, const T* Trows, int64_t t_scen, int64_t t_row, const int32_t* steps, const T* drive,
+                   int32_t n_steps, const T* fscale, int32_t n_fext, const T* fext, int32_t base, int32_t n_pulses,
+                   const int32_t* pulse_scen, const int32_t* pulse_gas, int32_t n_hor, const int32_t* horizons, int32_t row0,
+                   double* out, int64_t ld_out, double* io, void* stream) {
+    if (int rc = check_model(model)) return rc;
+    const int G = model->n_gas;
+    const auto mag = [](int64_t v) { return v < 0 ? -v : v; };
+    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
+    if (row0 < 0 || row0 > INT32_MAX - n_rows) return fail(FIVEEQ_E_INVALID, "row0=%d with n_rows=%d outside 0..2^31-1", row0, n_rows);
+    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
+    if (ld < n) return fail(FIVEEQ_E_INVALID, "ld=%lld < n_members=%lld", (long long)ld, (long long)n);
+    if (ld_out < n) return fail(FIVEEQ_E_INVALID, "ld_out=%lld < n_members=%lld", (long long)ld_out, (long long)n);
+    if (n_scen < 2) return fail(FIVEEQ_E_INVALID, "n_scen=%d: a base scenario and at least one pulse scenario are needed", n_scen);
+    if (n_pulses < 1 || n_pulses > FIVEEQ_MAX_PULSES) return fail(FIVEEQ_E_INVALID, "n_pulses=%d outside 1..%d", n_pulses, FIVEEQ_MAX_PULSES);
+    if (n_hor < 1 || n_hor > FIVEEQ_MAX_HORIZONS) return fail(FIVEEQ_E_INVALID, "n_horizons=%d outside 1..%d", n_hor, FIVEEQ_MAX_HORIZONS);
+    if (!pulse_scen || !pulse_gas) return fail(FIVEEQ_E_INVALID, "pulse_scen / pulse_gas is NULL");
+    if (!horizons) return fail(FIVEEQ_E_INVALID, "horizons is NULL");
+    if (base < 0 || base >= n_scen) return fail(FIVEEQ_E_INVALID, "base=%d outside the scenarios 0..%d", base, n_scen - 1);
+    for (int p = 0; p < n_pulses; ++p) {
+        if (pulse_scen[p] < 0 || pulse_scen[p] >= n_scen)
+            return fail(FIVEEQ_E_INVALID, "pulse %d: scenario %d outside the scenarios 0..%d", p, pulse_scen[p], n_scen - 1);
+        if (pulse_scen[p] == base) return fail(FIVEEQ_E_INVALID, "pulse %d names the base scenario %d", p, base);
+        if (pulse_gas[p] < 0 || pulse_gas[p] >= G) return fail(FIVEEQ_E_INVALID, "pulse %d: gas %d outside the gases 0..%d", p, pulse_gas[p], G - 1);
+    }
+    for (int h = 0; h < n_hor; ++h) {
+        if (horizons[h] < 1) return fail(FIVEEQ_E_INVALID, "horizon %d: %d rows; a horizon is a row count >= 1", h, horizons[h]);
+        if (h > 0 && horizons[h] <= horizons[h - 1])
+            return fail(FIVEEQ_E_INVALID, "horizons must be strictly increasing: horizon %d is %d after %d", h, horizons[h], horizons[h - 1]);
+    }
+    if (n_rows > 1 && c_row < n) return fail(FIVEEQ_E_INVALID, "c_row_stride=%lld < n_members=%lld", (long long)c_row, (long long)n);
+    if (G > 1 && mag(c_gas) < n) return fail(FIVEEQ_E_INVALID, "|c_gas_stride|=%lld < n_members=%lld", (long long)mag(c_gas), (long long)n);
+    if (mag(c_scen) < n) return fail(FIVEEQ_E_INVALID, "|c_scen_stride|=%lld < n_members=%lld", (long long)mag(c_scen), (long long)n);
+    if (n_rows > 1 && t_row < n) return fail(FIVEEQ_E_INVALID, "t_row_stride=%lld < n_members=%lld", (long long)t_row, (long long)n);
+    if (mag(t_scen) < n) return fail(FIVEEQ_E_INVALID, "|t_scen_stride|=%lld < n_members=%lld", (long long)mag(t_scen), (long long)n);
+    if (n_fext < 0 || n_fext > fiveeq::MAX_FEXT) return fail(FIVEEQ_E_INVALID, "n_fext=%d outside 0..%d", n_fext, fiveeq::MAX_FEXT);
+    if (n_fext > 0 && fscale && !fext) return fail(FIVEEQ_E_INVALID, "fscale with n_fext=%d categories needs fext: fext is NULL", n_fext);
+    if (n_fext > 0 && fext && !fscale) return fail(FIVEEQ_E_INVALID, "fext with n_fext=%d categories needs fscale: fscale is NULL", n_fext);
+    if (n_fext > 0 && !fscale) return fail(FIVEEQ_E_INVALID, "n_fext=%d without fscale and fext", n_fext);
+    if (n_steps < 1) return fail(FIVEEQ_E_INVALID, "n_steps=%d must be >= 1", n_steps);
+    if (n_rows > 0 && !C) return fail(FIVEEQ_E_INVALID, "C_rows is NULL");
+    if (n_rows > 0 && !Trows) return fail(FIVEEQ_E_INVALID, "T_rows is NULL");
+    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
+    if (!drive) return fail(FIVEEQ_E_INVALID, "drive is NULL");
+    if (!out) return fail(FIVEEQ_E_INVALID, "out is NULL");
+    if (!io) return fail(FIVEEQ_E_INVALID, "io is NULL");
+    const void* elem[] = {C, Trows, drive, fscale, fext};
+    for (const void* p : elem)
+        if (misaligned(p, sizeof(T))) return fail(FIVEEQ_E_INVALID, "a row pointer (%p) is not %d-byte aligned", p, (int)sizeof(T));
+    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
+    if (misaligned(out, 8) || misaligned(io, 8)) return fail(FIVEEQ_E_INVALID, "out and io must be 8-byte aligned");
+    if (n_rows == 0) return FIVEEQ_OK;                         // no row: nothing is written, and the carried sums stay what they are
+    fiveeq::PulseArgs<T> a;
+    a.n_gas = G, a.n_rows = n_rows, a.n = 0, a.n_steps = n_steps, a.n_fext = fscale ? n_fext : 0, a.n_hor = n_hor, a.row0 = row0;
+    a.scen[0] = base;
+    for (int p = 0; p < fiveeq::PULSE_MAX; ++p) {
+        a.scen[1 + p] = p < n_pulses ? pulse_scen[p] : base;
+        a.gas[p] = p < n_pulses ? pulse_gas[p] : 0;
+    }
+    for (int h = 0; h < fiveeq::PULSE_MAX_HORIZONS; ++h) a.hor[h] = h < n_hor ? horizons[h] : fiveeq::PULSE_NO_HORIZON;
+    a.C = C, a.c_scen = c_scen, a.c_row = n_rows > 1 ? c_row : 0, a.c_gas = G > 1 ? c_gas : 0;
+    a.Trows = Trows, a.t_scen = t_scen, a.t_row = n_rows > 1 ? t_row : 0;
+    a.steps = steps, a.drive = drive, a.fs = fscale, a.X = fscale ? fext : nullptr, a.ld = ld;
+    a.out = out, a.ld_out = ld_out, a.io = io;
+    // 16-byte accesses where every lane's address of every row read or written is aligned (as in forcing_rows above): the
+    // members [0, n_vec) in whole lanes; the ragged tail and unaligned rows take the element accesses in a launch of their own
+    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
+    const bool wide = !misaligned(C, 16) && !misaligned(Trows, 16) && !misaligned(out, 16) && a.c_scen % per16 == 0 &&
+                      a.c_row % per16 == 0 && a.c_gas % per16 == 0 && a.t_scen % per16 == 0 && a.t_row % per16 == 0 && ld_out % 2 == 0;
+    const int64_t n_vec = wide ? n / per16 * per16 : 0;
+    const KModel<T> km = make_kmodel<T>(model);
+    const auto launch = [&](auto vec, int64_t m0, int64_t members) {
+        fiveeq::PulseArgs<T> b = a;
+        b.n = (int)members;
+        b.C += m0, b.Trows += m0, b.out += m0, b.io += m0;
+        if (b.fs) b.fs += m0;
+        const dim3 grid((unsigned)((members + fiveeq::METRICS_TILE<T> - 1) / fiveeq::METRICS_TILE<T>));
+        constexpr bool VEC = decltype(vec)::value;
+        if (n_pulses == 1) hipLaunchKernelGGL((fiveeq::pulse_response_kernel<T, VEC, 1>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
+        else if (n_pulses == 2) hipLaunchKernelGGL((fiveeq::pulse_response_kernel<T, VEC, 2>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
+        else hipLaunchKernelGGL((fiveeq::pulse_response_kernel<T, VEC, 3>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
+    };
+    if (n_vec > 0) launch(std::true_type{}, 0, n_vec);
+    if (n_vec < n) launch(std::false_type{}, n_vec, n - n_vec);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int32_t fiveeq_max_pulses(void) { return FIVEEQ_MAX_PULSES; }
+int32_t fiveeq_max_horizons(void) { return FIVEEQ_MAX_HORIZONS; }
+int fiveeq_pulse_response_f64(const fiveeq_model* model, int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const double* C_rows,
+                              int64_t c_scen_stride, int64_t c_row_stride, int64_t c_gas_stride, const double* T_rows,
+                              int64_t t_scen_stride, int64_t t_row_stride, const int32_t* steps, const double* drive, int32_t n_steps,
+                              const double* fscale, int32_t n_fext, const double* fext, int32_t base, int32_t n_pulses,
+                              const int32_t* pulse_scen, const int32_t* pulse_gas, int32_t n_horizons, const int32_t* horizons,
+                              int32_t row0, double* out, int64_t ld_out, double* io, void* stream) {
+    return pulse_response<double>(model, n_scen, n_rows, n_members, ld, C_rows, c_scen_stride, c_row_stride, c_gas_stride, T_rows,
+                                  t_scen_stride, t_row_stride, steps, drive, n_steps, fscale, n_fext, fext, base, n_pulses, pulse_scen,
+                                  pulse_gas, n_horizons, horizons, row0, out, ld_out, io, stream);
+}
+int fiveeq_pulse_response_f32(const fiveeq_model* model, int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const float* C_rows,
+                              int64_t c_scen_stride, int64_t c_row_stride, int64_t c_gas_stride, const float* T_rows,
+                              int64_t t_scen_stride, int64_t t_row_stride, const int32_t* steps, const float* drive, int32_t n_steps,
+                              const float* fscale, int32_t n_fext, const float* fext, int32_t base, int32_t n_pulses,
+                              const int32_t* pulse_scen, const int32_t* pulse_gas, int32_t n_horizons, const int32_t* horizons,
+                              int32_t row0, double* out, int64_t ld_out, double* io, void* stream) {
+    return pulse_response<float>(model, n_scen, n_rows, n_members, ld, C_rows, c_scen_stride, c_row_stride, c_gas_stride, T_rows,
+                                 t_scen_stride, t_row_stride, steps, drive, n_steps, fscale, n_fext, fext, base, n_pulses, pulse_scen,
+                                 pulse_gas, n_horizons, horizons, row0, out, ld_out, io, stream);
+}
 
 }  // extern "C"

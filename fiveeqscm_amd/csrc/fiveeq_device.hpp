@@ -26,6 +26,7 @@
 //   fiveeq_diag.hpp     stream_copy_kernel, stream_copy_wide_kernel, stream_copy_nt_kernel, math_probe_kernel, busy_kernel
 //   fiveeq_score.hpp    11  score_rows_kernel   the misfit accumulators of stored rows against observed records, live rows only
 //   fiveeq_forcrows.hpp 12 forcing_rows_kernel the forcing, energy imbalance and heat uptake of a run recomputed from its stored rows
+//   fiveeq_pulse.hpp    13 pulse_response_kernel the forcing, warming and concentration response to emission pulses, summed to horizons
 // and what they share: fiveeq_math.hpp (the model struct, lane types, fe_* math), fiveeq_stats.hpp (per-wave statistics, the bin
 // rule), fiveeq_member.hpp (member_step(), gas_forcing(), the misfit update, the lane's member span and row access).
 // All model arithmetic is member_step(): every kernel that steps the model gives the same bits.
@@ -76,3 +77,4 @@ constexpr int DRIVE_STRIDE = 8;
 #include "fiveeq_diag.hpp"
 #include "fiveeq_score.hpp"
 #include "fiveeq_forcrows.hpp"
+#include "fiveeq_pulse.hpp"

@@ -94,6 +94,42 @@ struct ForcRowsLane {
     int mismatches;
 };
 
+// THE FORCING OF ONE ROW of a lane's M members from the row's shared record (fext, xr) and its loaded C rows: F_ext, then the
+// categories by fma, then the gases through gas_forcing() — fma with the scales (scaled), the plain sum without.  Written
+// ONCE: forcrows_row() below and the pulse-response pass (fiveeq_pulse.hpp) call it, so the two cannot drift apart.
+// fg_out(g, Fg) is handed every gas's forcing as it is formed (kernel 12 stores it when F_gas is asked for).
+template <typename T, bool VEC, typename FgOut>
+__device__ __forceinline__ void forcrows_F(const KModel<T>& km, const int n_gas, const int n_fext, const bool scaled, const T fext,
+                                           const T* xr, const MetricsLoad<T, VEC> (&c)[MAX_GAS],
+                                           const T (&sg)[MAX_GAS][METRICS_LANE<T>], const T (&sx)[MAX_FEXT][METRICS_LANE<T>],
+                                           T (&F)[METRICS_LANE<T>], FgOut&& fg_out) {
+    constexpr int M = METRICS_LANE<T>;
+#pragma unroll
+    for (int j = 0; j < M; ++j) F[j] = fext;
+    if (scaled) {
+#pragma unroll
+        for (int x = 0; x < MAX_FEXT; ++x) {
+            if (x < n_fext) {
+                const T xv = xr[x];
+#pragma unroll
+                for (int j = 0; j < M; ++j) F[j] = fe_fma(sx[x][j], xv, F[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < MAX_GAS; ++g) {
+        if (g < n_gas) {
+            T Fg[M];
+#pragma unroll
+            for (int j = 0; j < M; ++j) {
+                Fg[j] = gas_forcing<T>(km.gas[g], c[g].v[j]);
+                F[j] = scaled ? fe_fma(sg[g][j], Fg[j], F[j]) : F[j] + Fg[j];
+            }
+            fg_out(g, Fg);
+        }
+    }
+}
+
 // ONE ROW of the lane: row k of the call, its shared record (fext, xr: LDS), its loaded C rows and T row.
 template <typename T, bool VEC, bool SEQ>
 __device__ __forceinline__ void forcrows_row(const KModel<T>& km, const ForcRowsArgs<T>& a, const int k, const int64_t m, const int live,
@@ -101,30 +137,9 @@ __device__ __forceinline__ void forcrows_row(const KModel<T>& km, const ForcRows
                                              const MetricsLoad<T, VEC>& tr, ForcRowsLane<T>& s) {
     constexpr int M = METRICS_LANE<T>;
     T F[M];
-#pragma unroll
-    for (int j = 0; j < M; ++j) F[j] = fext;
-    if (a.fs) {
-#pragma unroll
-        for (int x = 0; x < MAX_FEXT; ++x) {
-            if (x < a.n_fext) {
-                const T xv = xr[x];
-#pragma unroll
-                for (int j = 0; j < M; ++j) F[j] = fe_fma(s.sx[x][j], xv, F[j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < MAX_GAS; ++g) {
-        if (g < a.n_gas) {
-            T Fg[M];
-#pragma unroll
-            for (int j = 0; j < M; ++j) {
-                Fg[j] = gas_forcing<T>(km.gas[g], c[g].v[j]);
-                F[j] = a.fs ? fe_fma(s.sg[g][j], Fg[j], F[j]) : F[j] + Fg[j];
-            }
-            if (a.Fg) forcrows_store<T, M, VEC>(a.Fg + ((int64_t)k * a.n_gas + g) * a.ld_out + m, Fg, live);
-        }
-    }
+    forcrows_F<T, VEC>(km, a.n_gas, a.n_fext, a.fs != nullptr, fext, xr, c, s.sg, s.sx, F, [&](const int g, const T (&Fg)[M]) {
+        if (a.Fg) forcrows_store<T, M, VEC>(a.Fg + ((int64_t)k * a.n_gas + g) * a.ld_out + m, Fg, live);
+    });
     if (a.F) forcrows_store<T, M, VEC>(a.F + (int64_t)k * a.ld_out + m, F, live);
     if (a.Trows) {
         T Nn[M];

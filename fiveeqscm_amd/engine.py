@@ -1137,6 +1137,40 @@ class EnsembleEngine(CheckpointMixin):
         return ForcingRows(stack("F"), stack("F_gas"), stack("N"), stack("H"), stack("S_end"),
                            [p.replay_mismatches for p in parts] if replay else None)
 
+    def pulse_response(self, experiment_or_pulses, horizons, base=0, rows=None):
+        """Per-member emission metrics from this engine's stored rows — pulse.pulse_response wired to the engine's C, T,
+        out_steps, drive tables, fscale and category tables (include/fiveeq.h, "PULSE RESPONSE"): the differences of forcing,
+        warming and concentration between each pulse scenario and the base scenario, summed to the horizons, in ONE streaming
+        HIP pass.  experiment_or_pulses: the pulse.PulseExperiment the engine was built from (pulse p is scenario 1 + p), or a
+        sequence of (scenario, gas, size).  horizons: strictly increasing row counts (years at dt = 1), counted from the first
+        stored row.  base: the base scenario.  rows: a slice of the stored rows (default: all); the first stored row must be
+        the step that carries the pulses, or the sums miss the pulse's first years.
+        ValueError for an engine without the scenario axis, without stored concentrations, for compensated=True (its forcing
+        comes from the unrounded excess) and for stored rows that are not consecutive steps.  Joins unjoined per-step streams
+        first.  Reads the engine; writes nothing into it.  Returns pulse.PulseResponse: agwp(), agtp(), iagtp(), irf(), gwp(),
+        gtp(), whose rows [p, h] go into gather_summary / gather_weighted_summary and drivers() unchanged."""
+        from .pulse import PulseExperiment, pulse_response
+        if not self.scenario_axis:
+            raise ValueError("pulse_response: this engine runs one scenario; a pulse response needs the base and the pulse scenarios "
+                             "in ONE engine (emissions [S, n_steps, G], e.g. pulse.pulse_experiment(...).emissions)")
+        if self.compensated:
+            raise ValueError("pulse_response: compensated=True takes its forcing from the UNROUNDED excess C - C0, which is not stored")
+        if self.C is None or self.T is None or self.n_rows == 0:
+            raise ValueError("pulse_response: no stored concentrations (store_concentrations=False or no output_steps): the "
+                             "forcing of every scenario is recomputed from its stored C rows")
+        sel = slice(None) if rows is None else rows
+        if not isinstance(sel, slice) or sel.step not in (None, 1):
+            raise ValueError("rows: want a slice of the stored rows with step 1 (or None for all)")
+        if isinstance(experiment_or_pulses, PulseExperiment):
+            table = [(1 + p, g, size) for p, (g, size) in enumerate(experiment_or_pulses.pulses)]
+        else:
+            table = list(experiment_or_pulses)
+        if self._ps_unjoined:
+            self.join()
+        with torch.cuda.device(self.device):
+            return pulse_response(self.C[:, sel], self.T[:, sel], self.out_steps[sel], self.params, q=self.q, F_ext=self.drive, dt=self.dt,
+                                  base=base, pulses=table, horizons=horizons, fscale=self.fscale, X=self.fext)
+
     def parameter_rows(self, names=None):
         """(names, rows [K, N]) — this shard's per-member parameters as device rows in the engine's dtype, in the order r0[g],
         rC[g], rT[g] per gas, q[0], q[1], ECS, TCR (params.ecs_tcr of the q rows) and, with forcing=, f_scale[g] and

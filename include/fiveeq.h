@@ -843,6 +843,61 @@ int fiveeq_forcing_rows_f32(const fiveeq_model *model, int32_t n_rows, int64_t n
                             int32_t n_fext, const float *fext, float *F, float *F_gas, float *N, double *H, int64_t ld_out,
                             double *H_io, float *S_io, uint64_t *n_mismatch, void *stream);
 
+/* new — PULSE RESPONSE: what a unit emission of a gas is worth, per member — the response of forcing, warming and concentration
+ * to emission pulses, summed to time horizons, FROM THE STORED ROWS of a scenario engine that ran "baseline" and "baseline +
+ * pulse of gas g" for the same members — DESIGN.md section 3.19; host side: fiveeqscm_amd/pulse.py pulse_response,
+ * EnsembleEngine.pulse_response.  Additive: no symbol above changes, FIVEEQ_ABI_VERSION stays 13, fiveeq_sizeof_model() stays 448.
+ *
+ * ONE streaming pass.  The concentration of scenario s, row k, gas g, member m is C_rows[s * c_scen_stride + k * c_row_stride +
+ * g * c_gas_stride + m] (the C rows [S][n_rows][G][ld] of a scenario engine), the warming T_rows[s * t_scen_stride + k *
+ * t_row_stride + m].  steps dev [n_rows] int32: entry k is the model step row k holds.  drive dev [n_scen][n_steps][8] (F_ext at
+ * [6]), fscale dev [G + n_fext][ld] and fext dev [n_scen][n_steps][fiveeq_max_fext()] as in SCENARIOS and FORCING SCALES; fscale
+ * and fext both NULL (n_fext 0) for a run without forcing scales.  All in the precision of the entry point.  base: the base
+ * scenario b.  pulse_scen, pulse_gas HOST [n_pulses] int32: pulse p is scenario s_p != b with gas g_p pulsed, 1 <= n_pulses <=
+ * fiveeq_max_pulses() (FIVEEQ_MAX_PULSES).  horizons HOST [n_horizons] int32, 1 <= n_horizons <= fiveeq_max_horizons()
+ * (FIVEEQ_MAX_HORIZONS): strictly increasing ROW COUNTS n_h >= 1, counted from the first row of the experiment; row0 is the
+ * number of rows earlier calls have covered (0 for the first call).
+ * DEFINITION.  For the rows in row order, per member and pulse p, every operation rounded on its own:
+ *     F_b, F_p = the forcing of scenario b / s_p at the row, formed exactly as FORCING ROWS forms F (the same device function)
+ *     dF_p = (double)F_p - (double)F_b;   dT_p = (double)T[s_p] - (double)T[b];   dC_p = (double)C[s_p][g_p] - (double)C[b][g_p]
+ *     I_F_p = I_F_p + dF_p;   I_T_p = I_T_p + dT_p;   I_C_p = I_C_p + dC_p        fp64 in both precisions; no fma
+ * — the rectangle rule over end-of-step values (times dt on the host), the convention of the heat uptake H.  When row0 + k ==
+ * n_h - 1 the values AFTER that row are written to out [5][n_pulses][n_horizons][ld_out] fp64 = (I_F, I_T, I_C, dT, dC) at
+ * [.][p][h], columns [0, n_members).  A horizon the rows of this call do not end on is NOT written (the caller pre-fills out,
+ * e.g. with NaN).  CARRIED STATE io [3][n_pulses][ld] fp64, in / out: (I_F, I_T, I_C) before the first row and after the last;
+ * the caller zeroes it before the first call.  NaN is not skipped: a NaN input makes the sums it enters NaN from that row on,
+ * for that member only.
+ * CONSEQUENCES: rows [0, k) in one call and rows [k, n) in a second (row0 = k, io carried) give the bits of one call; any
+ * member sub-range gives the bits of the whole; launch shape, strides and alignment cannot change a bit.  THE CALLER OWES rows
+ * of consecutive model steps and steps inside [0, n_steps) (the kernel clamps a step into the tables and never reads outside
+ * them).  Nothing is allocated, nothing synchronises.  The pass reads sizeof(element) * (1 + n_pulses)(G + 1) per member-row.
+ * FIVEEQ_E_UNSUPPORTED for a pool layout outside fiveeq_layout_supported.  FIVEEQ_E_INVALID, before anything is launched and
+ * with fiveeq_last_error() naming the argument, for: an invalid model; n_rows < 0; row0 < 0 or row0 + n_rows >= 2^31; n_members
+ * < 1 or >= 2^31; ld or ld_out < n_members; n_scen < 2; n_pulses or n_horizons out of range; a NULL pulse_scen, pulse_gas or
+ * horizons; base or a pulse's scenario outside [0, n_scen); a pulse naming the base scenario; a pulse's gas outside [0, G); a
+ * horizon < 1 or not above its predecessor; c_row_stride or t_row_stride < n_members with n_rows > 1; |c_gas_stride| <
+ * n_members with G > 1; |c_scen_stride| or |t_scen_stride| < n_members (rows that overlap); n_fext outside 0..fiveeq_max_fext();
+ * fscale without fext or fext without fscale when n_fext > 0; n_steps < 1; a NULL C_rows, T_rows or steps (allowed with n_rows
+ * == 0), drive, out or io; a pointer not aligned to its element. */
+#define FIVEEQ_MAX_PULSES   3
+#define FIVEEQ_MAX_HORIZONS 8
+int32_t fiveeq_max_pulses(void);
+int32_t fiveeq_max_horizons(void);
+int fiveeq_pulse_response_f64(const fiveeq_model *model, int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld,
+                              const double *C_rows, int64_t c_scen_stride, int64_t c_row_stride, int64_t c_gas_stride,
+                              const double *T_rows, int64_t t_scen_stride, int64_t t_row_stride, const int32_t *steps,
+                              const double *drive, int32_t n_steps, const double *fscale, int32_t n_fext, const double *fext,
+                              int32_t base, int32_t n_pulses, const int32_t *pulse_scen, const int32_t *pulse_gas,
+                              int32_t n_horizons, const int32_t *horizons, int32_t row0, double *out, int64_t ld_out,
+                              double *io, void *stream);
+int fiveeq_pulse_response_f32(const fiveeq_model *model, int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld,
+                              const float *C_rows, int64_t c_scen_stride, int64_t c_row_stride, int64_t c_gas_stride,
+                              const float *T_rows, int64_t t_scen_stride, int64_t t_row_stride, const int32_t *steps,
+                              const float *drive, int32_t n_steps, const float *fscale, int32_t n_fext, const float *fext,
+                              int32_t base, int32_t n_pulses, const int32_t *pulse_scen, const int32_t *pulse_gas,
+                              int32_t n_horizons, const int32_t *horizons, int32_t row0, double *out, int64_t ld_out,
+                              double *io, void *stream);
+
 /* new — SINGLE-VALUED PARAMETER ROWS: the per-step form without the loads of the parameter rows whose members all hold one value
  * — DESIGN.md section 3.16; host side: EnsembleEngine(uniform_rows=).  Additive: no symbol above changes, FIVEEQ_ABI_VERSION
  * stays 13, fiveeq_sizeof_model() stays 448.
