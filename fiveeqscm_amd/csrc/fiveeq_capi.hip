@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <type_traits>
 
@@ -37,6 +38,82 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess)                                                                  \
             return fail(FIVEEQ_E_HIP, "%s failed: %s (%d)", #expr, hipGetErrorString(e_), (int)e_); \
     } while (0)
+
+// ---- argument checks the passes share: each leaves its message and returns the code, or FIVEEQ_OK ------------
+// A pass calls them in the order it documents, so the first bad argument names itself; `name` is the argument's
+// name where the message carries it.
+constexpr int64_t MEMBERS_MAX = 0x7fffffffLL;               // members of a shard and outputs: int32 indices
+bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+int check_n_rows(int32_t n_rows) { return n_rows < 0 ? fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows) : FIVEEQ_OK; }
+int check_members(int64_t n) {
+    return n < 1 || n > MEMBERS_MAX ? fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n) : FIVEEQ_OK;
+}
+// a leading dimension, or a stride that cannot be negative, spans the members
+int check_ld(const char* name, int64_t ld, int64_t n) {
+    return ld < n ? fail(FIVEEQ_E_INVALID, "%s=%lld < n_members=%lld", name, (long long)ld, (long long)n) : FIVEEQ_OK;
+}
+// a signed stride spans the members in either direction
+int check_stride(const char* name, int64_t stride, int64_t n) {
+    const int64_t mag = stride < 0 ? -stride : stride;
+    return mag < n ? fail(FIVEEQ_E_INVALID, "|%s|=%lld < n_members=%lld", name, (long long)mag, (long long)n) : FIVEEQ_OK;
+}
+int check_n_bins(int32_t n_bins) {
+    return n_bins < 1 || n_bins > HIST_MAX_BINS ? fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, HIST_MAX_BINS) : FIVEEQ_OK;
+}
+// pointers by name: the first NULL among the required ones, then the first misaligned one (NULL counts as aligned)
+struct NamedPtr {
+    const char* name;
+    const void* p;
+    size_t align = 1;
+    bool required = true;
+};
+using NamedPtrs = std::initializer_list<NamedPtr>;
+int check_not_null(NamedPtrs ptrs) {
+    for (const NamedPtr& a : ptrs)
+        if (a.required && !a.p) return fail(FIVEEQ_E_INVALID, "%s is NULL", a.name);
+    return FIVEEQ_OK;
+}
+int check_aligned(NamedPtrs ptrs) {
+    for (const NamedPtr& a : ptrs)
+        if (misaligned(a.p, a.align)) return fail(FIVEEQ_E_INVALID, "%s must be %d-byte aligned", a.name, (int)a.align);
+    return FIVEEQ_OK;
+}
+// the optional forcing scales of a stored-row pass: fscale and the table fext come together, and categories need both
+int check_fext(int32_t n_fext, const void* fscale, const void* fext) {
+    if (n_fext < 0 || n_fext > MAX_FEXT) return fail(FIVEEQ_E_INVALID, "n_fext=%d outside 0..%d", n_fext, MAX_FEXT);
+    if (n_fext > 0 && fscale && !fext) return fail(FIVEEQ_E_INVALID, "fscale with n_fext=%d categories needs fext: fext is NULL", n_fext);
+    if (n_fext > 0 && fext && !fscale) return fail(FIVEEQ_E_INVALID, "fext with n_fext=%d categories needs fscale: fscale is NULL", n_fext);
+    if (n_fext > 0 && !fscale) return fail(FIVEEQ_E_INVALID, "n_fext=%d without fscale and fext", n_fext);
+    return FIVEEQ_OK;
+}
+// workgroups of `chunk` members each over n members: the x extent of a grid
+int member_chunks(int64_t n, int64_t chunk, int64_t* chunks) {
+    *chunks = (n + chunk - 1) / chunk;
+    return *chunks > 0x7fffffffLL ? fail(FIVEEQ_E_INVALID, "n_members too large") : FIVEEQ_OK;
+}
+
+// ---- the wide / narrow split of a pass over stored rows -------------------------------------------------------
+// 16-byte accesses where every lane's address of every row the pass reads or writes (the member index a multiple of the
+// lane's members) is aligned — the pass's own `wide` condition on its bases and strides: the members [0, n_vec) in whole
+// lanes.  The ragged tail (fewer members than a lane's) and unaligned rows take the element accesses, in a launch of their
+// own on the columns from n_vec.
+template <typename T>
+constexpr int64_t PER16 = 16 / (int64_t)sizeof(T);
+template <typename T>
+int64_t wide_members(bool wide, int64_t n) { return wide ? n / PER16<T> * PER16<T> : 0; }
+// launch(std::true_type / std::false_type: 16-byte or element accesses, first member, members)
+template <typename Launch>
+void launch_split(int64_t n_vec, int64_t n, const Launch& launch) {
+    if (n_vec > 0) launch(std::true_type{}, (int64_t)0, n_vec);
+    if (n_vec < n) launch(std::false_type{}, n_vec, n - n_vec);
+}
+// f(std::integral_constant<int, N>) for the N of LO..HI that v is; the caller has checked that v is one of them
+template <int LO, int HI, typename F>
+void dispatch_count(int v, const F& f) {
+    if constexpr (LO == HI) f(std::integral_constant<int, LO>{});
+    else if (v == LO) f(std::integral_constant<int, LO>{});
+    else dispatch_count<LO + 1, HI>(v, f);
+}
 
 // ---- pool layouts with a compiled kernel --------------------------------------------------
 // X(P0, P1, P2): pools of gas 0, 1, 2 (0 = gas absent).  CO2-like gases carry 4 pools,
@@ -1242,28 +1319,32 @@ int64_t hist_chunk(int32_t n_rows, int64_t n) {
     if (chunk < fiveeq::HIST_CHUNK_MIN) chunk = fiveeq::HIST_CHUNK_MIN;
     return (chunk + FIVEEQ_BLOCK - 1) / FIVEEQ_BLOCK * FIVEEQ_BLOCK;
 }
+// the chunk of a ranged histogram (the summaries': a few rows): every workgroup zeroes and flushes all n_bins counters, which
+// at 2048 workgroups of 18k members each is a third of the pass (68 us for 3 x 12.5M fp32 values at 4096 bins, 40 at 1024 bins)
+// — at least 8 members per bin and workgroup, in whole `unit`s: 47 us.  (The ring passes count 64+ rows per launch and are
+// far beyond that already.)
+int64_t ranged_chunk(int64_t chunk, int32_t n_bins, int64_t unit) {
+    const int64_t floor_ = (8LL * n_bins + unit - 1) / unit * unit;
+    return chunk < floor_ ? floor_ : chunk;
+}
+// the sizes of both counting passes
+int hist_check(int32_t n_rows, int64_t n, int64_t ld, int32_t n_bins) {
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (n < 1 || ld < n) return fail(FIVEEQ_E_INVALID, "n_members=%lld, ld=%lld invalid", (long long)n, (long long)ld);
+    return check_n_bins(n_bins);
+}
 
 template <typename T>
 int hist_rows(int32_t n_rows, int64_t n, int64_t ld, const T* rows, double lo, double hi, int32_t n_bins,
               uint64_t* hist, void* stream, const double* ranges = nullptr) {
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
-    if (n < 1 || ld < n) return fail(FIVEEQ_E_INVALID, "n_members=%lld, ld=%lld invalid", (long long)n, (long long)ld);
-    if (n_bins < 1 || n_bins > fiveeq::HIST_MAX_BINS)
-        return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, fiveeq::HIST_MAX_BINS);
+    if (int rc = hist_check(n_rows, n, ld, n_bins)) return rc;
     if (!ranges && (!(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi))) return fail(FIVEEQ_E_INVALID, "need finite lo < hi");
     if (n_rows == 0) return FIVEEQ_OK;
     if (!rows || !hist) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
     if (n_rows > 65535) return fail(FIVEEQ_E_INVALID, "n_rows=%d exceeds the 65535 rows of one launch", n_rows);
-    int64_t chunk = hist_chunk(n_rows, n);
-    if (ranges) {
-        // the summary's histogram (a few rows): every workgroup zeroes and flushes all n_bins counters, which at 2048 workgroups
-        // of 18k members each is a third of the pass (68 us for 3 x 12.5M fp32 values at 4096 bins, 40 at 1024 bins) — at least
-        // 8 members per bin and workgroup: 47 us.  (The ring passes count 64+ rows per launch and are far beyond that already.)
-        const int64_t floor_ = (8LL * n_bins + FIVEEQ_BLOCK - 1) / FIVEEQ_BLOCK * FIVEEQ_BLOCK;
-        if (chunk < floor_) chunk = floor_;
-    }
-    const int64_t chunks = (n + chunk - 1) / chunk;
-    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    const int64_t chunk = ranges ? ranged_chunk(hist_chunk(n_rows, n), n_bins, FIVEEQ_BLOCK) : hist_chunk(n_rows, n);
+    int64_t chunks;
+    if (int rc = member_chunks(n, chunk, &chunks)) return rc;
     const double inv_w = ranges ? 0.0 : (double)n_bins / (hi - lo);
     hipLaunchKernelGGL(fiveeq::hist_rows_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
                        (hipStream_t)stream, n, ld, chunk, rows, lo, inv_w, n_bins, reinterpret_cast<unsigned long long*>(hist),
@@ -1295,18 +1376,13 @@ int fiveeq_hist_rows_f64(int32_t n_rows, int64_t n_members, int64_t ld, const do
 }
 int fiveeq_hist_bins(int32_t n_rows, int64_t n_members, int64_t ld, const uint16_t* bins, int32_t n_bins, uint64_t* hist,
                      void* stream) {
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
-    if (n_members < 1 || ld < n_members)
-        return fail(FIVEEQ_E_INVALID, "n_members=%lld, ld=%lld invalid", (long long)n_members, (long long)ld);
-    if (n_bins < 1 || n_bins > fiveeq::HIST_MAX_BINS)
-        return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, fiveeq::HIST_MAX_BINS);
+    if (int rc = hist_check(n_rows, n_members, ld, n_bins)) return rc;
     if (n_rows == 0) return FIVEEQ_OK;
     if (!bins || !hist) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
     if (n_rows > 65535) return fail(FIVEEQ_E_INVALID, "n_rows=%d exceeds the 65535 rows of one launch", n_rows);
-    int64_t chunk = hist_chunk(n_rows, n_members);
+    int64_t chunk = hist_chunk(n_rows, n_members), chunks;
     chunk = (chunk + 8 * FIVEEQ_BLOCK - 1) / (8 * FIVEEQ_BLOCK) * (8 * FIVEEQ_BLOCK);      // eight members per lane and load
-    const int64_t chunks = (n_members + chunk - 1) / chunk;
-    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    if (int rc = member_chunks(n_members, chunk, &chunks)) return rc;
     hipLaunchKernelGGL(fiveeq::hist_bins_kernel, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
                        (hipStream_t)stream, n_members, ld, chunk, bins, n_bins, reinterpret_cast<unsigned long long*>(hist));
     HIP_TRY(hipGetLastError());
@@ -1325,7 +1401,7 @@ int64_t summary_chunk(int32_t n_rows, int64_t n) {
     return (hist_chunk(n_rows, n) + unit - 1) / unit * unit;
 }
 int summary_check(int32_t n_rows, int64_t n, int64_t ld, const void* rows) {
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
+    if (int rc = check_n_rows(n_rows)) return rc;
     if (n_rows > 65535) return fail(FIVEEQ_E_INVALID, "n_rows=%d exceeds the 65535 rows of one launch", n_rows);
     if (n < 1 || ld < n) return fail(FIVEEQ_E_INVALID, "n_members=%lld, ld=%lld invalid", (long long)n, (long long)ld);
     if (n_rows > 0 && !rows) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
@@ -1336,9 +1412,8 @@ int row_moments(int32_t n_rows, int64_t n, int64_t ld, const T* rows, double* pa
     if (int rc = summary_check(n_rows, n, ld, rows)) return rc;
     if (n_rows == 0) return FIVEEQ_OK;
     if (!partial || !moments) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
-    const int64_t chunk = summary_chunk(n_rows, n);
-    const int64_t chunks = (n + chunk - 1) / chunk;
-    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    int64_t chunk = summary_chunk(n_rows, n), chunks;
+    if (int rc = member_chunks(n, chunk, &chunks)) return rc;
     hipLaunchKernelGGL(fiveeq::row_moments_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
                        (hipStream_t)stream, n, ld, chunk, rows, partial);
     hipLaunchKernelGGL(fiveeq::row_moments_fold_kernel, dim3((unsigned)n_rows), dim3(64), 0, (hipStream_t)stream, chunks,
@@ -1350,14 +1425,12 @@ template <typename T>
 int select_bins(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const double* ranges, int32_t n_bins,
                 const uint32_t* binmask, T* cand, int64_t cap, uint64_t* cand_n, void* stream) {
     if (int rc = summary_check(n_rows, n, ld, rows)) return rc;
-    if (n_bins < 1 || n_bins > fiveeq::HIST_MAX_BINS)
-        return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, fiveeq::HIST_MAX_BINS);
+    if (int rc = check_n_bins(n_bins)) return rc;
     if (cap < 0) return fail(FIVEEQ_E_INVALID, "cap=%lld must be >= 0", (long long)cap);
     if (n_rows == 0) return FIVEEQ_OK;
     if (!ranges || !binmask || !cand_n || (cap > 0 && !cand)) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
-    const int64_t chunk = summary_chunk(n_rows, n);
-    const int64_t chunks = (n + chunk - 1) / chunk;
-    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    int64_t chunk = summary_chunk(n_rows, n), chunks;
+    if (int rc = member_chunks(n, chunk, &chunks)) return rc;
     hipLaunchKernelGGL(fiveeq::select_bins_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
                        (hipStream_t)stream, n, ld, chunk, rows, ranges, n_bins, binmask, cand, cap,
                        reinterpret_cast<unsigned long long*>(cand_n));
@@ -1423,18 +1496,12 @@ int fiveeq_select_bins_f32(int32_t n_rows, int64_t n_members, int64_t ld, const 
 // ---- weighted end-of-run summary passes (kernels 7a-7d) ------------------------------------------------------------
 }  // extern "C"
 namespace {
-bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 // the checks every weighted pass over rows shares: the sizes, the row pointer and the weights
 template <typename T>
 int wsummary_check(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uint64_t* weights) {
     if (int rc = summary_check(n_rows, n, ld, rows)) return rc;
     if (n_rows > 0 && !weights) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
     if (misaligned(rows, sizeof(T)) || misaligned(weights, 8)) return fail(FIVEEQ_E_INVALID, "rows / weights not aligned to their element size");
-    return FIVEEQ_OK;
-}
-int wsummary_bins_check(int32_t n_bins) {
-    if (n_bins < 1 || n_bins > fiveeq::HIST_MAX_BINS)
-        return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, fiveeq::HIST_MAX_BINS);
     return FIVEEQ_OK;
 }
 template <typename T>
@@ -1444,9 +1511,8 @@ int wrow_moments(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uin
     if (n_rows == 0) return FIVEEQ_OK;
     if (!partial || !moments) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
     if (misaligned(partial, 8) || misaligned(moments, 8)) return fail(FIVEEQ_E_INVALID, "partial / moments not 8-byte aligned");
-    const int64_t chunk = summary_chunk(n_rows, n);
-    const int64_t chunks = (n + chunk - 1) / chunk;
-    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    int64_t chunk = summary_chunk(n_rows, n), chunks;
+    if (int rc = member_chunks(n, chunk, &chunks)) return rc;
     hipLaunchKernelGGL(fiveeq::wrow_moments_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
                        (hipStream_t)stream, n, ld, chunk, rows, reinterpret_cast<const unsigned long long*>(weights), partial);
     hipLaunchKernelGGL(fiveeq::wrow_moments_fold_kernel, dim3((unsigned)n_rows), dim3(64), 0, (hipStream_t)stream, chunks,
@@ -1458,16 +1524,12 @@ template <typename T>
 int whist_rows(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uint64_t* weights, const double* ranges, int32_t n_bins,
                uint64_t* hist, void* stream) {
     if (int rc = wsummary_check(n_rows, n, ld, rows, weights)) return rc;
-    if (int rc = wsummary_bins_check(n_bins)) return rc;
+    if (int rc = check_n_bins(n_bins)) return rc;
     if (n_rows == 0) return FIVEEQ_OK;
     if (!ranges || !hist) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
     if (misaligned(ranges, 8) || misaligned(hist, 8)) return fail(FIVEEQ_E_INVALID, "ranges / hist not 8-byte aligned");
-    // the chunking of the unweighted ranged histogram (at least 8 members per bin and workgroup), in whole 16-byte loads
-    int64_t chunk = summary_chunk(n_rows, n);
-    const int64_t unit = 4 * FIVEEQ_BLOCK, floor_ = (8LL * n_bins + unit - 1) / unit * unit;
-    if (chunk < floor_) chunk = floor_;
-    const int64_t chunks = (n + chunk - 1) / chunk;
-    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    int64_t chunk = ranged_chunk(summary_chunk(n_rows, n), n_bins, 4 * FIVEEQ_BLOCK), chunks;      // in whole 16-byte loads
+    if (int rc = member_chunks(n, chunk, &chunks)) return rc;
     hipLaunchKernelGGL(fiveeq::whist_rows_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
                        (hipStream_t)stream, n, ld, chunk, rows, reinterpret_cast<const unsigned long long*>(weights), ranges, n_bins,
                        reinterpret_cast<unsigned long long*>(hist));
@@ -1478,15 +1540,14 @@ template <typename T>
 int wselect_bins(int32_t n_rows, int64_t n, int64_t ld, const T* rows, const uint64_t* weights, const double* ranges,
                  int32_t n_bins, const uint32_t* binmask, T* cand, uint64_t* candw, int64_t cap, uint64_t* cand_n, void* stream) {
     if (int rc = wsummary_check(n_rows, n, ld, rows, weights)) return rc;
-    if (int rc = wsummary_bins_check(n_bins)) return rc;
+    if (int rc = check_n_bins(n_bins)) return rc;
     if (cap < 0) return fail(FIVEEQ_E_INVALID, "cap=%lld must be >= 0", (long long)cap);
     if (n_rows == 0) return FIVEEQ_OK;
     if (!ranges || !binmask || !cand_n || (cap > 0 && (!cand || !candw))) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
     if (misaligned(ranges, 8) || misaligned(binmask, 4) || misaligned(cand, sizeof(T)) || misaligned(candw, 8) || misaligned(cand_n, 8))
         return fail(FIVEEQ_E_INVALID, "ranges / binmask / cand / candw / cand_n not aligned to their element size");
-    const int64_t chunk = summary_chunk(n_rows, n);
-    const int64_t chunks = (n + chunk - 1) / chunk;
-    if (chunks > 0x7fffffffLL) return fail(FIVEEQ_E_INVALID, "n_members too large");
+    int64_t chunk = summary_chunk(n_rows, n), chunks;
+    if (int rc = member_chunks(n, chunk, &chunks)) return rc;
     hipLaunchKernelGGL(fiveeq::wselect_bins_kernel<T>, dim3((unsigned)chunks, (unsigned)n_rows), dim3(FIVEEQ_BLOCK), 0,
                        (hipStream_t)stream, n, ld, chunk, rows, reinterpret_cast<const unsigned long long*>(weights), ranges, n_bins,
                        binmask, cand, reinterpret_cast<unsigned long long*>(candw), cap, reinterpret_cast<unsigned long long*>(cand_n));
@@ -1551,13 +1612,12 @@ int fiveeq_wselect_pick_f32(int32_t n_rows, int32_t n_seg, int64_t width, const 
 // ---- resampling a weighted ensemble (kernels 8a-8c) ------------------------------------------------------------------------
 }  // extern "C"
 namespace {
-constexpr int64_t RESAMPLE_MAX = 0x7fffffffLL;              // members of a shard and outputs: int32 indices
 template <typename T>
 int gather_rows(int32_t n_rows, int64_t n_out, int64_t ld_in, const T* rows_in, int64_t ld_out, T* rows_out, const int32_t* src,
                 void* stream) {
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
-    if (n_out < 0 || n_out > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_out=%lld outside 0..2^31-1", (long long)n_out);
-    if (ld_in < 1 || ld_in > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "ld_in=%lld outside 1..2^31-1", (long long)ld_in);
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (n_out < 0 || n_out > MEMBERS_MAX) return fail(FIVEEQ_E_INVALID, "n_out=%lld outside 0..2^31-1", (long long)n_out);
+    if (ld_in < 1 || ld_in > MEMBERS_MAX) return fail(FIVEEQ_E_INVALID, "ld_in=%lld outside 1..2^31-1", (long long)ld_in);
     if (ld_out < n_out) return fail(FIVEEQ_E_INVALID, "ld_out=%lld < n_out=%lld", (long long)ld_out, (long long)n_out);
     if (n_rows == 0 || n_out == 0) return FIVEEQ_OK;
     if (!rows_in || !rows_out || !src) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
@@ -1575,7 +1635,7 @@ int64_t fiveeq_wscan_chunks(int64_t n_members) {
     return (n_members + fiveeq::WSCAN_TILE - 1) / fiveeq::WSCAN_TILE * fiveeq::WSCAN_WORDS;
 }
 int fiveeq_wscan(int64_t n_members, const uint64_t* weights, uint64_t* partial, uint64_t* cum, uint64_t* flags, void* stream) {
-    if (n_members < 1 || n_members > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n_members);
+    if (int rc = check_members(n_members)) return rc;
     if (!weights || !partial || !cum || !flags) return fail(FIVEEQ_E_INVALID, "NULL device pointer");
     if (misaligned(weights, 8) || misaligned(partial, 8) || misaligned(cum, 8) || misaligned(flags, 8))
         return fail(FIVEEQ_E_INVALID, "weights / partial / cum / flags not 8-byte aligned");
@@ -1592,8 +1652,8 @@ int fiveeq_wscan(int64_t n_members, const uint64_t* weights, uint64_t* partial, 
 }
 int fiveeq_resample_pick(int64_t n_members, const uint64_t* cum, uint64_t c_lo, int64_t M, int64_t q, int64_t a, int64_t s, int64_t b,
                          int64_t j0, int64_t n_out, int32_t* src, void* stream) {
-    if (n_members < 1 || n_members > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n_members);
-    if (M < 1 || M > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "M=%lld outside 1..2^31-1", (long long)M);
+    if (int rc = check_members(n_members)) return rc;
+    if (M < 1 || M > MEMBERS_MAX) return fail(FIVEEQ_E_INVALID, "M=%lld outside 1..2^31-1", (long long)M);
     if (q < 0 || a < 0) return fail(FIVEEQ_E_INVALID, "q=%lld, a=%lld must be >= 0", (long long)q, (long long)a);
     if (s < 0 || s >= M || b < 0 || b >= M)
         return fail(FIVEEQ_E_INVALID, "s=%lld, b=%lld outside [0, M=%lld)", (long long)s, (long long)b, (long long)M);
@@ -1632,9 +1692,9 @@ int traj_metrics(int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, const T*
                  int32_t n_levels, const double* levels, int32_t n_windows, const int32_t* windows, double* fmet, int32_t* imet,
                  int32_t first_call, void* stream) {
     if (int rc = check_scen(n_scen)) return rc;
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
-    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
-    if (ld < n) return fail(FIVEEQ_E_INVALID, "ld=%lld < n_members=%lld", (long long)ld, (long long)n);
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
     if (n_scen > 1 && scen_stride < (int64_t)n_rows * ld)
         return fail(FIVEEQ_E_INVALID, "scen_stride=%lld < n_rows * ld = %lld", (long long)scen_stride, (long long)((int64_t)n_rows * ld));
     if (n_levels < 0 || n_levels > FIVEEQ_MAX_LEVELS) return fail(FIVEEQ_E_INVALID, "n_levels=%d outside 0..%d", n_levels, FIVEEQ_MAX_LEVELS);
@@ -1642,14 +1702,9 @@ int traj_metrics(int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, const T*
         return fail(FIVEEQ_E_INVALID, "n_windows=%d outside 0..%d", n_windows, FIVEEQ_MAX_WINDOWS);
     if (n_levels > 0 && !levels) return fail(FIVEEQ_E_INVALID, "levels is NULL with n_levels=%d", n_levels);
     if (n_windows > 0 && !windows) return fail(FIVEEQ_E_INVALID, "windows is NULL with n_windows=%d", n_windows);
-    if (n_rows > 0 && !rows) return fail(FIVEEQ_E_INVALID, "rows is NULL");
-    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
-    if (!fmet) return fail(FIVEEQ_E_INVALID, "fmet is NULL");
-    if (!imet) return fail(FIVEEQ_E_INVALID, "imet is NULL");
-    if (misaligned(rows, sizeof(T))) return fail(FIVEEQ_E_INVALID, "rows must be %d-byte aligned", (int)sizeof(T));
-    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
-    if (misaligned(fmet, 8)) return fail(FIVEEQ_E_INVALID, "fmet must be 8-byte aligned");
-    if (misaligned(imet, 4)) return fail(FIVEEQ_E_INVALID, "imet must be 4-byte aligned");
+    const NamedPtrs ptrs = {{"rows", rows, sizeof(T), n_rows > 0}, {"steps", steps, 4, n_rows > 0}, {"fmet", fmet, 8}, {"imet", imet, 4}};
+    if (int rc = check_not_null(ptrs)) return rc;
+    if (int rc = check_aligned(ptrs)) return rc;
     fiveeq::MetricsSpec sp = {};
     for (int l = 0; l < n_levels; ++l) {
         if (std::isnan(levels[l])) return fail(FIVEEQ_E_INVALID, "levels[%d] is NaN", l);
@@ -1662,35 +1717,20 @@ int traj_metrics(int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, const T*
     }
     sp.n_levels = n_levels, sp.n_windows = n_windows;
     if (n_rows == 0 && !first_call) return FIVEEQ_OK;         // nothing to fold into the state
-    // 16-byte row loads where every lane's address rows + s scen_stride + k ld + m (m a multiple of the lane's members) is
-    // aligned: the members [0, n_vec) in whole lanes; the ragged tail (fewer members than a lane's) and unaligned rows take the
-    // element loads, in a launch of their own on the columns from n_vec
-    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
-    const bool wide = !misaligned(rows, 16) && ld % per16 == 0 && (n_scen == 1 || scen_stride % per16 == 0);
-    const int64_t n_vec = wide ? n / per16 * per16 : 0;
-    const auto grid = [&](int64_t members) {
-        return dim3((unsigned)((members + fiveeq::METRICS_TILE<T> - 1) / fiveeq::METRICS_TILE<T>), (unsigned)n_scen);
-    };
-#define FIVEEQ_METRICS_LAUNCH1(F, NL, VEC, m0, members)                                                                          \
-    hipLaunchKernelGGL((fiveeq::traj_metrics_kernel<T, F, NL, VEC>), grid(members), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream,   \
-                       n_rows, (int)(members), ld, rows + (m0), scen_stride, steps, sp, fmet + (m0), imet + (m0))
-#define FIVEEQ_METRICS_LAUNCH(NL)                                                                                                \
-    case NL:                                                                                                                     \
-        if (n_vec > 0) {                                                                                                         \
-            if (first_call) FIVEEQ_METRICS_LAUNCH1(true, NL, true, 0, n_vec);                                                    \
-            else FIVEEQ_METRICS_LAUNCH1(false, NL, true, 0, n_vec);                                                              \
-        }                                                                                                                        \
-        if (n_vec < n) {                                                                                                         \
-            if (first_call) FIVEEQ_METRICS_LAUNCH1(true, NL, false, n_vec, n - n_vec);                                           \
-            else FIVEEQ_METRICS_LAUNCH1(false, NL, false, n_vec, n - n_vec);                                                     \
-        }                                                                                                                        \
-        break;
-    switch (n_levels) {                                        // a kernel per number of levels (fiveeq_metrics.hpp)
-        FIVEEQ_METRICS_LAUNCH(0) FIVEEQ_METRICS_LAUNCH(1) FIVEEQ_METRICS_LAUNCH(2) FIVEEQ_METRICS_LAUNCH(3) FIVEEQ_METRICS_LAUNCH(4)
-        FIVEEQ_METRICS_LAUNCH(5) FIVEEQ_METRICS_LAUNCH(6) FIVEEQ_METRICS_LAUNCH(7) FIVEEQ_METRICS_LAUNCH(8)
-    }
-#undef FIVEEQ_METRICS_LAUNCH
-#undef FIVEEQ_METRICS_LAUNCH1
+    // every row starts at rows + s scen_stride + k ld
+    const bool wide = !misaligned(rows, 16) && ld % PER16<T> == 0 && (n_scen == 1 || scen_stride % PER16<T> == 0);
+    launch_split(wide_members<T>(wide, n), n, [&](auto vec, int64_t m0, int64_t members) {
+        dispatch_count<0, FIVEEQ_MAX_LEVELS>(n_levels, [&](auto nl) {          // a kernel per number of levels (fiveeq_metrics.hpp)
+            const dim3 grid((unsigned)((members + fiveeq::METRICS_TILE<T> - 1) / fiveeq::METRICS_TILE<T>), (unsigned)n_scen);
+            const auto launch = [&](auto first) {
+                hipLaunchKernelGGL((fiveeq::traj_metrics_kernel<T, decltype(first)::value, decltype(nl)::value, decltype(vec)::value>), grid,
+                                   dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_rows, (int)members, ld, rows + m0, scen_stride, steps, sp,
+                                   fmet + m0, imet + m0);
+            };
+            if (first_call) launch(std::true_type{});
+            else launch(std::false_type{});
+        });
+    });
     HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
 }
@@ -1721,35 +1761,22 @@ namespace {
 template <typename T>
 int joint_check(int64_t n, int32_t n_x, int64_t ld_x, const T* x, int32_t n_y, int64_t ld_y, const T* y, const uint64_t* weights,
                 const double* pivots, const double* partial) {
-    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
+    if (int rc = check_members(n)) return rc;
     if (n_x < 1 || n_x > fiveeq::JOINT_MAX_ROWS) return fail(FIVEEQ_E_INVALID, "n_x=%d outside 1..%d", n_x, fiveeq::JOINT_MAX_ROWS);
     if (n_y < 1 || n_y > fiveeq::JOINT_MAX_ROWS) return fail(FIVEEQ_E_INVALID, "n_y=%d outside 1..%d", n_y, fiveeq::JOINT_MAX_ROWS);
-    if (ld_x < n) return fail(FIVEEQ_E_INVALID, "ld_x=%lld < n_members=%lld", (long long)ld_x, (long long)n);
-    if (ld_y < n) return fail(FIVEEQ_E_INVALID, "ld_y=%lld < n_members=%lld", (long long)ld_y, (long long)n);
-    if (!x) return fail(FIVEEQ_E_INVALID, "x is NULL");
-    if (!y) return fail(FIVEEQ_E_INVALID, "y is NULL");
-    if (!weights) return fail(FIVEEQ_E_INVALID, "weights is NULL");
-    if (!pivots) return fail(FIVEEQ_E_INVALID, "pivots is NULL");
-    if (!partial) return fail(FIVEEQ_E_INVALID, "partial is NULL");
-    if (misaligned(x, sizeof(T))) return fail(FIVEEQ_E_INVALID, "x must be %d-byte aligned", (int)sizeof(T));
-    if (misaligned(y, sizeof(T))) return fail(FIVEEQ_E_INVALID, "y must be %d-byte aligned", (int)sizeof(T));
-    if (misaligned(weights, 8)) return fail(FIVEEQ_E_INVALID, "weights must be 8-byte aligned");
-    if (misaligned(pivots, 8)) return fail(FIVEEQ_E_INVALID, "pivots must be 8-byte aligned");
-    if (misaligned(partial, 8)) return fail(FIVEEQ_E_INVALID, "partial must be 8-byte aligned");
-    return FIVEEQ_OK;
+    if (int rc = check_ld("ld_x", ld_x, n)) return rc;
+    if (int rc = check_ld("ld_y", ld_y, n)) return rc;
+    const NamedPtrs ptrs = {{"x", x, sizeof(T)}, {"y", y, sizeof(T)}, {"weights", weights, 8}, {"pivots", pivots, 8}, {"partial", partial, 8}};
+    if (int rc = check_not_null(ptrs)) return rc;
+    return check_aligned(ptrs);
 }
 template <typename T>
 int joint_moments(int64_t n, int32_t n_x, int64_t ld_x, const T* x, int32_t n_y, int64_t ld_y, const T* y, const uint64_t* weights,
                   const double* pivots, double* partial, double* co, double* margins, uint64_t* info, uint64_t* nanrows, void* stream) {
     if (int rc = joint_check(n, n_x, ld_x, x, n_y, ld_y, y, weights, pivots, partial)) return rc;
-    if (!co) return fail(FIVEEQ_E_INVALID, "co is NULL");
-    if (!margins) return fail(FIVEEQ_E_INVALID, "margins is NULL");
-    if (!info) return fail(FIVEEQ_E_INVALID, "info is NULL");
-    if (!nanrows) return fail(FIVEEQ_E_INVALID, "nanrows is NULL");
-    if (misaligned(co, 8)) return fail(FIVEEQ_E_INVALID, "co must be 8-byte aligned");
-    if (misaligned(margins, 8)) return fail(FIVEEQ_E_INVALID, "margins must be 8-byte aligned");
-    if (misaligned(info, 8)) return fail(FIVEEQ_E_INVALID, "info must be 8-byte aligned");
-    if (misaligned(nanrows, 8)) return fail(FIVEEQ_E_INVALID, "nanrows must be 8-byte aligned");
+    const NamedPtrs ptrs = {{"co", co, 8}, {"margins", margins, 8}, {"info", info, 8}, {"nanrows", nanrows, 8}};
+    if (int rc = check_not_null(ptrs)) return rc;
+    if (int rc = check_aligned(ptrs)) return rc;
     const int64_t chunks = fiveeq_joint_chunks(n), R = n_x + n_y, pairs = (int64_t)n_x * n_y;
     const unsigned tiles = (unsigned)(((n_x + fiveeq::JOINT_TX - 1) / fiveeq::JOINT_TX) * ((n_y + fiveeq::JOINT_TY - 1) / fiveeq::JOINT_TY));
     const hipStream_t st = (hipStream_t)stream;
@@ -1772,13 +1799,9 @@ int cond_sums(int64_t n, int32_t n_x, int64_t ld_x, const T* x, int32_t n_y, int
     if (int rc = joint_check(n, n_x, ld_x, x, n_y, ld_y, y, weights, pivots, partial)) return rc;
     if (n_bins < 1 || n_bins > fiveeq::JOINT_MAX_BINS) return fail(FIVEEQ_E_INVALID, "n_bins=%d outside 1..%d", n_bins, fiveeq::JOINT_MAX_BINS);
     if (n_bins > 1 && !edges) return fail(FIVEEQ_E_INVALID, "edges is NULL with n_bins=%d", n_bins);
-    if (!sums) return fail(FIVEEQ_E_INVALID, "sums is NULL");
-    if (!binw) return fail(FIVEEQ_E_INVALID, "binw is NULL");
-    if (!xnan) return fail(FIVEEQ_E_INVALID, "xnan is NULL");
-    if (misaligned(edges, 8)) return fail(FIVEEQ_E_INVALID, "edges must be 8-byte aligned");
-    if (misaligned(sums, 8)) return fail(FIVEEQ_E_INVALID, "sums must be 8-byte aligned");
-    if (misaligned(binw, 8)) return fail(FIVEEQ_E_INVALID, "binw must be 8-byte aligned");
-    if (misaligned(xnan, 8)) return fail(FIVEEQ_E_INVALID, "xnan must be 8-byte aligned");
+    const NamedPtrs ptrs = {{"edges", edges, 8, false}, {"sums", sums, 8}, {"binw", binw, 8}, {"xnan", xnan, 8}};
+    if (int rc = check_not_null(ptrs)) return rc;
+    if (int rc = check_aligned(ptrs)) return rc;
     const int64_t chunks = fiveeq_joint_chunks(n), cells = (int64_t)n_x * n_bins;
     const unsigned tiles = (unsigned)(n_x * ((n_bins + fiveeq::COND_TB - 1) / fiveeq::COND_TB) * ((n_y + fiveeq::COND_TY - 1) / fiveeq::COND_TY));
     const hipStream_t st = (hipStream_t)stream;
@@ -1849,35 +1872,23 @@ template <typename T>
 int score_rows(int32_t n_q, int32_t n_rows, int64_t n, const T* rows, int64_t row_stride, int64_t q_stride, const int32_t* steps,
                const double* obs, int32_t n_steps, double* misfit, int64_t ld_m, void* stream) {
     if (n_q < 1 || n_q > FIVEEQ_MAX_SCORE_Q) return fail(FIVEEQ_E_INVALID, "n_q=%d outside 1..%d", n_q, FIVEEQ_MAX_SCORE_Q);
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
-    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
-    if (ld_m < n) return fail(FIVEEQ_E_INVALID, "ld_m=%lld < n_members=%lld", (long long)ld_m, (long long)n);
-    if (n_q > 1 && (q_stride < 0 ? -q_stride : q_stride) < n)
-        return fail(FIVEEQ_E_INVALID, "|q_stride|=%lld < n_members=%lld", (long long)(q_stride < 0 ? -q_stride : q_stride), (long long)n);
-    if (n_rows > 1 && row_stride < n) return fail(FIVEEQ_E_INVALID, "row_stride=%lld < n_members=%lld", (long long)row_stride, (long long)n);
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld_m", ld_m, n)) return rc;
+    if (int rc = n_q > 1 ? check_stride("q_stride", q_stride, n) : FIVEEQ_OK) return rc;
+    if (int rc = n_rows > 1 ? check_ld("row_stride", row_stride, n) : FIVEEQ_OK) return rc;
     if (n_steps < 1) return fail(FIVEEQ_E_INVALID, "n_steps=%d must be >= 1", n_steps);
-    if (n_rows > 0 && !rows) return fail(FIVEEQ_E_INVALID, "rows is NULL");
-    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
-    if (!obs) return fail(FIVEEQ_E_INVALID, "obs is NULL");
-    if (!misfit) return fail(FIVEEQ_E_INVALID, "misfit is NULL");
-    if (misaligned(rows, sizeof(T))) return fail(FIVEEQ_E_INVALID, "rows must be %d-byte aligned", (int)sizeof(T));
-    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
-    if (misaligned(obs, 8)) return fail(FIVEEQ_E_INVALID, "obs must be 8-byte aligned");
-    if (misaligned(misfit, 8)) return fail(FIVEEQ_E_INVALID, "misfit must be 8-byte aligned");
+    const NamedPtrs ptrs = {{"rows", rows, sizeof(T), n_rows > 0}, {"steps", steps, 4, n_rows > 0}, {"obs", obs, 8}, {"misfit", misfit, 8}};
+    if (int rc = check_not_null(ptrs)) return rc;
+    if (int rc = check_aligned(ptrs)) return rc;
     if (n_rows == 0) return FIVEEQ_OK;                         // nothing to fold into the accumulators
-    // 16-byte row loads where every lane's address rows + k row_stride + j q_stride + m (m a multiple of the lane's members) is
-    // aligned: the members [0, n_vec) in whole lanes; the ragged tail (fewer members than a lane's) and unaligned rows take the
-    // element loads, in a launch of their own on the columns from n_vec
-    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
-    const bool wide = !misaligned(rows, 16) && (n_rows == 1 || row_stride % per16 == 0) && (n_q == 1 || q_stride % per16 == 0);
-    const int64_t n_vec = wide ? n / per16 * per16 : 0;
-    const auto grid = [](int64_t members) { return dim3((unsigned)((members + fiveeq::SCORE_TILE<T> - 1) / fiveeq::SCORE_TILE<T>)); };
-    if (n_vec > 0)
-        hipLaunchKernelGGL((fiveeq::score_rows_kernel<T, true>), grid(n_vec), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_q, n_rows,
-                           (int)n_vec, rows, row_stride, q_stride, steps, obs, n_steps, misfit, ld_m);
-    if (n_vec < n)
-        hipLaunchKernelGGL((fiveeq::score_rows_kernel<T, false>), grid(n - n_vec), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_q, n_rows,
-                           (int)(n - n_vec), rows + n_vec, row_stride, q_stride, steps, obs, n_steps, misfit + n_vec, ld_m);
+    // every row starts at rows + k row_stride + j q_stride
+    const bool wide = !misaligned(rows, 16) && (n_rows == 1 || row_stride % PER16<T> == 0) && (n_q == 1 || q_stride % PER16<T> == 0);
+    launch_split(wide_members<T>(wide, n), n, [&](auto vec, int64_t m0, int64_t members) {
+        const dim3 grid((unsigned)((members + fiveeq::SCORE_TILE<T> - 1) / fiveeq::SCORE_TILE<T>));
+        hipLaunchKernelGGL((fiveeq::score_rows_kernel<T, decltype(vec)::value>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, n_q, n_rows,
+                           (int)members, rows + m0, row_stride, q_stride, steps, obs, n_steps, misfit + m0, ld_m);
+    });
     HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
 }
@@ -1906,30 +1917,24 @@ int forcing_rows(const fiveeq_model* model, int32_t n_rows, int64_t n, int64_t l
                  void* stream) {
     if (int rc = check_model(model)) return rc;
     const int G = model->n_gas;
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
-    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
-    if (ld < n) return fail(FIVEEQ_E_INVALID, "ld=%lld < n_members=%lld", (long long)ld, (long long)n);
-    if ((F || Fg || Nout || H) && ld_out < n) return fail(FIVEEQ_E_INVALID, "ld_out=%lld < n_members=%lld", (long long)ld_out, (long long)n);
-    if (n_rows > 1 && c_row < n) return fail(FIVEEQ_E_INVALID, "c_row_stride=%lld < n_members=%lld", (long long)c_row, (long long)n);
-    if (G > 1 && (c_gas < 0 ? -c_gas : c_gas) < n)
-        return fail(FIVEEQ_E_INVALID, "|c_gas_stride|=%lld < n_members=%lld", (long long)(c_gas < 0 ? -c_gas : c_gas), (long long)n);
-    if (Trows && n_rows > 1 && t_row < n) return fail(FIVEEQ_E_INVALID, "t_row_stride=%lld < n_members=%lld", (long long)t_row, (long long)n);
+    const bool outs = F || Fg || Nout || H;
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (int rc = outs ? check_ld("ld_out", ld_out, n) : FIVEEQ_OK) return rc;
+    if (int rc = n_rows > 1 ? check_ld("c_row_stride", c_row, n) : FIVEEQ_OK) return rc;
+    if (int rc = G > 1 ? check_stride("c_gas_stride", c_gas, n) : FIVEEQ_OK) return rc;
+    if (int rc = Trows && n_rows > 1 ? check_ld("t_row_stride", t_row, n) : FIVEEQ_OK) return rc;
     if (!Trows && (Nout || H || H_io)) return fail(FIVEEQ_E_INVALID, "N / H / H_io need T_rows: T_rows is NULL");
     if (!Trows && S_io) return fail(FIVEEQ_E_INVALID, "S_io (the replay) needs T_rows: T_rows is NULL");
     if (S_io && !n_mismatch) return fail(FIVEEQ_E_INVALID, "S_io (the replay) needs n_mismatch: n_mismatch is NULL");
-    if (n_fext < 0 || n_fext > fiveeq::MAX_FEXT) return fail(FIVEEQ_E_INVALID, "n_fext=%d outside 0..%d", n_fext, fiveeq::MAX_FEXT);
-    if (n_fext > 0 && fscale && !fext) return fail(FIVEEQ_E_INVALID, "fscale with n_fext=%d categories needs fext: fext is NULL", n_fext);
-    if (n_fext > 0 && fext && !fscale) return fail(FIVEEQ_E_INVALID, "fext with n_fext=%d categories needs fscale: fscale is NULL", n_fext);
-    if (n_fext > 0 && !fscale) return fail(FIVEEQ_E_INVALID, "n_fext=%d without fscale and fext", n_fext);
+    if (int rc = check_fext(n_fext, fscale, fext)) return rc;
     if (n_steps < 1) return fail(FIVEEQ_E_INVALID, "n_steps=%d must be >= 1", n_steps);
-    if (n_rows > 0 && !C) return fail(FIVEEQ_E_INVALID, "C_rows is NULL");
-    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
-    if (!drive) return fail(FIVEEQ_E_INVALID, "drive is NULL");
-    if (!q) return fail(FIVEEQ_E_INVALID, "q is NULL");
+    if (int rc = check_not_null({{"C_rows", C, 1, n_rows > 0}, {"steps", steps, 4, n_rows > 0}, {"drive", drive}, {"q", q}})) return rc;
     const void* elem[] = {C, Trows, drive, q, fscale, fext, F, Fg, Nout, S_io};
     for (const void* p : elem)
         if (misaligned(p, sizeof(T))) return fail(FIVEEQ_E_INVALID, "a row pointer (%p) is not %d-byte aligned", p, (int)sizeof(T));
-    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
+    if (int rc = check_aligned({{"steps", steps, 4}})) return rc;
     if (misaligned(H, 8) || misaligned(H_io, 8) || misaligned(n_mismatch, 8))
         return fail(FIVEEQ_E_INVALID, "H, H_io and n_mismatch must be 8-byte aligned");
     if (n_rows == 0) return FIVEEQ_OK;                         // no row: no output row, and the carried state stays what it is
@@ -1941,19 +1946,13 @@ int forcing_rows(const fiveeq_model* model, int32_t n_rows, int64_t n, int64_t l
     a.steps = steps, a.drive = drive, a.q = q, a.fs = fscale, a.X = fscale ? fext : nullptr, a.ld = ld;
     a.F = F, a.Fg = Fg, a.N = Nout, a.H = H, a.ld_out = ld_out, a.H_io = H_io, a.S_io = S_io;
     a.n_mismatch = reinterpret_cast<unsigned long long*>(n_mismatch), a.dt = model->dt;
-    // 16-byte accesses where every lane's address of every row read or written (m a multiple of the lane's members) is aligned:
-    // the members [0, n_vec) in whole lanes; the ragged tail (fewer members than a lane's) and unaligned rows take the element
-    // accesses, in a launch of their own on the columns from n_vec
-    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
-    const bool outs = F || Fg || Nout || H;
     const bool wide = !misaligned(C, 16) && !misaligned(a.Trows, 16) && !misaligned(F, 16) && !misaligned(Fg, 16) &&
-                      !misaligned(Nout, 16) && !misaligned(H, 16) && a.c_row % per16 == 0 && a.c_gas % per16 == 0 &&
-                      (!a.Trows || a.t_row % per16 == 0) && (!outs || ld_out % per16 == 0);
-    const int64_t n_vec = wide ? n / per16 * per16 : 0;
+                      !misaligned(Nout, 16) && !misaligned(H, 16) && a.c_row % PER16<T> == 0 && a.c_gas % PER16<T> == 0 &&
+                      (!a.Trows || a.t_row % PER16<T> == 0) && (!outs || ld_out % PER16<T> == 0);
     const KModel<T> km = make_kmodel<T>(model);
     const unsigned gy = seq ? 1u : (unsigned)((n_rows + fiveeq::FORCROWS_YROWS - 1) / fiveeq::FORCROWS_YROWS);
     if (gy > 65535u) return fail(FIVEEQ_E_INVALID, "n_rows=%d too many for one row-parallel launch: at most %d", n_rows, 65535 * fiveeq::FORCROWS_YROWS);
-    const auto launch = [&](auto vec, int64_t m0, int64_t members) {
+    launch_split(wide_members<T>(wide, n), n, [&](auto vec, int64_t m0, int64_t members) {
         fiveeq::ForcRowsArgs<T> b = a;
         b.n = (int)members;
         b.C += m0, b.q += m0;
@@ -1969,9 +1968,7 @@ int forcing_rows(const fiveeq_model* model, int32_t n_rows, int64_t n, int64_t l
         constexpr bool VEC = decltype(vec)::value;
         if (seq) hipLaunchKernelGGL((fiveeq::forcing_rows_kernel<T, VEC, true>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
         else hipLaunchKernelGGL((fiveeq::forcing_rows_kernel<T, VEC, false>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
-    };
-    if (n_vec > 0) launch(std::true_type{}, 0, n_vec);
-    if (n_vec < n) launch(std::false_type{}, n_vec, n - n_vec);
+    });
     HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
 }
@@ -2007,12 +2004,11 @@ int pulse_response(const fiveeq_model* model, int32_t n_scen, int32_t n_rows, in
                    double* out, int64_t ld_out, double* io, void* stream) {
     if (int rc = check_model(model)) return rc;
     const int G = model->n_gas;
-    const auto mag = [](int64_t v) { return v < 0 ? -v : v; };
-    if (n_rows < 0) return fail(FIVEEQ_E_INVALID, "n_rows=%d must be >= 0", n_rows);
+    if (int rc = check_n_rows(n_rows)) return rc;
     if (row0 < 0 || row0 > INT32_MAX - n_rows) return fail(FIVEEQ_E_INVALID, "row0=%d with n_rows=%d outside 0..2^31-1", row0, n_rows);
-    if (n < 1 || n > RESAMPLE_MAX) return fail(FIVEEQ_E_INVALID, "n_members=%lld outside 1..2^31-1", (long long)n);
-    if (ld < n) return fail(FIVEEQ_E_INVALID, "ld=%lld < n_members=%lld", (long long)ld, (long long)n);
-    if (ld_out < n) return fail(FIVEEQ_E_INVALID, "ld_out=%lld < n_members=%lld", (long long)ld_out, (long long)n);
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (int rc = check_ld("ld_out", ld_out, n)) return rc;
     if (n_scen < 2) return fail(FIVEEQ_E_INVALID, "n_scen=%d: a base scenario and at least one pulse scenario are needed", n_scen);
     if (n_pulses < 1 || n_pulses > FIVEEQ_MAX_PULSES) return fail(FIVEEQ_E_INVALID, "n_pulses=%d outside 1..%d", n_pulses, FIVEEQ_MAX_PULSES);
     if (n_hor < 1 || n_hor > FIVEEQ_MAX_HORIZONS) return fail(FIVEEQ_E_INVALID, "n_horizons=%d outside 1..%d", n_hor, FIVEEQ_MAX_HORIZONS);
@@ -2030,26 +2026,20 @@ int pulse_response(const fiveeq_model* model, int32_t n_scen, int32_t n_rows, in
         if (h > 0 && horizons[h] <= horizons[h - 1])
             return fail(FIVEEQ_E_INVALID, "horizons must be strictly increasing: horizon %d is %d after %d", h, horizons[h], horizons[h - 1]);
     }
-    if (n_rows > 1 && c_row < n) return fail(FIVEEQ_E_INVALID, "c_row_stride=%lld < n_members=%lld", (long long)c_row, (long long)n);
-    if (G > 1 && mag(c_gas) < n) return fail(FIVEEQ_E_INVALID, "|c_gas_stride|=%lld < n_members=%lld", (long long)mag(c_gas), (long long)n);
-    if (mag(c_scen) < n) return fail(FIVEEQ_E_INVALID, "|c_scen_stride|=%lld < n_members=%lld", (long long)mag(c_scen), (long long)n);
-    if (n_rows > 1 && t_row < n) return fail(FIVEEQ_E_INVALID, "t_row_stride=%lld < n_members=%lld", (long long)t_row, (long long)n);
-    if (mag(t_scen) < n) return fail(FIVEEQ_E_INVALID, "|t_scen_stride|=%lld < n_members=%lld", (long long)mag(t_scen), (long long)n);
-    if (n_fext < 0 || n_fext > fiveeq::MAX_FEXT) return fail(FIVEEQ_E_INVALID, "n_fext=%d outside 0..%d", n_fext, fiveeq::MAX_FEXT);
-    if (n_fext > 0 && fscale && !fext) return fail(FIVEEQ_E_INVALID, "fscale with n_fext=%d categories needs fext: fext is NULL", n_fext);
-    if (n_fext > 0 && fext && !fscale) return fail(FIVEEQ_E_INVALID, "fext with n_fext=%d categories needs fscale: fscale is NULL", n_fext);
-    if (n_fext > 0 && !fscale) return fail(FIVEEQ_E_INVALID, "n_fext=%d without fscale and fext", n_fext);
+    if (int rc = n_rows > 1 ? check_ld("c_row_stride", c_row, n) : FIVEEQ_OK) return rc;
+    if (int rc = G > 1 ? check_stride("c_gas_stride", c_gas, n) : FIVEEQ_OK) return rc;
+    if (int rc = check_stride("c_scen_stride", c_scen, n)) return rc;
+    if (int rc = n_rows > 1 ? check_ld("t_row_stride", t_row, n) : FIVEEQ_OK) return rc;
+    if (int rc = check_stride("t_scen_stride", t_scen, n)) return rc;
+    if (int rc = check_fext(n_fext, fscale, fext)) return rc;
     if (n_steps < 1) return fail(FIVEEQ_E_INVALID, "n_steps=%d must be >= 1", n_steps);
-    if (n_rows > 0 && !C) return fail(FIVEEQ_E_INVALID, "C_rows is NULL");
-    if (n_rows > 0 && !Trows) return fail(FIVEEQ_E_INVALID, "T_rows is NULL");
-    if (n_rows > 0 && !steps) return fail(FIVEEQ_E_INVALID, "steps is NULL");
-    if (!drive) return fail(FIVEEQ_E_INVALID, "drive is NULL");
-    if (!out) return fail(FIVEEQ_E_INVALID, "out is NULL");
-    if (!io) return fail(FIVEEQ_E_INVALID, "io is NULL");
+    if (int rc = check_not_null({{"C_rows", C, 1, n_rows > 0}, {"T_rows", Trows, 1, n_rows > 0}, {"steps", steps, 4, n_rows > 0},
+                                 {"drive", drive}, {"out", out}, {"io", io}}))
+        return rc;
     const void* elem[] = {C, Trows, drive, fscale, fext};
     for (const void* p : elem)
         if (misaligned(p, sizeof(T))) return fail(FIVEEQ_E_INVALID, "a row pointer (%p) is not %d-byte aligned", p, (int)sizeof(T));
-    if (misaligned(steps, 4)) return fail(FIVEEQ_E_INVALID, "steps must be 4-byte aligned");
+    if (int rc = check_aligned({{"steps", steps, 4}})) return rc;
     if (misaligned(out, 8) || misaligned(io, 8)) return fail(FIVEEQ_E_INVALID, "out and io must be 8-byte aligned");
     if (n_rows == 0) return FIVEEQ_OK;                         // no row: nothing is written, and the carried sums stay what they are
     fiveeq::PulseArgs<T> a;
@@ -2064,26 +2054,21 @@ int pulse_response(const fiveeq_model* model, int32_t n_scen, int32_t n_rows, in
     a.Trows = Trows, a.t_scen = t_scen, a.t_row = n_rows > 1 ? t_row : 0;
     a.steps = steps, a.drive = drive, a.fs = fscale, a.X = fscale ? fext : nullptr, a.ld = ld;
     a.out = out, a.ld_out = ld_out, a.io = io;
-    // 16-byte accesses where every lane's address of every row read or written is aligned (as in forcing_rows above): the
-    // members [0, n_vec) in whole lanes; the ragged tail and unaligned rows take the element accesses in a launch of their own
-    constexpr int64_t per16 = 16 / (int64_t)sizeof(T);
-    const bool wide = !misaligned(C, 16) && !misaligned(Trows, 16) && !misaligned(out, 16) && a.c_scen % per16 == 0 &&
-                      a.c_row % per16 == 0 && a.c_gas % per16 == 0 && a.t_scen % per16 == 0 && a.t_row % per16 == 0 && ld_out % 2 == 0;
-    const int64_t n_vec = wide ? n / per16 * per16 : 0;
+    const bool wide = !misaligned(C, 16) && !misaligned(Trows, 16) && !misaligned(out, 16) && a.c_scen % PER16<T> == 0 &&
+                      a.c_row % PER16<T> == 0 && a.c_gas % PER16<T> == 0 && a.t_scen % PER16<T> == 0 && a.t_row % PER16<T> == 0 &&
+                      ld_out % 2 == 0;
     const KModel<T> km = make_kmodel<T>(model);
-    const auto launch = [&](auto vec, int64_t m0, int64_t members) {
+    launch_split(wide_members<T>(wide, n), n, [&](auto vec, int64_t m0, int64_t members) {
         fiveeq::PulseArgs<T> b = a;
         b.n = (int)members;
         b.C += m0, b.Trows += m0, b.out += m0, b.io += m0;
         if (b.fs) b.fs += m0;
         const dim3 grid((unsigned)((members + fiveeq::METRICS_TILE<T> - 1) / fiveeq::METRICS_TILE<T>));
-        constexpr bool VEC = decltype(vec)::value;
-        if (n_pulses == 1) hipLaunchKernelGGL((fiveeq::pulse_response_kernel<T, VEC, 1>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
-        else if (n_pulses == 2) hipLaunchKernelGGL((fiveeq::pulse_response_kernel<T, VEC, 2>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
-        else hipLaunchKernelGGL((fiveeq::pulse_response_kernel<T, VEC, 3>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
-    };
-    if (n_vec > 0) launch(std::true_type{}, 0, n_vec);
-    if (n_vec < n) launch(std::false_type{}, n_vec, n - n_vec);
+        dispatch_count<1, FIVEEQ_MAX_PULSES>(n_pulses, [&](auto np) {
+            hipLaunchKernelGGL((fiveeq::pulse_response_kernel<T, decltype(vec)::value, decltype(np)::value>), grid, dim3(FIVEEQ_BLOCK), 0,
+                               (hipStream_t)stream, km, b);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
 }

@@ -5,7 +5,8 @@ refusals and the rows downstream in constrain.score_rows.
 
 Shapes: 24 steps, every step stored; N in {1, 3, 63, 64, 65, 129, 131} — the tails of 2- and 4-member lanes and of a wave —
 as the engine lays them out (row stride N) and embedded in rows of stride N + 5 (odd for even N: the element-access path) and
-of a stride that is a multiple of 4 (16-byte accesses with a ragged tail)."""
+of a stride that is a multiple of 4 (16-byte accesses with a ragged tail); and once one workgroup tile plus three members,
+where one call makes the 16-byte and the element launch, beside the same rows from a base one element off."""
 import functools
 
 import numpy as np
@@ -237,6 +238,55 @@ def test_outputs_do_not_depend_on_member_range_stride_split_or_launch_form(sfx, 
         for ld in _strides(N):
             assert torch.equal(_diag(eng, ld, want=("F",)).F, base.F), ld
             assert torch.equal(_diag(eng, ld, want=("F", "N", "H")).F, base.F), ld
+
+
+def _embed_at(t, ld, off):
+    """t [.., N] as the first N columns of rows of stride ld that begin `off` elements into a 16-byte aligned buffer."""
+    lead = tuple(t.shape[:-1])
+    flat = torch.full((off + int(np.prod(lead)) * ld,), float("nan"), dtype=t.dtype, device=t.device)
+    view = flat[off:].view(lead + (ld,))[..., :t.shape[-1]]
+    view.copy_(t)
+    assert flat.data_ptr() % 16 == 0 and view.data_ptr() == flat.data_ptr() + off * t.element_size()
+    return view
+
+
+@pytest.mark.parametrize("sfx", ["f64", "f32"])
+def test_a_tile_and_three_members_in_both_launches_and_from_a_base_one_element_off(sfx):
+    """One workgroup tile plus three members, rows of a stride that is a multiple of 16 bytes: aligned rows give the 16-byte
+    launch on [0, n_vec) and the element launch on the three (fp64: one) members from n_vec > 0 in ONE call; the same rows one
+    element into the buffer give the element launch alone.  Both replay the stored T in every bit and end in the engine's S,
+    agree with each other in every bit of F, F_gas, N and H, and give N and H of the twin fed the device's F; fp64 F and F_gas
+    against the oracle at the bound of test_forcing_values (its fp32 bound is a measurement over that test's own cases)."""
+    from fiveeqscm_amd import _capi
+    from fiveeqscm_amd.engine import EnsembleEngine
+    width = 8 if sfx == "f64" else 4
+    per16, tile = 16 // width, int(_capi.load().fiveeq_forcing_rows_tile(width))
+    N = tile + 3
+    ld = (N + 3) // 4 * 4 + 4
+    assert N // per16 * per16 >= tile and N % per16 != 0 and ld % per16 == 0
+    base = params.default_params("multigas")
+    p = params.sample_ensemble_shard(base, N, 0, N)
+    sc = params.sample_forcing_scales(base, N, 0, N, ranges=[(0.8, 1.2)] * 3 + [(0.3, 2.0), (0.5, 1.5)])
+    p["f_scale"], p["fx_scale"] = sc[:3], sc[3:]
+    eng = EnsembleEngine(p, N, _emissions("multigas"), dtype=DTYPES[sfx], device="cuda:0", forcing=ExternalForcings(_table()))
+    eng.run(mode="per_step")
+    torch.cuda.synchronize()
+    names = ("F", "F_gas", "N", "H")
+    res = {}
+    for off in (0, 1):
+        put = lambda t: _embed_at(t, ld, off)                                                 # noqa: E731
+        res[off] = r = diagnose.forcing_rows(put(eng.C), eng.out_steps, eng.params, q=put(eng.q), F_ext=eng.drive, dt=eng.dt,
+                                             T_rows=put(eng.T), fscale=put(eng.fscale), X=eng.fext, want=names,
+                                             S_begin=torch.zeros_like(eng.S))
+        assert r.replay_mismatches == 0 and torch.equal(r.S_end, eng.S), off
+        Nn = twin.imbalance(r.F.cpu().numpy(), eng.T.cpu().numpy(), eng.q.cpu().numpy())
+        assert torch.equal(r.N.cpu(), torch.from_numpy(Nn)) and torch.equal(r.H.cpu(), torch.from_numpy(twin.heat(Nn, eng.dt))), off
+    for name in names:
+        assert torch.equal(getattr(res[0], name), getattr(res[1], name)), name
+    if sfx == "f64":
+        ref_g, ref = _oracle_forcing(eng)
+        for got, want in ((res[0].F, ref), (res[0].F_gas, ref_g)):
+            assert np.all(np.abs(got.cpu().numpy() - want) <= 1e-10 * np.abs(want) + 1e-13)
 
 
 # ---- 5. rows by hand ----------------------------------------------------------------------------------------------------------
