@@ -171,7 +171,7 @@ def test_hfc_conc_kernel_matches_reference_golden(gpu, golden_hfc):
 def test_hfc_conc_kernel_ragged_sizes(gpu):
     from fiveeqscm_amd.concentrations import calculate_hfc_conc_ensemble
     rng = np.random.default_rng(5)
-    for N, K in ((1, 1), (63, 5), (257, 300), (1000, 513)):
+    for N, K in ((1, 1), (63, 5), (257, 300), (1000, 513), (256, 256), (257, 512)):
         e0 = rng.normal(size=N) * 10
         time = rng.uniform(-2, 30, size=K)
         out = calculate_hfc_conc_ensemble(e0, time).cpu().numpy()
