@@ -8,8 +8,6 @@ is read, `time` is an absolute coordinate, empty `emissions` raises IndexError. 
 NumPy-in / NumPy-out and CPU-only, like the reference (BASELINE.json configs[0]:
 "plumbing, no GPU").
 """
-import ctypes
-
 import numpy as np
 
 
@@ -25,6 +23,7 @@ def calculate_hfc_conc_ensemble(e0, time, device=None):
     import torch
 
     from . import _capi
+    from ._rowargs import call, ptr
 
     lib = _capi.load()
     if not torch.cuda.is_available():
@@ -36,11 +35,7 @@ def calculate_hfc_conc_ensemble(e0, time, device=None):
     tm = torch.as_tensor(np.asarray(time, dtype=np.float64)).reshape(-1).to(dev).contiguous()
     N, K = e0_t.numel(), tm.numel()
     out = torch.empty((K, N), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.fiveeq_hfc_conc_f64(N, N, K, ctypes.c_void_p(e0_t.data_ptr()), ctypes.c_void_p(tm.data_ptr()),
-                                     ctypes.c_void_p(out.data_ptr()),
-                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _capi.check(lib, rc)
+    call(lib, _capi, "fiveeq_hfc_conc", torch.float64, dev, N, N, K, ptr(e0_t), ptr(tm), ptr(out))
     return out
 
 

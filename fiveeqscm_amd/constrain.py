@@ -178,9 +178,9 @@ def score_rows(rows, steps, observations, acc=None):
     (p_t = b_t = 0) are neither read nor do their values matter.  acc: the result of an earlier call over EARLIER rows of the
     same members — the call continues a copy of it, and the result is that of one call over all the rows.  chi2 of quantity
     j: chi2_from_misfit(out[j], observations[j].P).  Runs on the current stream; there is no CPU path."""
-    import ctypes
-
     import torch
+
+    from . import _rowargs
     single = isinstance(observations, Observations)
     recs = [observations] if single else list(observations)
     if not recs or not all(isinstance(o, Observations) for o in recs):
@@ -202,14 +202,7 @@ def score_rows(rows, steps, observations, acc=None):
     n_steps = recs[0].n_steps
     if any(o.n_steps != n_steps for o in recs):
         raise ValueError(f"observations: tables of {[o.n_steps for o in recs]} steps, want equal n_steps")
-    st = np.asarray(steps)
-    if st.shape != (K,) or (K and not np.issubdtype(st.dtype, np.integer)):
-        raise ValueError(f"steps: want {K} integers, one per row")
-    st = st.astype(np.int64)
-    if K and np.any(np.diff(st) <= 0):
-        raise ValueError("steps: want strictly increasing model steps")
-    if K and (st[0] < 0 or st[-1] >= n_steps):
-        raise ValueError(f"steps: {int(st[0])}..{int(st[-1])} outside the tables' steps 0..{n_steps - 1}")
+    st = _rowargs.model_steps(steps, K, n_steps=n_steps)
     dev = rows.device
     out_shape = (3, N) if single else (Q, 3, N)
     if acc is None:
@@ -218,20 +211,13 @@ def score_rows(rows, steps, observations, acc=None):
         if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float64 or tuple(acc.shape) != out_shape or acc.device != dev:
             raise ValueError(f"acc: want an fp64 tensor of shape {list(out_shape)} on {dev}")
         misfit = acc.reshape(Q, 3, N).clone()
-    # rows the kernel walks in place: unit column stride, rows and quantities at least N apart (a row stride of 0 — an expanded
-    # view — is not)
-    if (N > 1 and x.stride(2) != 1) or (K > 1 and x.stride(0) < N) or (Q > 1 and abs(x.stride(1)) < N):
-        x = x.contiguous()
-    row_stride = int(x.stride(0)) if K > 1 else N
-    q_stride = int(x.stride(1)) if Q > 1 else N
+    x, (row_stride, q_stride) = _rowargs.walk_in_place(x, N)
     lib, capi, stream, guard = _lib_and_stream(rows)
-    st32 = torch.from_numpy(st.astype(np.int32)).to(dev)
+    st32 = _rowargs.steps_i32(st, dev)
     obs = torch.from_numpy(np.stack([o.table for o in recs])).to(dev)          # [Q, n_steps, 4]
-    fn = lib.fiveeq_score_rows_f64 if rows.dtype == torch.float64 else lib.fiveeq_score_rows_f32
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())                  # noqa: E731
-    with guard:
-        capi.check(lib, fn(Q, K, N, ptr(x) if K else None, row_stride, q_stride, ptr(st32) if K else None, ptr(obs), n_steps,
-                           ptr(misfit), N, stream))
+    ptr = _rowargs.ptr
+    _rowargs.call(lib, capi, "fiveeq_score_rows", rows.dtype, dev, Q, K, N, ptr(x) if K else None, row_stride, q_stride,
+                  ptr(st32) if K else None, ptr(obs), n_steps, ptr(misfit), N, stream=stream, guard=guard)
     return misfit[0] if single else misfit
 
 
@@ -403,19 +389,14 @@ class Resample:
             raise ValueError(f"gather: rows on {rows.device}, but the plan's indices are not (resample device weights there)")
         if rows.dtype not in (torch.float64, torch.float32) or not rows.is_contiguous():
             raise ValueError("gather: want contiguous fp64 or fp32 rows")
-        import ctypes
-
         from . import _capi
+        from ._rowargs import call, ptr
         lib = _capi.load()
         M, N = self.n_members, self.n_source
         out = torch.empty(tuple(rows.shape[:-1]) + (M,), dtype=rows.dtype, device=rows.device)
         n_rows = rows.numel() // N
         if M and n_rows:
-            fn = lib.fiveeq_gather_rows_f64 if rows.dtype == torch.float64 else lib.fiveeq_gather_rows_f32
-            p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
-            with torch.cuda.device(rows.device):
-                st = ctypes.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
-                _capi.check(lib, fn(n_rows, M, N, p(rows), M, p(out), p(self.src), st))
+            call(lib, _capi, "fiveeq_gather_rows", rows.dtype, rows.device, n_rows, M, N, ptr(rows), M, ptr(out), ptr(self.src))
         return out
 
     def gather_params(self, params):
@@ -466,17 +447,13 @@ def resample(weights, n_out=None, seed=None, group=None):
     if flag:
         pass                                                   # nothing is scanned: the refusal follows the exchange
     elif on_gpu and n:
-        import ctypes
-
         from . import _capi
+        from ._rowargs import call, ptr
         lib = _capi.load()
         w = w.to(torch.int64).contiguous()
         cum = torch.empty(n + 1, dtype=torch.int64, device=w.device)       # the scan, and behind it the flag word
         work = torch.empty(int(lib.fiveeq_wscan_chunks(n)), dtype=torch.int64, device=w.device)
-        p = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + 8 * off)      # noqa: E731
-        with torch.cuda.device(w.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
-            _capi.check(lib, lib.fiveeq_wscan(n, p(w), p(work), p(cum), p(cum, n), st))
+        call(lib, _capi, "fiveeq_wscan", None, w.device, n, ptr(w), ptr(work), ptr(cum), ptr(cum[n:]))
         local_sum, flag = (int(v) for v in cum[n - 1:].cpu())                # bit 1: a weight outside [0, 2^32]
         cum = cum[:n]
     elif n:
@@ -515,8 +492,7 @@ def resample(weights, n_out=None, seed=None, group=None):
     if on_gpu:
         src = torch.empty(mine_out, dtype=torch.int32, device=w.device)
         if mine_out:
-            with torch.cuda.device(w.device):
-                _capi.check(lib, lib.fiveeq_resample_pick(n, p(cum), *args, p(src), st))
+            call(lib, _capi, "fiveeq_resample_pick", None, w.device, n, ptr(cum), *args, ptr(src))
     else:
         src = _resample_host.pick(cum, *args) if mine_out else np.zeros(0, dtype=np.int32)
         if on_torch:

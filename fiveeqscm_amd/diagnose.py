@@ -75,6 +75,7 @@ def forcing_rows(C_rows, steps, params, *, q, F_ext, dt, T_rows=None, fscale=Non
     import torch
 
     from . import _capi
+    from ._rowargs import call, dev_rows, drive_table, forcing_tables, model_steps, ptr, steps_i32, steps_in_tables, walk_in_place
     from .forcing import ExternalForcings
     from .params import make_model
     want = tuple(want)
@@ -92,12 +93,7 @@ def forcing_rows(C_rows, steps, params, *, q, F_ext, dt, T_rows=None, fscale=Non
         raise ValueError(f"C_rows hold {G} gases, params {int(model.n_gas)}")
     if N < 1:
         raise ValueError("C_rows: no members")
-    st = np.asarray(steps)
-    if st.shape != (K,) or (K and not np.issubdtype(st.dtype, np.integer)):
-        raise ValueError(f"steps: want {K} integers, one per row")
-    st = st.astype(np.int64)
-    if K and np.any(np.diff(st) <= 0):
-        raise ValueError("steps: want strictly increasing model steps")
+    st = model_steps(steps, K)
     need_T = "N" in want or "H" in want or S_begin is not None or heat0 is not None
     if need_T and T_rows is None:
         raise ValueError("N, H and the replay need T_rows")
@@ -106,64 +102,32 @@ def forcing_rows(C_rows, steps, params, *, q, F_ext, dt, T_rows=None, fscale=Non
     if S_begin is not None:
         check_consecutive(st, "the replay")
 
-    def dev_rows(t, shape, name, dtype=dtp):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype:
-            raise ValueError(f"{name}: want a {dtype} tensor of shape {list(shape)}")
-        if not t.is_cuda:
-            raise TypeError(f"{name} must be on the GPU (got {t.device}): there is no CPU path")
-        if t.device != dev:
-            raise ValueError(f"{name}: on {t.device}, the rows on {dev}")
-        return t
-
     # the shared tables: F_ext as a drive table, X padded to the C ABI's four columns
-    if isinstance(F_ext, torch.Tensor) and F_ext.dim() == 2:
-        drive = dev_rows(F_ext, (int(F_ext.shape[0]), _capi.DRIVE_STRIDE), "F_ext (a drive table)").contiguous()
-    else:
-        fe = np.asarray(F_ext.cpu() if isinstance(F_ext, torch.Tensor) else F_ext, dtype=np.float64).reshape(-1)
-        table = np.zeros((fe.size, _capi.DRIVE_STRIDE))
-        table[:, 6] = fe
-        drive = torch.from_numpy(table).to(dev, dtp)
+    drive = drive_table(F_ext, (), "F_ext (a drive table)", dtp, dev)
     n_steps = int(drive.shape[0])
-    if K and (st[0] < 0 or st[-1] >= n_steps):
-        raise ValueError(f"steps: {int(st[0])}..{int(st[-1])} outside the tables' steps 0..{n_steps - 1}")
-    if (fscale is None) != (X is None):
-        raise ValueError("fscale and X come together: the scale rows and the category table of a forcing= run (a table without "
-                         "categories will do)")
-    n_fext, fext = 0, None
-    if fscale is not None:
-        if isinstance(X, torch.Tensor):
-            n_fext = int(fscale.shape[0]) - G
-            fext = dev_rows(X, (n_steps, _capi.MAX_FEXT), "X (a device table)").contiguous()
-        else:
-            fx = X if isinstance(X, ExternalForcings) else ExternalForcings(np.asarray(X, dtype=np.float64).reshape(n_steps, -1))
-            if fx.n_steps != n_steps:
-                raise ValueError(f"X: table of {fx.n_steps} steps, F_ext of {n_steps}")
-            n_fext = fx.n_categories
-            fext = torch.from_numpy(fx.padded()).to(dev, dtp)
-        if not 0 <= n_fext <= _capi.MAX_FEXT:
-            raise ValueError(f"fscale: {int(fscale.shape[0])} rows for {G} gases: want G + K rows, K <= {_capi.MAX_FEXT}")
-        fscale = dev_rows(fscale, (G + n_fext, N), "fscale")
-    q = dev_rows(q, (2, N), "q")
+    steps_in_tables(st, n_steps)
+
+    def host_table(X):
+        fx = X if isinstance(X, ExternalForcings) else ExternalForcings(np.asarray(X, dtype=np.float64).reshape(n_steps, -1))
+        if fx.n_steps != n_steps:
+            raise ValueError(f"X: table of {fx.n_steps} steps, F_ext of {n_steps}")
+        return fx
+
+    n_fext, fext, fscale = forcing_tables(
+        fscale, X, (), G, N, n_steps, dtp, dev, x_name="X (a device table)", host_table=host_table,
+        together="fscale and X come together: the scale rows and the category table of a forcing= run (a table without "
+                 "categories will do)")
     # per-member rows the kernel reads with ONE row stride ld: q as it lies when its columns are contiguous, the scales and
     # the carried state laid out to match
-    if N > 1 and q.stride(1) != 1 or q.stride(0) < N:
-        q = q.contiguous()
-    ld = int(q.stride(0))
+    q, (ld,) = walk_in_place(dev_rows(q, (2, N), "q", dtp, dev), N)
     if fscale is not None and (fscale.stride(0) != ld or (N > 1 and fscale.stride(1) != 1)):
         buf = torch.empty((G + n_fext, ld), dtype=dtp, device=dev)[:, :N]
         buf.copy_(fscale)
         fscale = buf
-    # rows the kernel walks in place: unit member stride, rows and gases at least N apart
-    x = C_rows
-    if (N > 1 and x.stride(2) != 1) or (K > 1 and x.stride(0) < N) or (G > 1 and abs(x.stride(1)) < N):
-        x = x.contiguous()
-    c_row, c_gas = (int(x.stride(0)) if K > 1 else N), (int(x.stride(1)) if G > 1 else N)
+    x, (c_row, c_gas) = walk_in_place(C_rows, N)
     tr, t_row = None, N
     if need_T:
-        tr = dev_rows(T_rows, (K, N), "T_rows")
-        if (N > 1 and tr.stride(1) != 1) or (K > 1 and tr.stride(0) < N):
-            tr = tr.contiguous()
-        t_row = int(tr.stride(0)) if K > 1 else N
+        tr, (t_row,) = walk_in_place(dev_rows(T_rows, (K, N), "T_rows", dtp, dev), N)
     res = ForcingRows()
     # every output row starts 16-byte aligned: one row length for all of them, N rounded up to 16 bytes of the rows' type
     per16 = 16 // x.element_size()
@@ -177,20 +141,15 @@ def forcing_rows(C_rows, steps, params, *, q, F_ext, dt, T_rows=None, fscale=Non
     if "H" in want or heat0 is not None:
         H_io = torch.zeros((ld,), dtype=torch.float64, device=dev)[:N]
         if heat0 is not None:
-            H_io.copy_(dev_rows(heat0, (N,), "heat0", torch.float64))
+            H_io.copy_(dev_rows(heat0, (N,), "heat0", torch.float64, dev))
     if S_begin is not None:
         S_io = torch.empty((2, ld), dtype=dtp, device=dev)[:, :N]
-        S_io.copy_(dev_rows(S_begin, (2, N), "S_begin"))
+        S_io.copy_(dev_rows(S_begin, (2, N), "S_begin", dtp, dev))
         mism = torch.zeros((1,), dtype=torch.int64, device=dev)
-    lib = _capi.load()
-    fn = lib.fiveeq_forcing_rows_f64 if dtp == torch.float64 else lib.fiveeq_forcing_rows_f32
-    ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())           # noqa: E731
-    st32 = torch.from_numpy(st.astype(np.int32)).to(dev)
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(lib, fn(ctypes.byref(model), K, N, ld, ptr(x) if K else None, c_row, c_gas, ptr(tr) if K else None, t_row,
-                            ptr(st32) if K else None, ptr(drive), n_steps, ptr(q), ptr(fscale), n_fext, ptr(fext), ptr(res.F),
-                            ptr(res.F_gas), ptr(res.N), ptr(res.H), ld_out, ptr(H_io), ptr(S_io), ptr(mism), stream))
+    st32 = steps_i32(st, dev)
+    call(_capi.load(), _capi, "fiveeq_forcing_rows", dtp, dev, ctypes.byref(model), K, N, ld, ptr(x) if K else None, c_row, c_gas,
+         ptr(tr) if K else None, t_row, ptr(st32) if K else None, ptr(drive), n_steps, ptr(q), ptr(fscale), n_fext, ptr(fext),
+         ptr(res.F), ptr(res.F_gas), ptr(res.N), ptr(res.H), ld_out, ptr(H_io), ptr(S_io), ptr(mism))
     if S_io is not None:
         res.S_end = S_io
         res.replay_mismatches = int(mism.item())

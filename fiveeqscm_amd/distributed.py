@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _capi            # (importing it binds nothing: the library is opened by _capi.load(), in _lib_and_stream)
+from ._rowargs import int_weights
 
 
 def shard_bounds(n_total, rank, world):
@@ -690,10 +691,7 @@ def gather_weighted_summary(rows, weights, percentiles=(5.0, 50.0, 95.0), dst=0,
     if rows.shape[1] > 0 and (rows.stride(1) != 1 or rows.stride(0) < rows.shape[1]):      # rows of a wider buffer are read in place
         rows = rows.contiguous()
     _need_device_rows(rows)
-    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or weights.device != rows.device \
-            or tuple(weights.shape) != (rows.shape[1],):
-        raise ValueError(f"weights: want an int64 tensor of shape [{rows.shape[1]}] on {rows.device}")
-    weights = weights.contiguous()
+    weights = int_weights(weights, rows.shape[1], rows.device, check_range=False).contiguous()
     P = len(percentiles)
     if P < 1:
         raise ValueError("no percentiles asked for")

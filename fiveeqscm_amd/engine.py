@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._rowargs import bool_mask, int_weights
 from .checkpoint import CheckpointMixin
 from .emissions import emissions_sha256, make_drive, make_scenario_drive
 from .forcing import ScenarioForcings
@@ -82,6 +83,21 @@ def _rows(x, K, N, name):
     if x.shape != (K, N):
         raise ValueError(f"{name}: shape {x.shape}, want [{K}] or [{K},{N}]")
     return x
+
+
+def _joined(eng, stream=None):
+    """Before a reader looks at the engine's rows: `stream` (default: the current one) waits for what run(..., join=False) left
+    outstanding.  (A function: the CPU tests call the readers on a stub engine that has no join().)"""
+    if eng._ps_unjoined:
+        eng.join(stream)
+
+
+def _stored_rows_slice(rows):
+    """rows= of a reader of the stored rows, as a slice."""
+    sel = slice(None) if rows is None else rows
+    if not isinstance(sel, slice) or sel.step not in (None, 1):
+        raise ValueError("rows: want a slice of the stored rows with step 1 (or None for all)")
+    return sel
 
 
 def _is_scenario_set(emissions):
@@ -916,8 +932,7 @@ class EnsembleEngine(CheckpointMixin):
         if not self.collect_stats:
             raise RuntimeError("engine was built with collect_stats=False")
         sc = self._scen(scenario)
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         t_end = self.n_steps if t_end is None else int(t_end)
         step_sums = self._step_sums if sc is None else self._step_sums[sc]
         valid = self._step_sums_valid[t_begin:t_end]
@@ -948,8 +963,7 @@ class EnsembleEngine(CheckpointMixin):
         last = self.observations.window[1]
         if self.t_next < last:
             raise RuntimeError(f"chi2: the run is at step {self.t_next}, the observation window ends at step {last}")
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         from .constrain import chi2_from_misfit
         return chi2_from_misfit(self.misfit, self.observations.P)
 
@@ -978,8 +992,7 @@ class EnsembleEngine(CheckpointMixin):
             raise RuntimeError(f"no stored {'T' if gas is None else 'C'} rows to summarise")
         if gas is not None and not 0 <= int(gas) < self.n_gas:
             raise ValueError(f"gas {gas}: the parameter set has gases 0..{self.n_gas - 1}")
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         row_of = {int(t): r for r, t in enumerate(self.out_steps)}
         missing = [int(t) for t in steps if int(t) not in row_of]
         if missing:
@@ -989,14 +1002,10 @@ class EnsembleEngine(CheckpointMixin):
         C_rows = None if self.C is None else (self.C if sc is None else self.C[sc])
         rows = T_rows[picked] if gas is None else C_rows[picked, int(gas)]
         if weights is not None:
-            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or tuple(weights.shape) != (self.n_members,) \
-                    or weights.device != rows.device:
-                raise ValueError(f"weights: want an int64 tensor of shape [{self.n_members}] on {rows.device}")
+            int_weights(weights, self.n_members, rows.device, check_range=False)
             return gather_weighted_summary(rows, weights, percentiles, dst=dst, group=group, stats=stats)
         if accepted is not None:
-            mask = torch.as_tensor(accepted, device=self.device)
-            if mask.dtype != torch.bool or tuple(mask.shape) != (self.n_members,):
-                raise ValueError(f"accepted: want a boolean mask of shape [{self.n_members}]")
+            mask = bool_mask(accepted, self.n_members, self.device)
             return gather_summary(rows[:, mask].contiguous(), percentiles, dst=dst, group=group, stats=stats)
         sums = None
         if gas is None and self.collect_stats and all(self._stats_have[int(t)] for t in steps):   # else: the moments pass over the rows
@@ -1013,8 +1022,7 @@ class EnsembleEngine(CheckpointMixin):
         from .metrics import trajectory_metrics
         if self.T is None or self.n_rows == 0:
             raise RuntimeError("no stored T rows: trajectory metrics need output_steps")
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         rows = self.T[self._scen(scenario)] if self.scenario_axis and scenario is not None else self.T
         with torch.cuda.device(self.device):
             return trajectory_metrics(rows, self.out_steps, levels=levels, windows=windows, state=state)
@@ -1053,8 +1061,7 @@ class EnsembleEngine(CheckpointMixin):
             if missing:
                 raise ValueError(f"records[{key!r}]: {len(missing)} live steps of the record are not stored steps (out_steps), "
                                  f"first {missing[:5]}: the score would silently cover part of the record")
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         misfit = {}
         if "T" in records:
             misfit["T"] = score_rows(self.T if sc is None else self.T[sc], self.out_steps, records["T"])
@@ -1074,6 +1081,14 @@ class EnsembleEngine(CheckpointMixin):
         for key in order[1:]:
             total = total + chi2[key]
         return Score(misfit, chi2, total, {key: records[key].n_obs for key in order})
+
+    def _need_stored_C(self, what, why_not_compensated, why_C):
+        """The refusals of the passes that recompute the forcing from the stored C rows; `what` names the pass."""
+        if self.compensated:
+            raise ValueError(f"{what}: compensated=True takes its forcing from the UNROUNDED excess C - C0, which is not stored"
+                             f"{why_not_compensated}")
+        if self.C is None or self.T is None or self.n_rows == 0:
+            raise ValueError(f"{what}: no stored concentrations (store_concentrations=False or no output_steps): {why_C}")
 
     def forcing_rows(self, want=("F",), rows=None, scenario=None, replay=False):
         """The effective radiative forcing F, its split by gas F_gas, the energy imbalance N = F - T / (q0 + q1) and the
@@ -1098,22 +1113,14 @@ class EnsembleEngine(CheckpointMixin):
         if self.concentration_driven:
             raise ValueError("forcing_rows: a concentration-driven engine stores the diagnosed EMISSIONS in its C rows, not "
                              "concentrations; the forcing of its target concentrations is not diagnosed here")
-        if self.compensated:
-            raise ValueError("forcing_rows: compensated=True takes its forcing from the UNROUNDED excess C - C0, which is not stored; "
-                             "the stored C rows cannot reproduce that F")
-        if self.C is None or self.T is None or self.n_rows == 0:
-            raise ValueError("forcing_rows: no stored concentrations (store_concentrations=False or no output_steps): F is "
-                             "recomputed from the stored C rows")
-        sel = slice(None) if rows is None else rows
-        if not isinstance(sel, slice) or sel.step not in (None, 1):
-            raise ValueError("rows: want a slice of the stored rows with step 1 (or None for all)")
+        self._need_stored_C("forcing_rows", "; the stored C rows cannot reproduce that F", "F is recomputed from the stored C rows")
+        sel = _stored_rows_slice(rows)
         steps = self.out_steps[sel]
         if replay and (steps.size == 0 or steps[0] != 0 or np.any(np.diff(steps) != 1)):
             raise ValueError("forcing_rows(replay=True) repeats the run from its initial state: it needs every step from 0 stored "
                              f"and rows from the first (stored steps {steps[:3].tolist()}..: output_steps is a subset, or rows= "
                              "starts later)")
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
 
         def one(sc):
             pick = (lambda t: t) if sc is None else (lambda t: t[sc])
@@ -1153,20 +1160,13 @@ class EnsembleEngine(CheckpointMixin):
         if not self.scenario_axis:
             raise ValueError("pulse_response: this engine runs one scenario; a pulse response needs the base and the pulse scenarios "
                              "in ONE engine (emissions [S, n_steps, G], e.g. pulse.pulse_experiment(...).emissions)")
-        if self.compensated:
-            raise ValueError("pulse_response: compensated=True takes its forcing from the UNROUNDED excess C - C0, which is not stored")
-        if self.C is None or self.T is None or self.n_rows == 0:
-            raise ValueError("pulse_response: no stored concentrations (store_concentrations=False or no output_steps): the "
-                             "forcing of every scenario is recomputed from its stored C rows")
-        sel = slice(None) if rows is None else rows
-        if not isinstance(sel, slice) or sel.step not in (None, 1):
-            raise ValueError("rows: want a slice of the stored rows with step 1 (or None for all)")
+        self._need_stored_C("pulse_response", "", "the forcing of every scenario is recomputed from its stored C rows")
+        sel = _stored_rows_slice(rows)
         if isinstance(experiment_or_pulses, PulseExperiment):
             table = [(1 + p, g, size) for p, (g, size) in enumerate(experiment_or_pulses.pulses)]
         else:
             table = list(experiment_or_pulses)
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         with torch.cuda.device(self.device):
             return pulse_response(self.C[:, sel], self.T[:, sel], self.out_steps[sel], self.params, q=self.q, F_ext=self.drive, dt=self.dt,
                                   base=base, pulses=table, horizons=horizons, fscale=self.fscale, X=self.fext)
@@ -1199,8 +1199,7 @@ class EnsembleEngine(CheckpointMixin):
         a call: pass names= for a larger set.  Collective over `group`.  Returns joint.Sensitivity; its x axis follows
         parameter_rows(names)[0]."""
         from .joint import sensitivity
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         x = self.parameter_rows(names)[1]
         with torch.cuda.device(self.device):
             return sensitivity(x, y, bins=bins, weights=weights, accepted=accepted, group=group)
@@ -1218,8 +1217,7 @@ class EnsembleEngine(CheckpointMixin):
             raise ValueError("resampled: a concentration-driven engine carries cumE, which the resampled triple does not hold")
         if not isinstance(plan.src, torch.Tensor) or plan.src.device != self.device or plan.n_source != self.n_members:
             raise ValueError(f"resampled: want a plan over this engine's {self.n_members} members with indices on {self.device}")
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         G = self.n_gas
         with torch.cuda.device(self.device):
             r = plan.gather(self.r)                                  # [3 G, M], gas-major (r0, rC, rT)
@@ -1241,8 +1239,7 @@ class EnsembleEngine(CheckpointMixin):
         if self.T is None:
             raise RuntimeError("no stored T rows to histogram")
         sc = self._scen(scenario)
-        if self._ps_unjoined:
-            self.join(stream)
+        _joined(self, stream)
         T_rows = self.T if sc is None else self.T[sc]
         x = T_rows if rows is None else T_rows[rows].contiguous()
         k = x.shape[0]
@@ -1260,8 +1257,7 @@ class EnsembleEngine(CheckpointMixin):
         percentiles near that tail (compare with stats()['min'/'max'])."""
         if self.T_hist is None:
             raise RuntimeError("engine was built without hist=")
-        if self._ps_unjoined:
-            self.join()
+        _joined(self)
         return torch.stack([self.T_hist[:, 0], self.T_hist[:, -1]], dim=1)
 
     def fscale_sha256(self):

@@ -18,6 +18,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import _rowargs
+
 
 def _lib_and_stream(rows):
     """(library, _capi, stream) for rows on a GPU.  (_joint_host.host_passes() replaces this function and the next.)"""
@@ -69,27 +71,18 @@ def _rows_of(t, name):
 
 
 def _in_place(t):
-    K, N = t.shape
-    if N > 0 and ((N > 1 and t.stride(1) != 1) or (K > 1 and t.stride(0) < N)):
-        t = t.contiguous()
-    return t, (int(t.stride(0)) if K > 1 else max(N, 1))
+    t, (ld,) = _rowargs.walk_in_place(t, t.shape[1])
+    return t, (ld if t.shape[0] > 1 else max(ld, 1))           # one row of no members still reports 1
 
 
 def _weights_of(N, dev, weights, accepted):
     if weights is not None and accepted is not None:
         raise ValueError("weights= and accepted= exclude each other (a weight of 0 drops a member)")
     if accepted is not None:
-        mask = torch.as_tensor(accepted, device=dev)
-        if mask.dtype != torch.bool or tuple(mask.shape) != (N,):
-            raise ValueError(f"accepted: want a boolean mask of shape [{N}]")
-        return mask.to(torch.int64)
+        return _rowargs.bool_mask(accepted, N, dev).to(torch.int64)
     if weights is None:
         return torch.ones(N, dtype=torch.int64, device=dev)
-    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or tuple(weights.shape) != (N,) or weights.device != dev:
-        raise ValueError(f"weights: want an int64 tensor of shape [{N}] on {dev}")
-    if N and (int(weights.min()) < 0 or int(weights.max()) > (1 << 32)):
-        raise ValueError("weights: values outside [0, 2^32]")
-    return weights.contiguous()
+    return _rowargs.int_weights(weights, N, dev, check_range=True).contiguous()
 
 
 def _prepare(x, y, weights, accepted):

@@ -17,6 +17,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import _rowargs
+
 
 def _lib_and_stream(rows):
     """(library, _capi, stream, device guard) for rows on a GPU.  (_metrics_host.host_passes() replaces this function and the
@@ -63,6 +65,16 @@ def _spec(levels, windows):
     return lv, wn
 
 
+def _rows_in_place(x):
+    """x [S, K, N] -> (x or its contiguous copy, ld, scen_stride).  The C ABI has ONE ld for the rows and the state blocks, so
+    a narrow slice of a wide buffer (ld >= 2 N) is copied: read in place it would cost (3 + W + 2 L) state rows of ld words
+    each, most of them padding.  The scenario axis is this pass's own: scenario blocks at least K ld apart."""
+    S, K, N = x.shape
+    ld = int(x.stride(1)) if K > 1 else N
+    x, (ld,) = _rowargs.walk_in_place(x, N, first=1, copy=ld >= 2 * N or (S > 1 and K > 0 and x.stride(0) < K * ld))
+    return x, ld, (int(x.stride(0)) if S > 1 and K > 0 else K * ld)
+
+
 def trajectory_metrics(rows, steps, levels=(), windows=(), state=None):
     """rows [n_rows, N] or [S, n_rows, N] (fp32 / fp64 ON THE GPU; a column-sliced view of a buffer less than twice as wide is read in place, a narrower slice is copied),
     steps [n_rows]: the model step each row holds, strictly increasing.  levels: up to 8 values; windows: up to 4 step ranges
@@ -80,12 +92,7 @@ def trajectory_metrics(rows, steps, levels=(), windows=(), state=None):
     S, K, N = x.shape
     if N < 1:
         raise ValueError("rows: no members")
-    st = np.asarray(steps)
-    if st.shape != (K,) or (K and not np.issubdtype(st.dtype, np.integer)):
-        raise ValueError(f"steps: want {K} integers, one per row")
-    st = st.astype(np.int64)
-    if K and (st[0] < 0 or st[-1] >= 2 ** 31 or np.any(np.diff(st) <= 0)):
-        raise ValueError("steps: want non-negative, strictly increasing model steps")
+    st = _rowargs.model_steps(steps, K, non_negative=True)
     if state is not None:
         if not isinstance(state, TrajectoryMetrics) or state.levels != lv or state.windows != wn:
             raise ValueError("state: levels and windows must equal those of the call that made it")
@@ -93,14 +100,7 @@ def trajectory_metrics(rows, steps, levels=(), windows=(), state=None):
             raise ValueError(f"state: made for other rows ({tuple(state.peak.shape)} on {state.peak.device})")
         if K and state.steps.size and st[0] <= state.steps[-1]:
             raise ValueError(f"steps: the first new step {int(st[0])} does not lie after the state's last step {int(state.steps[-1])}")
-    # rows the kernel can walk in place: unit column stride, rows ld >= N apart, scenario blocks at least K ld apart.  The C
-    # ABI has ONE ld for the rows and the state blocks, so a narrow slice of a wide buffer (ld >= 2 N) is copied: read in
-    # place it would cost (3 + W + 2 L) state rows of ld words each, most of them padding.
-    ld = int(x.stride(1)) if K > 1 else N
-    if (N > 1 and x.stride(2) != 1) or ld < N or ld >= 2 * N or (S > 1 and K > 0 and x.stride(0) < K * ld):
-        x = x.contiguous()
-        ld = N
-    scen_stride = int(x.stride(0)) if S > 1 and K > 0 else K * ld
+    x, ld, scen_stride = _rows_in_place(x)
     L, W = len(lv), len(wn)
     dev = rows.device
     fmet = torch.empty((S, 1 + W, ld), dtype=torch.float64, device=dev)
@@ -113,15 +113,13 @@ def trajectory_metrics(rows, steps, levels=(), windows=(), state=None):
         if L:
             imet[:, 2:2 + L, :N], imet[:, 2 + L:, :N] = lead(state.first), lead(state.n_above)
     lib, capi, stream, guard = _lib_and_stream(rows)
-    st32 = torch.from_numpy(st.astype(np.int32)).to(dev)
+    st32 = _rowargs.steps_i32(st, dev)
     c_lv = (ctypes.c_double * max(L, 1))(*lv)
     c_wn = (ctypes.c_int32 * max(2 * W, 1))(*[v for ab in wn for v in ab])
-    fn = lib.fiveeq_traj_metrics_f64 if rows.dtype == torch.float64 else lib.fiveeq_traj_metrics_f32
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())                  # noqa: E731
-    with guard:
-        capi.check(lib, fn(S, K, N, ld, ptr(x) if K else None, scen_stride, ptr(st32) if K else None, L,
-                           ctypes.cast(c_lv, ctypes.c_void_p), W, ctypes.cast(c_wn, ctypes.c_void_p), ptr(fmet), ptr(imet),
-                           1 if state is None else 0, stream))
+    ptr = _rowargs.ptr
+    _rowargs.call(lib, capi, "fiveeq_traj_metrics", rows.dtype, dev, S, K, N, ld, ptr(x) if K else None, scen_stride,
+                  ptr(st32) if K else None, L, ctypes.cast(c_lv, ctypes.c_void_p), W, ctypes.cast(c_wn, ctypes.c_void_p), ptr(fmet),
+                  ptr(imet), 1 if state is None else 0, stream=stream, guard=guard)
     all_steps = st if state is None else np.concatenate([state.steps, st])
     counts = torch.tensor([int(np.count_nonzero((all_steps >= a) & (all_steps < b))) for a, b in wn], dtype=torch.float64, device=dev)
     drop = (lambda t: t) if scen else (lambda t: t[0])
@@ -144,11 +142,7 @@ def exceedance(first, weights=None, group=None):
     if weights is None:
         acc = torch.cat([crossed.sum(dim=1, dtype=torch.int64), torch.tensor([n], dtype=torch.int64, device=first.device)])
     else:
-        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or tuple(weights.shape) != (n,) \
-                or weights.device != first.device:
-            raise ValueError(f"weights: want an int64 tensor of shape [{n}] on {first.device}")
-        if n and (int(weights.min()) < 0 or int(weights.max()) > (1 << 32)):
-            raise ValueError("weights: values outside [0, 2^32]")
+        _rowargs.int_weights(weights, n, first.device, check_range=True)
         acc = torch.cat([(crossed.to(torch.int64) * weights.unsqueeze(0)).sum(dim=1), weights.sum().reshape(1)])
     dist, _, _, exchange = _dist(group)
     if exchange:
@@ -175,9 +169,7 @@ def crossing_summary(first_row, years, percentiles=(5.0, 50.0, 95.0), weights=No
     yr = torch.as_tensor(np.asarray(years, dtype=np.float64), device=dev)
     crossed = first_row >= 0
     if accepted is not None:
-        mask = torch.as_tensor(accepted, device=dev)
-        if mask.dtype != torch.bool or mask.shape != crossed.shape:
-            raise ValueError(f"accepted: want a boolean mask of shape [{crossed.shape[0]}]")
+        mask = _rowargs.bool_mask(accepted, crossed.shape[0], dev)
         crossed = crossed & mask
     if first_row.numel() and int(first_row.max()) >= yr.numel():
         raise ValueError("years: shorter than the steps in first_row")
@@ -185,8 +177,7 @@ def crossing_summary(first_row, years, percentiles=(5.0, 50.0, 95.0), weights=No
     if weights is None:
         w_eff = crossed.to(torch.int64)
     else:
-        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or weights.shape != crossed.shape or weights.device != dev:
-            raise ValueError(f"weights: want an int64 tensor of shape [{crossed.shape[0]}] on {dev}")
+        _rowargs.int_weights(weights, crossed.shape[0], dev, check_range=False)
         w_eff = weights * crossed.to(torch.int64)
     total = w_eff.sum().reshape(1)
     dist, rank, _, exchange = _dist(group)

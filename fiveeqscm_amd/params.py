@@ -284,20 +284,16 @@ def lhs_rows(n_total, dims, lo=0, hi=None, seed=LHS_SEED):
 
 def lhs_rows_device(n_total, dims, lo, hi, device, seed=LHS_SEED):
     """The same rows computed on `device` by the HIP kernel (dims must be consecutive)."""
-    import ctypes
-
     import torch
+
+    from ._rowargs import call, ptr
     dims = list(dims)
     if dims != list(range(dims[0], dims[0] + len(dims))):
         raise ValueError("dims must be consecutive")
-    lib = _capi.load()
     dev = torch.device(device)
     out = torch.empty((len(dims), hi - lo), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.fiveeq_lhs_rows_f64(int(seed), int(n_total), int(lo), int(hi - lo), dims[0], len(dims), hi - lo,
-                                     ctypes.c_void_p(out.data_ptr()),
-                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _capi.check(lib, rc)
+    call(_capi.load(), _capi, "fiveeq_lhs_rows", torch.float64, dev, int(seed), int(n_total), int(lo), int(hi - lo), dims[0],
+         len(dims), hi - lo, ptr(out))
     return out
 
 

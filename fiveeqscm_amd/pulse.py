@@ -160,6 +160,7 @@ def pulse_response(C_rows, T_rows, steps, params, *, q=None, F_ext, dt, base, pu
     import torch
 
     from . import _capi
+    from ._rowargs import call, dev_rows, drive_table, forcing_tables, model_steps, ptr, steps_i32, steps_in_tables, walk_in_place
     from .diagnose import check_consecutive
     from .forcing import ScenarioForcings
     from .params import make_model
@@ -177,22 +178,9 @@ def pulse_response(C_rows, T_rows, steps, params, *, q=None, F_ext, dt, base, pu
         raise ValueError("C_rows: no members")
     if S < 2:
         raise ValueError("C_rows: a pulse response needs the base scenario and at least one pulse scenario")
-    st = np.asarray(steps)
-    if st.shape != (K,) or (K and not np.issubdtype(st.dtype, np.integer)):
-        raise ValueError(f"steps: want {K} integers, one per row")
-    st = st.astype(np.int64)
+    st = model_steps(steps, K, increasing=False)
     check_consecutive(st, "the pulse response")
-
-    def dev_rows(t, shape, name, dtype=dtp):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype:
-            raise ValueError(f"{name}: want a {dtype} tensor of shape {list(shape)}")
-        if not t.is_cuda:
-            raise TypeError(f"{name} must be on the GPU (got {t.device}): there is no CPU path")
-        if t.device != dev:
-            raise ValueError(f"{name}: on {t.device}, the rows on {dev}")
-        return t
-
-    T_rows = dev_rows(T_rows, (S, K, N), "T_rows")
+    T_rows = dev_rows(T_rows, (S, K, N), "T_rows", dtp, dev)
     # the pulses and the horizons
     table = tuple((int(s), int(g), float(size)) for s, g, size in pulses)
     if not 1 <= len(table) <= _capi.MAX_PULSES:
@@ -213,47 +201,24 @@ def pulse_response(C_rows, T_rows, steps, params, *, q=None, F_ext, dt, base, pu
     P, H = len(table), len(hz)
 
     # the shared tables, one per scenario: F_ext as drive tables, X padded to the C ABI's four columns
-    if isinstance(F_ext, torch.Tensor) and F_ext.dim() == 3:
-        drive = dev_rows(F_ext, (S, int(F_ext.shape[1]), _capi.DRIVE_STRIDE), "F_ext (the scenarios' drive tables)").contiguous()
-    else:
-        fe = np.asarray(F_ext.cpu() if isinstance(F_ext, torch.Tensor) else F_ext, dtype=np.float64)
-        fe = np.broadcast_to(fe, (S, fe.shape[-1])) if fe.ndim == 1 else fe
-        if fe.ndim != 2 or fe.shape[0] != S:
-            raise ValueError(f"F_ext: want [n_steps] or [{S}, n_steps]")
-        tab = np.zeros((S, fe.shape[1], _capi.DRIVE_STRIDE))
-        tab[:, :, 6] = fe
-        drive = torch.from_numpy(tab).to(dev, dtp)
+    drive = drive_table(F_ext, (S,), "F_ext (the scenarios' drive tables)", dtp, dev)
     n_steps = int(drive.shape[1])
-    if K and (st[0] < 0 or st[-1] >= n_steps):
-        raise ValueError(f"steps: {int(st[0])}..{int(st[-1])} outside the tables' steps 0..{n_steps - 1}")
-    if (fscale is None) != (X is None):
-        raise ValueError("fscale and X come together: the scale rows and the category tables of a forcing= run")
-    n_fext, fext, ld = 0, None, N
+    steps_in_tables(st, n_steps)
+
+    def host_table(X):
+        fx = X if isinstance(X, ScenarioForcings) else ScenarioForcings(np.asarray(X, dtype=np.float64))
+        if fx.n_scenarios != S or fx.n_steps != n_steps:
+            raise ValueError(f"X: tables of {fx.n_scenarios} scenarios x {fx.n_steps} steps; the rows hold {S} x {n_steps}")
+        return fx
+
+    n_fext, fext, fscale = forcing_tables(
+        fscale, X, (S,), G, N, n_steps, dtp, dev, x_name="X (the scenarios' device tables)", host_table=host_table,
+        together="fscale and X come together: the scale rows and the category tables of a forcing= run")
+    ld = N
     if fscale is not None:
-        if isinstance(X, torch.Tensor):
-            n_fext = int(fscale.shape[0]) - G
-            fext = dev_rows(X, (S, n_steps, _capi.MAX_FEXT), "X (the scenarios' device tables)").contiguous()
-        else:
-            fx = X if isinstance(X, ScenarioForcings) else ScenarioForcings(np.asarray(X, dtype=np.float64))
-            if fx.n_scenarios != S or fx.n_steps != n_steps:
-                raise ValueError(f"X: tables of {fx.n_scenarios} scenarios x {fx.n_steps} steps; the rows hold {S} x {n_steps}")
-            n_fext = fx.n_categories
-            fext = torch.from_numpy(fx.padded()).to(dev, dtp)
-        if not 0 <= n_fext <= _capi.MAX_FEXT:
-            raise ValueError(f"fscale: {int(fscale.shape[0])} rows for {G} gases: want G + K rows, K <= {_capi.MAX_FEXT}")
-        fscale = dev_rows(fscale, (G + n_fext, N), "fscale")
-        if (N > 1 and fscale.stride(1) != 1) or fscale.stride(0) < N:
-            fscale = fscale.contiguous()
-        ld = int(fscale.stride(0))
-    # rows the kernel walks in place: unit member stride; scenarios, rows and gases at least N apart
-    x = C_rows
-    if (N > 1 and x.stride(3) != 1) or abs(x.stride(0)) < N or (K > 1 and x.stride(1) < N) or (G > 1 and abs(x.stride(2)) < N):
-        x = x.contiguous()
-    c_scen, c_row, c_gas = int(x.stride(0)), (int(x.stride(1)) if K > 1 else N), (int(x.stride(2)) if G > 1 else N)
-    tr = T_rows
-    if (N > 1 and tr.stride(2) != 1) or abs(tr.stride(0)) < N or (K > 1 and tr.stride(1) < N):
-        tr = tr.contiguous()
-    t_scen, t_row = int(tr.stride(0)), (int(tr.stride(1)) if K > 1 else N)
+        fscale, (ld,) = walk_in_place(fscale, N, always=(0,))      # the carried sums take ld from one row of scales as from several
+    x, (c_scen, c_row, c_gas) = walk_in_place(C_rows, N, always=(0,))
+    tr, (t_scen, t_row) = walk_in_place(T_rows, N, always=(0,))
     # every output row starts 16-byte aligned; the carried sums are laid out with the scales' row stride
     ld_out = (N + 1) // 2 * 2
     row0 = 0
@@ -265,20 +230,14 @@ def pulse_response(C_rows, T_rows, steps, params, *, q=None, F_ext, dt, base, pu
             raise ValueError("state: want the .state of an earlier pulse_response")
         row0 = int(state.rows)
         out = torch.empty((5, P, H, ld_out), dtype=torch.float64, device=dev)[..., :N]
-        out.copy_(dev_rows(state.out, (5, P, H, N), "state.out", torch.float64))
+        out.copy_(dev_rows(state.out, (5, P, H, N), "state.out", torch.float64, dev))
         io = torch.empty((3, P, ld), dtype=torch.float64, device=dev)[..., :N]
-        io.copy_(dev_rows(state.sums, (3, P, N), "state.sums", torch.float64))
-    lib = _capi.load()
-    fn = lib.fiveeq_pulse_response_f64 if dtp == torch.float64 else lib.fiveeq_pulse_response_f32
-    ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())           # noqa: E731
+        io.copy_(dev_rows(state.sums, (3, P, N), "state.sums", torch.float64, dev))
     i32 = lambda v: (ctypes.c_int32 * len(v))(*v)                                  # noqa: E731
-    st32 = torch.from_numpy(st.astype(np.int32)).to(dev)
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(lib, fn(ctypes.byref(model), S, K, N, ld, ptr(x) if K else None, c_scen, c_row, c_gas, ptr(tr) if K else None,
-                            t_scen, t_row, ptr(st32) if K else None, ptr(drive), n_steps, ptr(fscale), n_fext, ptr(fext), base, P,
-                            i32([s for s, _, _ in table]), i32([g for _, g, _ in table]), H, i32(hz), row0, ptr(out), ld_out,
-                            ptr(io), stream))
+    st32 = steps_i32(st, dev)
+    call(_capi.load(), _capi, "fiveeq_pulse_response", dtp, dev, ctypes.byref(model), S, K, N, ld, ptr(x) if K else None, c_scen,
+         c_row, c_gas, ptr(tr) if K else None, t_scen, t_row, ptr(st32) if K else None, ptr(drive), n_steps, ptr(fscale), n_fext,
+         ptr(fext), base, P, i32([s for s, _, _ in table]), i32([g for _, g, _ in table]), H, i32(hz), row0, ptr(out), ld_out, ptr(io))
     c = np.asarray(params["emis2conc"], dtype=np.float64).reshape(G)
     return PulseResponse(out[0], out[1], out[2], out[3], out[4], PulseState(io, row0 + K, out), hz,
                          tuple((s, g) for s, g, _ in table), tuple(size for _, _, size in table),

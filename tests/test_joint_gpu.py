@@ -175,6 +175,35 @@ def test_flags_nan_rows_and_the_python_layer():
     assert torch.isnan(s.eta2[2]).all() and torch.isnan(s.eta2[:, 1]).all() and int(torch.isnan(s.eta2).sum()) == 7
 
 
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_the_python_layer_reads_a_wider_buffer_in_place_and_copies_a_strided_view(dtype):
+    """joint.sensitivity on x [3, N], y [2, N] of one 256-member tile plus three members: rows in buffers N + 3 wide (read in
+    place: ld_x = ld_y = N + 3) and on every second column of buffers 2 N wide (copied) — every bit of the same call on
+    contiguous clones."""
+    from fiveeqscm_amd.joint import sensitivity
+    n = 259
+    x, y, w, _, _ = case_data(n, 3, 2, 8, "mix", _tile()[2])
+    xd, yd = (torch.from_numpy(a.astype(NP[dtype])).to(DEV) for a in (x, y))
+    wd = torch.from_numpy(w.astype(np.int64)).to(DEV)
+    base = sensitivity(xd.clone(), yd.clone(), bins=8, weights=wd)
+    assert not bool(torch.isnan(base.eta2).any()) and base.moments.weight_sum == int(w.sum())
+    bits = lambda t: t.contiguous().view(torch.int64)                                        # noqa: E731  (NaN equal to NaN)
+
+    def embed(rows, width, step):
+        view = torch.full((rows.shape[0], width), float("nan"), dtype=dtype, device=DEV)[:, :step * n:step]
+        view.copy_(rows)
+        return view
+    for width, step in ((n + 3, 1), (2 * n, 2)):
+        xv, yv = embed(xd, width, step), embed(yd, width, step)
+        assert xv.stride() == (width, step) and yv.stride() == (width, step)
+        got = sensitivity(xv, yv, bins=8, weights=wd)
+        for name in ("eta2", "cond_mean", "bin_weight", "edges"):
+            assert torch.equal(bits(getattr(got, name)), bits(getattr(base, name))), (width, name)
+        for name in ("mean_x", "mean_y", "var_x", "var_y", "cov", "corr", "slope"):
+            assert torch.equal(bits(getattr(got.moments, name)), bits(getattr(base.moments, name))), (width, name)
+        assert (got.moments.weight_sum, got.moments.count, got.moments.ess) == (base.moments.weight_sum, base.moments.count, base.moments.ess)
+
+
 def _sha(eng):
     return [hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()
             for t in (eng.R, eng.S, eng.T, eng.C, eng.r, eng.q, eng.fscale, eng.misfit) if t is not None]

@@ -94,6 +94,36 @@ def test_row_splits_and_a_poisoned_state(dtype):
         assert_equal(_run([x], steps, levels, windows, ld=n + 5 - off, off=off, gap=0, poison=True)[0], want, "first_call ignores the state")
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_the_wrapper_reads_a_wider_buffer_in_place_and_copies_a_strided_view(dtype):
+    """metrics.trajectory_metrics on 3 rows of one 256-member tile plus three members: in a buffer N + 3 wide (read in place, the
+    state blocks laid out with the buffer's ld), on every second column of a buffer 2 N wide (copied), and both under a scenario
+    axis — every bit of the same call on a contiguous clone, which is the reference's."""
+    from fiveeqscm_amd.metrics import trajectory_metrics
+    n, k = 259, 3
+    data = [case_data(k, n, dtype, seed, 2, 2) for seed in (11, 12)]
+    _, steps, levels, windows, _ = data[0]
+    names = ("peak", "t_peak", "n_nan", "first", "n_above", "wsum", "window_mean")
+    bits = lambda t: t.view(torch.int64) if t.dtype == torch.float64 else t                  # noqa: E731  (NaN equal to NaN)
+
+    def embed(rows, width, step):
+        view = torch.full(tuple(rows.shape[:-1]) + (width,), float("nan"), dtype=rows.dtype, device=rows.device)[..., :step * n:step]
+        view.copy_(rows)
+        return view
+    for rows in (torch.from_numpy(data[0][0].copy()).cuda(), torch.from_numpy(np.stack([d[0] for d in data])).cuda()):
+        base = trajectory_metrics(rows.clone(), steps, levels, windows)
+        for s_, d in enumerate(data[:1] if rows.dim() == 2 else data):
+            pick = (lambda t: t) if rows.dim() == 2 else (lambda t: t[s_])                   # noqa: E731
+            assert_equal({key: pick(getattr(base, key)).cpu().numpy() for key in d[4]}, d[4], (rows.dim(), s_))
+        for width, step in ((n + 3, 1), (2 * n, 2)):
+            view = embed(rows, width, step)
+            assert view.stride(-1) == step and view.stride(-2) == width
+            got = trajectory_metrics(view, steps, levels, windows)
+            for name in names:
+                assert torch.equal(bits(getattr(got, name)), bits(getattr(base, name))), (rows.dim(), width, name)
+            assert got.peak.stride(-1) == 1 and (got.wsum.stride(-2) == width if step == 1 else got.wsum.stride(-2) == n)
+
+
 def _sha(eng):
     return [hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest() for t in (eng.R, eng.S, eng.T, eng.C) if t is not None]
 
