@@ -4,13 +4,16 @@
 The record is the synthetic one committed for the tests (tests/golden/obs_synthetic.csv, made by
 tests/golden/make_obs_synthetic.py: one known member plus 0.1 K noise over 1900..2069).  Needs an MI355X.
 
-    python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing] [--co2-record]
+    python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing] [--co2-record] [--concentration-driven]
 
 --forcing adds forcing uncertainty (EnsembleEngine(forcing=), fiveeqscm_amd/forcing.py): an aerosol-like cooling scaled per
 member, and the accepted range of ECS with a shared and with a sampled scale.
 --co2-record also makes a CO2 record the same way (one known member's stored concentration plus 1 ppm noise over the same
 years), scores the stored T and C rows against both records (EnsembleEngine.score) and prints the posterior spread of the
 carbon-cycle parameter r0 of CO2 with and without the CO2 record.
+--concentration-driven runs the calibration the other way round (ConcentrationDrivenEngine): the history 1750..2019 is driven by
+"observed" concentrations, every member carries its own aerosol scale and is scored against the warming record in-loop; the
+weighted ensemble then branches into an emission-driven projection to 2499 through R0 / S0.
 """
 import argparse
 import os
@@ -34,6 +37,8 @@ def main():
                     help="also sample an aerosol scale per member and print the accepted range of ECS with and without it")
     ap.add_argument("--co2-record", action="store_true",
                     help="also score the stored CO2 rows against a synthetic CO2 record and print what it does to r0 of CO2")
+    ap.add_argument("--concentration-driven", action="store_true",
+                    help="also constrain a concentration-driven history with an aerosol scale per member and branch into a projection")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -60,6 +65,8 @@ def main():
         forcing_uncertainty(p, N, n_steps, dtype, obs)
     if a.co2_record:
         co2_record(p, N, n_steps, dtype, obs, run_years, years)
+    if a.concentration_driven:
+        concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma)
 
 
 def co2_record(p, N, n_steps, dtype, obs, run_years, years, truth=12345, sigma_ppm=1.0):
@@ -86,6 +93,50 @@ def co2_record(p, N, n_steps, dtype, obs, run_years, years, truth=12345, sigma_p
         lo, mid, hi = (float(r0[order][int(torch.searchsorted(cdf, torch.tensor(q, dtype=cdf.dtype, device=cdf.device)))]) for q in (0.05, 0.5, 0.95))
         print(f"  r0[CO2] {label:18s} 5/50/95 %: {lo:.2f} / {mid:.2f} / {hi:.2f}   (90 % width {hi - lo:.2f})")
     eng.close()
+
+
+def concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma, cut=270):
+    """--concentration-driven: the concentrations of the default member's forward run stand in for the observed record up to
+    2019 (step `cut`).  History: every member reaches exactly those concentrations (its own emissions are diagnosed), scales the
+    aerosol-like cooling by its own factor and accumulates its misfit against the warming observed up to 2019.  Projection: a
+    forward forcing= engine with the same scale rows starts from the history's pools and boxes (R0 / S0) at step `cut`; its
+    drive table continues the cumulative emissions from the ensemble mean of the history's diagnosed cumE (the first `cut` rows
+    of its emissions hold that mean rate; they are not run)."""
+    from fiveeqscm_amd.engine import ConcentrationDrivenEngine
+    from fiveeqscm_amd.forcing import ExternalForcings
+    E = emissions.rcp_like_emissions(n_steps, 3)
+    base = params.default_params("multigas")
+    one = EnsembleEngine(base, 1, E, device="cuda:0")
+    one.run(mode="fused")
+    conc = one.C[:cut, :, 0].cpu().numpy()
+    one.close()
+    aerosol = -0.9 * E[:, 0] / E[:, 0].max()
+    scales = params.sample_forcing_scales(3, N, ranges=[(1.0, 1.0)] * 3 + [(0.3, 2.0)], device="cuda:0")
+    ps = dict(p, fx_scale=scales[3:].to(dtype))
+    seen = years < run_years[cut]
+    obs = constrain.Observations.from_years(run_years[:cut], years[seen], T_obs[seen], np.broadcast_to(sigma, years.shape)[seen],
+                                            baseline=(1900, 1950))
+    hist = ConcentrationDrivenEngine(ps, N, conc, dtype=dtype, forcing=ExternalForcings(aerosol[:cut], ("aerosol",)),
+                                     observations=obs, store_trajectory=False, device="cuda:0")
+    hist.run()
+    chi2 = hist.chi2()
+    w = constrain.importance_weights(chi2)
+    ess = float(w.double().sum() ** 2 / (w.double() ** 2).sum())
+    print(f"concentration-driven history to {int(run_years[cut - 1])}: {obs.n_obs} observed years, chi2 min {float(chi2.min()):.1f}, "
+          f"effective sample size {ess:.0f} of {N}")
+    E_proj = E.copy()
+    E_proj[:cut] = hist.cumE.double().mean(1).cpu().numpy()[None, :] / cut          # the drive's cumulative emissions at the cut
+    last = n_steps - 1
+    proj = EnsembleEngine(ps, N, E_proj, dtype=dtype, forcing=ExternalForcings(aerosol, ("aerosol",)), R0=hist.R, S0=hist.S,
+                          output_steps=[last], store_concentrations=False, device="cuda:0")
+    proj.run(cut, n_steps, mode="fused")
+    pct = (5.0, 50.0, 95.0)
+    for label, s in (("unweighted", proj.gather_summary([last], percentiles=pct)),
+                     ("weighted", proj.gather_summary([last], percentiles=pct, weights=w))):
+        q = s["percentiles"][0].tolist()
+        print(f"  T({int(run_years[last])}) {label:11s} 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} K")
+    hist.close()
+    proj.close()
 
 
 def forcing_uncertainty(p, N, n_steps, dtype, obs):

@@ -110,6 +110,7 @@ _RUNS = {
     "run_bins": _run_args(_RING + _ST),
     "run_fused_bins": _run_args(_RING + _ST),
     "run_inverse": _run_args(_ST, cumE=True),
+    "run_inverse_forc": _run_args(_FORC + _OBS + _ST, cumE=True),
     "plan_create": _run_args(_PLAN),
     "run_obs": _run_args(_OBS + _FORM),
     "plan_create_obs": _run_args(_OBS + _PLAN),

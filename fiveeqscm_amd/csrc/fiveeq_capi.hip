@@ -424,8 +424,8 @@ template <typename T, bool INV = false, bool BINS = false, bool COMP = false, bo
           bool FORC = false>
 int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
-    static_assert(!FORC || (!INV && !BINS && !COMP), "the forcing scales are carried by the plain forward form only");
-    static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
+    static_assert(!FORC || (!BINS && !COMP), "the forcing scales are carried by the plain forward and inverse forms only");
+    static_assert(!MISFIT || (!BINS && !COMP), "the misfit is carried by the plain forward and inverse forms only");
     static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
     constexpr bool HAS_PACKED = !INV && !std::is_same<P, T>::value;     // the inverse form has no packed instantiation
     // packed lanes store two 2-byte bin indices as one 4-byte word: the ring rows must be 4-byte aligned too; the misfit forms
@@ -593,12 +593,14 @@ struct Features {
     bool uniform = false;        // fiveeq_run_uniform / fiveeq_plan_create_uniform: mask and values are the caller's
     uint32_t mask = 0;
     const T* values = nullptr;   // host, 3G + 2
+    bool inv = false;            // fiveeq_run_inverse_forc: cumE is the caller's, required
+    T* cumE = nullptr;
 };
 
 // Every check of a forward call but its last (the form of a run, the range of a plan), in the ONE order every family reports
 // in (tests/test_forward_precedence_cpu.py): the scenario count, [a plan: plan_out, cleared before anything else,] the base
 // arguments, the forcing rows, obs and misfit given together, the misfit rows; the single-valued rows of the plain family's
-// uniform twins come right behind the base arguments.
+// uniform twins come right behind the base arguments, and so does the cumE of fiveeq_run_inverse_forc.
 template <typename T>
 int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan = false, void** plan_out = nullptr) {
     if (plan_out) *plan_out = nullptr;
@@ -606,6 +608,10 @@ int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan
     if (plan && !plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
     if (int rc = make_args(a, b, f.n_scen)) return rc;
     a.scen = f.scen;
+    if (f.inv) {
+        if (!f.cumE) return fail(FIVEEQ_E_INVALID, "cumE is NULL");
+        a.cumE = f.cumE;
+    }
     if (int rc = f.uniform ? check_uniform(a, f.mask, f.values) : FIVEEQ_OK) return rc;
     if (int rc = f.forc ? check_forcing(a, f.fc.fscale, f.fc.fext, f.fc.n_fext) : FIVEEQ_OK) return rc;
     if (f.misfit == OPTIONAL && (f.mf.obs == nullptr) != (f.mf.misfit == nullptr))
@@ -664,6 +670,31 @@ int run_inverse(const BaseArgs<T>& b, T* cumE, void* stream) {        // (C_traj
     a.cumE = cumE;
     hipStream_t st = (hipStream_t)stream;
     return each_span(a, 0, [&](int t0, int t1) { return launch_fused<T, true>(a, t0, t1, st); });
+}
+
+// the concentration-driven form with the forcing scales and / or the misfit: fscale NULL = no scales (then n_fext must be 0: a
+// count without rows is check_forcing's "fscale is NULL"), obs and misfit both NULL = no misfit, all three NULL = the plain
+// inverse kernel.  Validated by prepare() in the order of the forward families, cumE right behind the base arguments; one
+// launch for the span.
+template <typename T>
+int run_inverse_forc(const BaseArgs<T>& b, T* cumE, const ForcRows<T>& fc, const MisfitRows& mf, void* stream) {
+    RunArgs<T> a;
+    Features<T> f;
+    f.forc = fc.fscale != nullptr || fc.n_fext != 0;
+    f.fc = fc;
+    f.misfit = OPTIONAL;
+    f.mf = mf;
+    f.inv = true;
+    f.cumE = cumE;
+    if (int rc = prepare(a, b, f)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool forc = a.fc.fscale != nullptr, misfit = a.mf.misfit != nullptr;
+    return each_span(a, 0, [&](int t0, int t1) {
+        if (forc)
+            return misfit ? launch_fused<T, true, false, false, true, false, true>(a, t0, t1, st)
+                          : launch_fused<T, true, false, false, false, false, true>(a, t0, t1, st);
+        return misfit ? launch_fused<T, true, false, false, true>(a, t0, t1, st) : launch_fused<T, true>(a, t0, t1, st);
+    });
 }
 
 // ---- the compensated fp32 form: the fused kernel <.., COMP = true> over spans of k_steps, with or without the bin ring ----
@@ -1004,6 +1035,22 @@ int fiveeq_run_inverse_f32(const fiveeq_model* model, int64_t n_members, int64_t
                            void* stream) {
     return run_inverse<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, T_stats},
                               cumE, stream);
+}
+int fiveeq_run_inverse_forc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,
+                                int32_t n_steps, int32_t t_begin, int32_t t_end, const double* r, const double* q,
+                                double* R, double* S, double* cumE, double* E_traj, double* T_traj, int32_t n_rows,
+                                double* T_stats, const double* fscale, const double* fext, int32_t n_fext,
+                                const double* obs, double* misfit, void* stream) {
+    return run_inverse_forc<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, T_stats},
+                                    cumE, {fscale, fext, n_fext}, {obs, misfit}, stream);
+}
+int fiveeq_run_inverse_forc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive,
+                                int32_t n_steps, int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R,
+                                float* S, float* cumE, float* E_traj, float* T_traj, int32_t n_rows, double* T_stats,
+                                const float* fscale, const float* fext, int32_t n_fext, const double* obs, double* misfit,
+                                void* stream) {
+    return run_inverse_forc<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, T_stats},
+                                   cumE, {fscale, fext, n_fext}, {obs, misfit}, stream);
 }
 
 int fiveeq_run_ksteps_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,

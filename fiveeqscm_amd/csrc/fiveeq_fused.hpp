@@ -49,7 +49,7 @@ constexpr int LDS_PER_CU = 160 * 1024;            // MI355X
 // per-member cumulative-emission state (in/out), and C_traj receives the DIAGNOSED EMISSIONS.
 // (112 VGPRs at fp64 4+1+1 = 4 waves/SIMD; launch-bounds hints for 5 or 6 waves spill: -3 % / -16 %.)
 //
-// MISFIT = true (round 7; INV, BINS and COMP false): the member's misfit accumulators (misfit_update()) are loaded from
+// MISFIT = true (round 7; BINS and COMP false; with INV see below): the member's misfit accumulators (misfit_update()) are loaded from
 // misfit [3][ld] fp64 once at launch start, carried on chip and stored once at the end — 48 B per member and launch.
 // THE CARRIER IS LDS, NOT REGISTERS: three fp64 per member are 6 VGPRs (12 on a packed lane), and in registers they cost the
 // fp64 {4} form a wave per SIMD (93 -> 105 VGPRs: 5 -> 4 waves) and the fp32 {4} form one too (66 -> 74: 7 -> 6).  Each lane
@@ -66,11 +66,17 @@ constexpr int LDS_PER_CU = 160 * 1024;            // MI355X
 // scenario strides of kernel 1s (all derived from ld, n_steps and n_rows, so no argument is added).  With SCEN false not
 // one instruction of the kernel changes.
 //
-// FORC = true (round 8; INV, BINS and COMP false, with or without MISFIT): per-member forcing scales
+// FORC = true (round 8; BINS and COMP false, with or without MISFIT; with INV see below): per-member forcing scales
 // (member_step<.., FORC>).  The G + n_fext scales are loaded once at launch start and stay on chip for the span; the table chunk
 // fext [tc .. tc + nt)[MAX_FEXT] is staged into LDS beside the drive chunk.  Where the scales live is FS_LDS, below.
 // With SCEN (round 9; MISFIT false) the table is fext [n_scen][n_steps][MAX_FEXT], one per scenario: the workgroup offsets it
 // by its scenario like the drive table; the scale rows are shared by the scenarios.
+//
+// INV WITH FORC AND / OR MISFIT (scalar lanes, layouts {4} and 4 + 1 + 1): the concentration-driven form with the forcing scales
+// and the in-loop misfit, fiveeq_run_inverse_forc_*.  The scales, the table chunk and the accumulators sit where the forward
+// forms put them (FusedForc: the fp64 4 + 1 + 1 form keeps its scales in the LDS slot and stages 25 steps per refill); nothing
+// of the plain INV kernels changes.  The fp64 4 + 1 + 1 forms run at 3 waves per SIMD (129 to 133 VGPRs; plain INV: 127, 4
+// waves); no form uses scratch: profiles/r24/NOTES.md.
 template <typename V, int P0, int P1, int P2, bool INV, bool BINS = false, bool COMP = false, bool MISFIT = false,
           bool SCEN = false, bool FORC = false>
 __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
@@ -91,10 +97,12 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
     static_assert(!(INV && BINS), "no streamed histograms in the concentration-driven form");
-    static_assert(!FORC || (!INV && !BINS && !COMP), "the forcing scales are carried by the plain forward form only");
+    static_assert(!FORC || (!BINS && !COMP), "the forcing scales are carried by the plain forward and inverse forms only");
+    constexpr int OWN = INV && (MISFIT || FORC) ? 1 : 0;                    // see member_step(): the step functions of their own
     constexpr int CHUNK = FusedForc<V, L, MISFIT, FORC, SCEN>::CHUNK;       // steps staged per refill
     constexpr bool FS_LDS = FusedForc<V, L, MISFIT, FORC, SCEN>::FS_LDS;    // FORC: the scales in a lane-private LDS slot
-    static_assert(!MISFIT || (!INV && !BINS && !COMP), "the misfit is carried by the plain forward form only");
+    static_assert(!MISFIT || (!BINS && !COMP), "the misfit is carried by the plain forward and inverse forms only");
+    static_assert(!INV || !(MISFIT || FORC) || W == 1, "the concentration-driven form has no packed instantiation");
     static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
     if constexpr (SCEN) {
         const int64_t sc = blockIdx.y;
@@ -178,10 +186,10 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
         for (int k = 0; k < nt; ++k) {
             const T* d = &drv[k * DRIVE_STRIDE];
             if constexpr (FORC)
-                member_step<V, L, false, false, true>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo, fs, FS_STRIDE, &xs[k * MAX_FEXT],
-                                                      n_fext);
+                member_step<V, L, INV, false, true, NoGasHook, OWN>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo, fs, FS_STRIDE,
+                                                                    &xs[k * MAX_FEXT], n_fext);
             else
-                member_step<V, L, INV, COMP>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo);
+                member_step<V, L, INV, COMP, false, NoGasHook, OWN>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, cum, Rlo);
             if constexpr (MISFIT) misfit_step(obs + (int64_t)(tc + k) * 4, Tn, acc, 3 * FIVEEQ_BLOCK, FIVEEQ_BLOCK, true);
             // the output row is wave-uniform: read it once into an SGPR so that the row test is a
             // scalar branch and the row offsets are scalar arithmetic, not 64-bit VALU per lane

@@ -52,7 +52,7 @@ __device__ __forceinline__ V gas_forcing(const KGas<typename Lane<V>::S>& kg, co
     return Fg;
 }
 
-template <typename V, typename L, int g, bool INV, bool COMP = false>
+template <typename V, typename L, int g, bool INV, bool COMP = false, int OWN = 0>
 __device__ __forceinline__ V gas_step(const KModel<typename Lane<V>::S>& km, const KGas<typename Lane<V>::S>& kg,
                                       const typename Lane<V>::S* __restrict__ drv, const V (&rr)[3 * L::G], const V T_old,
                                       V (&R)[L::SP], V (&out)[L::G], V (&cum)[L::G], V (&Rlo)[L::SP]) {
@@ -139,6 +139,12 @@ __device__ __forceinline__ V gas_step(const KModel<typename Lane<V>::S>& km, con
 // K = 0 (or an all-zero table) give the bits of the plain step.  Scale j of the lane is fs[j * fs_stride] (gas rows first:
 // registers with stride 1, or a lane-private LDS slot), xr the step's table record (wave-uniform), n_fext = K is
 // wave-uniform: the category loop is scalar branches.  Nothing else of the step differs; FORC = false is the code as it was.
+// With INV (the concentration-driven form) the gas step is the inverse one as it stands — gas_step() does not know FORC — and F
+// is accumulated in exactly this way from the forcing of the concentrations the diagnosed emissions reach.
+// OWN (gas_step() too) changes no code: it is a tag that gives the INV forms with FORC or MISFIT instantiations of the two step
+// functions that no other kernel shares.  Sharing gas_step<.., INV = true> with the plain INV kernel of the same layout moved
+// that kernel's instruction schedule (the same instructions in another order); with the tag every kernel that existed keeps
+// its machine code (profiles/r24/inverse_forcing_isa.txt).
 // AFTER-GAS HOOK (round 18): after_gas(GasTag<g>{}) is called once gas g's pools R[off(g) ..], its out[g] and its share of F
 // are final and before the next gas's arithmetic starts — the per-step kernels store that gas's rows there (step_body).  The
 // hook touches no value of the step: the arithmetic, its order and its roundings are those of the unhooked call, and the
@@ -152,14 +158,14 @@ struct NoGasHook {
     template <int g>
     __device__ __forceinline__ void operator()(GasTag<g>) const {}
 };
-template <typename V, typename L, bool INV, bool COMP, bool FORC = false, typename Hook = NoGasHook>
+template <typename V, typename L, bool INV, bool COMP, bool FORC = false, typename Hook = NoGasHook, int OWN = 0>
 __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& km, const typename Lane<V>::S* __restrict__ drv,
                                             const V (&rr)[3 * L::G], const V (&qq)[2],
                                             V (&R)[L::SP], V (&S)[2], V (&out)[L::G], V& Tnew, V (&cum)[L::G],
                                             V (&Rlo)[L::SP], const V* fs = nullptr, const int fs_stride = 1,
                                             const typename Lane<V>::S* xr = nullptr, const int n_fext = 0,
                                             const Hook after_gas = Hook{}) {
-    static_assert(!FORC || (!INV && !COMP), "the forcing scales are carried by the plain forward form only");
+    static_assert(!FORC || !COMP, "the forcing scales are not carried by the compensated form");
     const V T_old = S[0] + S[1];
     V F = (V)drv[6];
     if constexpr (FORC) {
@@ -171,20 +177,20 @@ __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& k
     // ~45 being hoisted to the kernel top (VGPR pressure) or out of the fused time loop.  (Issuing gas
     // g+1's reads before gas g's arithmetic was tried: +-1 %, 133 VGPRs; not kept.)
     asm volatile("" ::: "memory");
-    const V F0 = gas_step<V, L, 0, INV, COMP>(km, km.gas[0], drv, rr, T_old, R, out, cum, Rlo);
+    const V F0 = gas_step<V, L, 0, INV, COMP, OWN>(km, km.gas[0], drv, rr, T_old, R, out, cum, Rlo);
     if constexpr (FORC) F = fe_fma(fs[0 * fs_stride], F0, F);
     else F += F0;
     after_gas(GasTag<0>{});
     if constexpr (L::G > 1) {
         asm volatile("" ::: "memory");
-        const V F1 = gas_step<V, L, 1, INV, COMP>(km, km.gas[1], drv, rr, T_old, R, out, cum, Rlo);
+        const V F1 = gas_step<V, L, 1, INV, COMP, OWN>(km, km.gas[1], drv, rr, T_old, R, out, cum, Rlo);
         if constexpr (FORC) F = fe_fma(fs[1 * fs_stride], F1, F);
         else F += F1;
         after_gas(GasTag<1>{});
     }
     if constexpr (L::G > 2) {
         asm volatile("" ::: "memory");
-        const V F2 = gas_step<V, L, 2, INV, COMP>(km, km.gas[2], drv, rr, T_old, R, out, cum, Rlo);
+        const V F2 = gas_step<V, L, 2, INV, COMP, OWN>(km, km.gas[2], drv, rr, T_old, R, out, cum, Rlo);
         if constexpr (FORC) F = fe_fma(fs[2 * fs_stride], F2, F);
         else F += F2;
         after_gas(GasTag<2>{});

@@ -111,6 +111,8 @@ class EnsembleEngine(CheckpointMixin):
     """Advance N ensemble members of the five-equation model on one MI355X."""
 
     MODES = ("per_step", "graph", "fused", "ksteps", "small", "auto")
+    # concentration_driven=True together with forcing= / observations=: refused here, carried by ConcentrationDrivenEngine below
+    _INVERSE_CALIBRATION = False
 
     def __init__(self, params, n_members, emissions, *, F_ext=None, dt=1.0, dtype=torch.float64,
                  device=None, store_trajectory=True, output_steps=None, store_concentrations=True,
@@ -307,7 +309,7 @@ class EnsembleEngine(CheckpointMixin):
             self._bins = None            # the bin-index ring, allocated by the first run that fills T_hist
             self.observations, self.obs, self.misfit = None, None, None
             if observations is not None:
-                if self.compensated or self.concentration_driven or hist is not None:
+                if self.compensated or (self.concentration_driven and not self._INVERSE_CALIBRATION) or hist is not None:
                     raise ValueError("observations= cannot be combined with compensated=True, concentration_driven=True or "
                                      "hist=: the misfit is carried by the plain forward forms only")
                 if not self.lib.fiveeq_misfit_layout_supported(G, n_pools):
@@ -320,7 +322,8 @@ class EnsembleEngine(CheckpointMixin):
                 self.misfit = torch.zeros((3, N), dtype=torch.float64, device=dev)
             self.forcing, self.fscale, self.fext = None, None, None
             if forcing is not None:
-                for flag, why in ((hist is not None, "hist="), (self.concentration_driven, "concentration_driven=True"),
+                for flag, why in ((hist is not None, "hist="),
+                                  (self.concentration_driven and not self._INVERSE_CALIBRATION, "concentration_driven=True"),
                                   (self.compensated, "compensated=True")):
                     if flag:
                         raise ValueError(f"forcing= cannot be combined with {why}: the forcing scales are carried by the plain "
@@ -1311,6 +1314,42 @@ class EnsembleEngine(CheckpointMixin):
         if self.observations is not None:
             extra += 48.0 / max(int(span), 1)
         return w * (out + (2 * SP + 3 * G + 6 + fr) / max(int(span), 1)) + extra + ring
+
+
+class ConcentrationDrivenEngine(EnsembleEngine):
+    """A concentration-driven (inverse) ensemble that carries per-member forcing scales and the in-loop misfit: the history
+    leg of a calibration.  `concentrations` [n_steps, G] are the target concentrations at the end of each step, shared by
+    all members; the emissions that reach them are diagnosed per member into `E` and cumulated in `cumE`, as
+    EnsembleEngine(concentration_driven=True) does.  On top of that
+        forcing=       a forcing.ExternalForcings table [n_steps, K]: the member scales the forcing of gas g by
+                       params["f_scale"][g] and category k by params["fx_scale"][k] — F = F_ext + sum_k sx_k X[t, k] +
+                       sum_g sg_g F_g, every term one fma, as in the forward forcing form;
+        observations=  a constrain.Observations table: `misfit` [3, N] is accumulated in-loop from T; chi2() scores.
+    Every other argument is EnsembleEngine's (concentration_driven itself is not one: it is always True).  One time-fused
+    launch per run() call (fiveeq_run_inverse_forc_*, include/fiveeq.h): without forcing= and observations= that is the plain
+    inverse kernel; unit scales with K = 0 or a zero table give its bits, and observations= changes nothing but `misfit`.  Pool
+    layouts {4} and 4 + 1 + 1 for either feature.
+    What an EnsembleEngine offers on its rows works here as there: fscale, misfit, chi2(), score() of T, stats(),
+    gather_summary(), parameter_rows() and drivers() with the scale rows, state_dict() / load_state_dict() (cumE, misfit and
+    the forcing identity travel), reset_state(), bytes_per_member_step().  Refused as for every concentration-driven engine:
+    the scenario axis, hist=, compensated=True, mode 'small', forcing_rows() (the C rows hold emissions) and resampled()
+    (cumE does not travel).
+    A projection branches off through R0 / S0: EnsembleEngine(params, N, emissions, forcing=..., R0=hist.R, S0=hist.S) — the
+    forward engine with the same f_scale / fx_scale rows continues T without a jump."""
+
+    _INVERSE_CALIBRATION = True
+
+    def __init__(self, params, n_members, concentrations, *, forcing=None, observations=None, **kw):
+        if "concentration_driven" in kw:
+            raise TypeError("ConcentrationDrivenEngine is always concentration-driven: concentration_driven= is not an argument")
+        super().__init__(params, n_members, concentrations, concentration_driven=True, forcing=forcing,
+                         observations=observations, **kw)
+
+    def _run_inverse(self, t_begin, t_end, stream):
+        forc = (None, None, 0) if self.fscale is None else (self._ptr(self.fscale), self._ptr(self.fext), self.forcing.n_categories)
+        obs = (None, None) if self.misfit is None else self._obs_args()
+        return self._fn("run_inverse_forc")(*self._run_args(t_begin, t_end, cumE=self._ptr(self.cumE)), *forc, *obs,
+                                            self._stream(stream))
 
 
 def run_ensemble(emissions, params, n_members, *, F_ext=None, dt=1.0, dtype=torch.float64, device=None,

@@ -307,8 +307,8 @@ int32_t fiveeq_max_scenarios(void);
  *   form FIVEEQ_FORM_FUSED: the time-fused kernel over spans of k_steps (0 = one launch for the range): the scales stay on
  *       chip for the span and the table chunk is staged through LDS beside the drive chunk.
  * Every form gives the same bits, fp32 packed or not.  Pool layouts {4} and 4 + 1 + 1 (fiveeq_forcing_layout_supported); not
- * in the small-ensemble, concentration-driven, compensated or histogram-ring forms; under the scenario axis through
- * fiveeq_run_scen_forc_* below (without the misfit).  FIVEEQ_E_INVALID for a NULL or
+ * in the small-ensemble, compensated or histogram-ring forms; under the scenario axis through
+ * fiveeq_run_scen_forc_* below (without the misfit); concentration-driven through fiveeq_run_inverse_forc_*.  FIVEEQ_E_INVALID for a NULL or
  * misaligned fscale, n_fext outside 0..4, a NULL fext with n_fext > 0, exactly one of obs / misfit set, a layout without the
  * form, an unknown form, k_steps < 0 or a step range outside [0, n_steps) — before anything is launched. */
 int fiveeq_run_forc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
@@ -474,6 +474,37 @@ int fiveeq_run_inverse_f32(const fiveeq_model *model, int64_t n_members, int64_t
                            const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
                            const float *r, const float *q, float *R, float *S, float *cumE,
                            float *E_traj, float *T_traj, int32_t n_rows, double *T_stats, void *stream);
+
+/* CONCENTRATION-DRIVEN RUNS WITH FORCING SCALES AND THE IN-LOOP MISFIT (new; ADDITIVE: FIVEEQ_ABI_VERSION stays 13, no existing
+ * prototype or struct changes, sizeof(fiveeq_model) stays 448).  The arguments of fiveeq_run_inverse_*, then fscale, fext,
+ * n_fext of FORCING SCALES and obs, misfit of CONSTRAINED RUNS above (the same layouts), then stream.  The gas step is the
+ * inverse step as it stands: the target concentrations are reached whatever the scales, E_traj and cumE do not see them in
+ * the step that forms them.  The forcing of the step is accumulated as in the forward forcing form,
+ *     F = drive[t][6];   F = fma(sx_k, fext[t][k], F), k = 0 .. n_fext-1;   F = fma(sg_g, F_g, F), g = 0 .. G-1
+ * with F_g the forcing of the concentration gas g reached, so T, the boxes — and through T the next step's emissions — carry
+ * the member's scales; the misfit is accumulated from T exactly as in the forward forms.
+ *   fscale  may be NULL: no scales; then n_fext must be 0 (fext is not read);
+ *   obs, misfit  both NULL (no misfit) or both set;
+ *   all three NULL: the call IS fiveeq_run_inverse_* (the same kernel).
+ * Unit scales with n_fext == 0, or with an all-zero table, give fiveeq_run_inverse_* bit for bit; obs / misfit change nothing
+ * but the misfit rows.  One launch for the whole span: the scales stay on chip, the table chunk is staged through LDS beside
+ * the drive chunk, the accumulators cross HBM once.  One member per lane in both precisions.  Pool layouts {4} and 4 + 1 + 1
+ * for the scales and for the misfit (any compiled layout with all three NULL).  FIVEEQ_E_INVALID, in this order and before
+ * anything is launched: the base arguments as fiveeq_run_inverse_* reports them, a NULL cumE, n_fext outside 0..4, a NULL
+ * fscale with n_fext > 0, a misaligned fscale, a NULL fext with n_fext > 0, a misaligned fext, a layout without the forcing
+ * form, exactly one of obs / misfit set, misaligned obs / misfit, a layout without the misfit form. */
+int fiveeq_run_inverse_forc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                const double *r, const double *q, double *R, double *S, double *cumE,
+                                double *E_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                                const double *fscale, const double *fext, int32_t n_fext,
+                                const double *obs, double *misfit, void *stream);
+int fiveeq_run_inverse_forc_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                const float *r, const float *q, float *R, float *S, float *cumE,
+                                float *E_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                                const float *fscale, const float *fext, int32_t n_fext,
+                                const double *obs, double *misfit, void *stream);
 
 /* Ensemble form of the reference's one function,
  *   calculate_hfc_conc(emissions, time, lifetime) = emissions[0]*exp(-time)
