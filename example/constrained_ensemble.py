@@ -5,6 +5,7 @@ The record is the synthetic one committed for the tests (tests/golden/obs_synthe
 tests/golden/make_obs_synthetic.py: one known member plus 0.1 K noise over 1900..2069).  Needs an MI355X.
 
     python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing] [--co2-record] [--concentration-driven]
+                                           [--variability SIGMA PHI]
 
 --forcing adds forcing uncertainty (EnsembleEngine(forcing=), fiveeqscm_amd/forcing.py): an aerosol-like cooling scaled per
 member, and the accepted range of ECS with a shared and with a sampled scale.
@@ -14,6 +15,9 @@ carbon-cycle parameter r0 of CO2 with and without the CO2 record.
 --concentration-driven runs the calibration the other way round (ConcentrationDrivenEngine): the history 1750..2019 is driven by
 "observed" concentrations, every member carries its own aerosol scale and is scored against the warming record in-loop; the
 weighted ensemble then branches into an emission-driven projection to 2499 through R0 / S0.
+--variability SIGMA PHI gives every member its own AR(1) forcing noise (standard deviation SIGMA W m-2, lag-1 autocorrelation
+PHI; forcing.ar1_noise_rows, EnsembleEngine(member_forcing=)), constrains with the in-loop misfit and prints the accepted
+fraction and the 5-95 % range of the final T with and without the variability.
 """
 import argparse
 import os
@@ -39,6 +43,8 @@ def main():
                     help="also score the stored CO2 rows against a synthetic CO2 record and print what it does to r0 of CO2")
     ap.add_argument("--concentration-driven", action="store_true",
                     help="also constrain a concentration-driven history with an aerosol scale per member and branch into a projection")
+    ap.add_argument("--variability", nargs=2, type=float, metavar=("SIGMA", "PHI"),
+                    help="also give every member AR(1) forcing noise (W m-2, lag-1 autocorrelation) and constrain with it")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -67,6 +73,8 @@ def main():
         co2_record(p, N, n_steps, dtype, obs, run_years, years)
     if a.concentration_driven:
         concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma)
+    if a.variability:
+        internal_variability(p, N, n_steps, dtype, obs, run_years, *a.variability)
 
 
 def co2_record(p, N, n_steps, dtype, obs, run_years, years, truth=12345, sigma_ppm=1.0):
@@ -137,6 +145,31 @@ def concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, 
         print(f"  T({int(run_years[last])}) {label:11s} 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} K")
     hist.close()
     proj.close()
+
+
+def internal_variability(p, N, n_steps, dtype, obs, run_years, sigma_f, phi):
+    """--variability: the observed record contains year-to-year noise a deterministic member cannot produce, so the chi2
+    charges every member for it and the posterior comes out too narrow.  With a stochastic forcing realisation per member
+    (rows [n_steps, N]: n_steps N w bytes on the device, 3 GB for 1M fp32 members over 750 steps) the members carry such noise
+    themselves."""
+    from fiveeqscm_amd.forcing import ar1_noise_rows
+    E = emissions.rcp_like_emissions(n_steps, 3)
+    last = n_steps - 1
+    rows = ar1_noise_rows(N, n_steps, sigma_f, phi, device="cuda:0", dtype=dtype)
+    print(f"internal variability: AR(1) forcing noise, sigma {sigma_f} W m-2, phi {phi} ({rows.numel() * rows.element_size() / 1e6:.0f} MB of rows)")
+    for label, mf in (("without", None), ("with", rows)):
+        eng = EnsembleEngine(p, N, E, dtype=dtype, observations=obs, member_forcing=mf, output_steps=[last],
+                             store_concentrations=False, device="cuda:0")
+        eng.run(mode="auto")
+        keep = constrain.accept_rejection(eng.chi2(), constrain.ACCEPT_SEED, 0, N)
+        n_keep = int(keep.sum())
+        if n_keep:
+            q = eng.gather_summary([last], percentiles=(5.0, 95.0), accepted=keep)["percentiles"][0].tolist()
+        else:
+            q = [float("nan")] * 2
+        print(f"  {label:7s} variability (mode {eng.last_mode}): accepted {n_keep} of {N} ({n_keep / N:.4f}); "
+              f"T({int(run_years[last])}) 5-95 %: {q[0]:.3f} .. {q[1]:.3f} K")
+        eng.close()
 
 
 def forcing_uncertainty(p, N, n_steps, dtype, obs):

@@ -101,6 +101,7 @@ def _run_args(tail, scen=False, cumE=False):
 _ST, _PLAN, _FORM, _OBS, _FORC = [_p], [ctypes.POINTER(_p)], [_i32, _i32, _p], [_p, _p], [_p, _p, _i32]
 _RING = [ctypes.c_double, ctypes.c_double, _i32, _p, _i32]
 _UNI = [ctypes.c_uint32, _p]        # (mask, values): the single-valued parameter rows, values on the host
+_MFORC = [_p, _i32]                 # (mforc, n_mforc_rows): the member-forcing rows
 # the stepping entry points that come as _f64 and _f32: name -> _run_args(...)
 _RUNS = {
     "run": _run_args(_ST),
@@ -118,6 +119,8 @@ _RUNS = {
     "plan_create_scen": _run_args(_PLAN, scen=True),
     "run_forc": _run_args(_FORC + _OBS + _FORM),
     "plan_create_forc": _run_args(_FORC + _OBS + _PLAN),
+    "run_mforc": _run_args(_FORC + _OBS + _MFORC + _FORM),
+    "plan_create_mforc": _run_args(_FORC + _OBS + _MFORC + _PLAN),
     "run_scen_forc": _run_args(_FORC + _FORM, scen=True),
     "plan_create_scen_forc": _run_args(_FORC + _PLAN, scen=True),
     "run_uniform": _run_args(_UNI + _ST),
@@ -157,6 +160,9 @@ SIGNATURES = {
     "fiveeq_rows_streamed": (ctypes.c_int, [_i32, ctypes.POINTER(_i32), _i64, _i64, _i32]),
     "fiveeq_lhs_rows_f64": (ctypes.c_int, [ctypes.c_uint64, _i64, _i64, _i64, _i32, _i32, _i64, _p, _p]),
     "fiveeq_lhs_rows_host_f64": (ctypes.c_int, [ctypes.c_uint64, _i64, _i64, _i64, _i32, _i32, _i64, _p]),
+    # (seed, m0, n_members, ld, t_begin, t_end, phi, s, xi_state, rows, stream)
+    "fiveeq_noise_rows_f64": (ctypes.c_int, [ctypes.c_uint64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
+    "fiveeq_noise_rows_f32": (ctypes.c_int, [ctypes.c_uint64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "fiveeq_plan_launch": (ctypes.c_int, [_p, _p]),
     "fiveeq_plan_destroy": (ctypes.c_int, [_p]),
     "fiveeq_hfc_conc_f64": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, _p, _p]),
@@ -224,7 +230,7 @@ _lib = None
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
-    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp")) + (
+    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp", "fiveeq_noise.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

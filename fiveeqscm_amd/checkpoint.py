@@ -32,6 +32,8 @@ class CheckpointMixin:
         if self.forcing is not None:                             # which forcing set the state was run under
             out["forcing_sha256"] = self.forcing.sha256
             out["fscale_sha256"] = self.fscale_sha256()
+        if getattr(self, "member_forcing", None) is not None:    # which per-member series the state was run under
+            out["member_forcing_sha256"] = self.member_forcing_sha256()
         if self.scenario_axis:                                   # which scenario set the per-scenario state belongs to
             out["n_scenarios"] = int(self.n_scenarios)
             out["drive_sha256"] = self.drive_sha256
@@ -73,6 +75,9 @@ class CheckpointMixin:
         theirs = (state.get("forcing_sha256"), state.get("fscale_sha256")) if "forcing_sha256" in state else None
         if theirs != mine:
             raise ValueError(f"checkpoint forcing set (table sha256, scale rows sha256) {theirs!r} is not this engine's {mine!r}")
+        mine = None if getattr(self, "member_forcing", None) is None else self.member_forcing_sha256()
+        if state.get("member_forcing_sha256") != mine:
+            raise ValueError(f"checkpoint member_forcing rows {state.get('member_forcing_sha256')!r} are not this engine's ({mine!r})")
         mine = (self.n_scenarios, self.drive_sha256) if self.scenario_axis else None
         theirs = (int(state["n_scenarios"]), state.get("drive_sha256")) if "n_scenarios" in state else None
         if theirs != mine:

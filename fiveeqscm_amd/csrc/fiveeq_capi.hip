@@ -285,6 +285,7 @@ struct RunArgs : BaseArgs<T> {
     BinRing br;                  // the histogram forms' ring (else none)
     MisfitRows mf;               // the constrained forms' accumulators (else none)
     ForcRows<T> fc;              // the forcing forms' scale rows and table (else none)
+    const T* mforc = nullptr;    // the member-forcing forms' rows [n_steps][ld] (else none)
     UniformRows<T> uni{};        // the single-valued parameter rows of fiveeq_run_uniform (mask 0: every row is loaded)
 };
 
@@ -351,20 +352,26 @@ constexpr bool uniform_layout(int code) { return misfit_layout(code); }
 // SCEN: the scenario axis (step_scen_kernel; the fused kernel with the scenario as blockIdx.y).
 // FORC: the per-member forcing scales (with or without MISFIT, or with SCEN: the scale rows shared by the scenarios, a table
 // per scenario).
-template <typename T, bool BINS = false, bool MISFIT = false, bool SCEN = false, bool FORC = false>
+// MFORC: a per-member forcing row per step on top of FORC (step_mforc_kernel, fused_mforc_kernel), with or without MISFIT.
+template <typename T, bool BINS = false, bool MISFIT = false, bool SCEN = false, bool FORC = false, bool MFORC = false>
 int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
     static_assert(BINS + MISFIT + SCEN <= 1, "the histogram ring, the misfit and the scenario axis are separate forms");
     static_assert(!FORC || !BINS, "the forcing scales combine with the misfit or the scenario axis only");
+    static_assert(!MFORC || (FORC && !SCEN), "the member-forcing rows ride on the forcing-scale forms without the scenario axis");
     const bool packed = LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0) &&
-                        (!FORC || (((uintptr_t)a.fc.fscale) & 7) == 0);
+                        (!FORC || (((uintptr_t)a.fc.fscale) & 7) == 0) && (!MFORC || (((uintptr_t)a.mforc) & 7) == 0);
     unsigned blocks;
     if (int rc = grid_blocks(a.n, (int64_t)FIVEEQ_STEP_BLOCK * (packed ? 2 : 1), blocks)) return rc;
     const dim3 grid(blocks), block(FIVEEQ_STEP_BLOCK);
     switch (a.code) {
 #define FIVEEQ_STEP_LAUNCH(V, p0, p1, p2, NT)                                                                                     \
     do {                                                                                                                          \
-        if constexpr (SCEN)                                                                                                       \
+        if constexpr (MFORC)                                                                                                      \
+            hipLaunchKernelGGL((step_mforc_kernel<V, p0, p1, p2, MISFIT>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n,  \
+                               a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.mf.obs, a.mf.misfit,            \
+                               a.fc.fscale, a.fc.fext, a.fc.n_fext, a.mforc);                                                     \
+        else if constexpr (SCEN)                                                                                                  \
             hipLaunchKernelGGL((step_scen_kernel<V, p0, p1, p2, NT, FORC>), grid, block, 0, st, a.km, a.drive, a.n_steps, t, a.n, \
                                a.ld, a.n_scen, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats, a.fc.fscale, a.fc.fext, \
                                a.fc.n_fext);                                                                                      \
@@ -421,9 +428,10 @@ int launch_step(const RunArgs<T>& a, int t, hipStream_t st) {
 }
 
 template <typename T, bool INV = false, bool BINS = false, bool COMP = false, bool MISFIT = false, bool SCEN = false,
-          bool FORC = false>
+          bool FORC = false, bool MFORC = false>
 int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
     using P = typename LaneOf<T>::Packed;
+    static_assert(!MFORC || (FORC && !INV && !SCEN), "the member-forcing rows ride on the forward forcing-scale forms only");
     static_assert(!FORC || (!BINS && !COMP), "the forcing scales are carried by the plain forward and inverse forms only");
     static_assert(!MISFIT || (!BINS && !COMP), "the misfit is carried by the plain forward and inverse forms only");
     static_assert(!SCEN || (!INV && !BINS && !COMP && !MISFIT), "the scenario axis is carried by the plain forward form only");
@@ -432,16 +440,23 @@ int launch_fused(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
     // have a packed instantiation for some layouts only (misfit_packed_fused) — decided HERE, before the grid is sized for it
     const bool packed = HAS_PACKED && (!MISFIT || misfit_packed_fused(a.code / 100, a.code / 10 % 10, a.code % 10)) &&
                         LaneOf<T>::can_pack(a) && (!BINS || (((uintptr_t)a.br.ring) & 3) == 0) &&
-                        (!FORC || (((uintptr_t)a.fc.fscale) & 7) == 0);
+                        (!FORC || (((uintptr_t)a.fc.fscale) & 7) == 0) && (!MFORC || (((uintptr_t)a.mforc) & 7) == 0);
     unsigned blocks;
     if (int rc = grid_blocks(a.n, (int64_t)FIVEEQ_BLOCK * (packed ? 2 : 1), blocks)) return rc;
     const dim3 grid(blocks, (unsigned)a.n_scen), block(FIVEEQ_BLOCK);     // the scenarios are rows of the grid
     switch (a.code) {
 #define FIVEEQ_FUSED_LAUNCH(V, p0, p1, p2, I)                                                                                    \
-    hipLaunchKernelGGL((fused_kernel<V, p0, p1, p2, I, BINS, COMP, MISFIT, SCEN, FORC>), grid, block, FIVEEQ_FUSED_DYN_LDS, st,  \
-                       a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.cumE, a.C_traj, a.T_traj,      \
-                       a.n_rows, a.stats, a.br.ring, a.br.ring_rows, a.br.lo, a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit,    \
-                       a.fc.fscale, a.fc.fext, a.fc.n_fext)
+    do {                                                                                                                         \
+        if constexpr (MFORC)                                                                                                     \
+            hipLaunchKernelGGL((fused_mforc_kernel<V, p0, p1, p2, MISFIT>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km, a.drive, \
+                               a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.C_traj, a.T_traj, a.n_rows, a.stats,  \
+                               a.mf.obs, a.mf.misfit, a.fc.fscale, a.fc.fext, a.fc.n_fext, a.mforc);                             \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((fused_kernel<V, p0, p1, p2, I, BINS, COMP, MISFIT, SCEN, FORC>), grid, block,                    \
+                               FIVEEQ_FUSED_DYN_LDS, st, a.km, a.drive, a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R,     \
+                               a.S, a.cumE, a.C_traj, a.T_traj, a.n_rows, a.stats, a.br.ring, a.br.ring_rows, a.br.lo,           \
+                               a.br.inv_w, a.br.n_bins, a.mf.obs, a.mf.misfit, a.fc.fscale, a.fc.fext, a.fc.n_fext);             \
+    } while (0)
 #define X(p0, p1, p2)                                                                                  \
     case (p0) * 100 + (p1) * 10 + (p2):                                                                \
         if constexpr (MISFIT && !misfit_layout(p0, p1, p2)) {                                          \
@@ -548,6 +563,18 @@ int check_forcing(RunArgs<T>& a, const T* fscale, const T* fext, int32_t n_fext)
     return FIVEEQ_OK;
 }
 
+// the member-forcing rows mforc [n_mforc_rows][ld] of a forcing-scale call (check_forcing has passed: the layout carries the
+// form): present, aligned to the kernel's word, and long enough for the steps of this call
+template <typename T>
+int check_mforc(RunArgs<T>& a, const T* mforc, int32_t n_mforc_rows) {
+    if (int rc = check_not_null({{"mforc", mforc}})) return rc;
+    if (int rc = check_aligned({{"mforc", mforc, sizeof(T)}})) return rc;
+    if (n_mforc_rows < a.t_end)
+        return fail(FIVEEQ_E_INVALID, "n_mforc_rows=%d < t_end=%d: mforc holds one row per step from step 0", n_mforc_rows, a.t_end);
+    a.mforc = mforc;
+    return FIVEEQ_OK;
+}
+
 // the single-valued parameter rows (step_uniform_kernel): the caller's mask over the 3G rows of r and the 2 of q, and their
 // values (host).  A layout without the form keeps mask 0 and launches what the plain call launches.
 template <typename T>
@@ -595,6 +622,9 @@ struct Features {
     const T* values = nullptr;   // host, 3G + 2
     bool inv = false;            // fiveeq_run_inverse_forc: cumE is the caller's, required
     T* cumE = nullptr;
+    bool mforc = false;          // fiveeq_run_mforc / fiveeq_plan_create_mforc (a forcing family: forc is set too): the rows are the caller's
+    const T* mforc_rows = nullptr;
+    int32_t n_mforc_rows = 0;
 };
 
 // Every check of a forward call but its last (the form of a run, the range of a plan), in the ONE order every family reports
@@ -614,6 +644,7 @@ int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan
     }
     if (int rc = f.uniform ? check_uniform(a, f.mask, f.values) : FIVEEQ_OK) return rc;
     if (int rc = f.forc ? check_forcing(a, f.fc.fscale, f.fc.fext, f.fc.n_fext) : FIVEEQ_OK) return rc;
+    if (int rc = f.mforc ? check_mforc(a, f.mforc_rows, f.n_mforc_rows) : FIVEEQ_OK) return rc;
     if (f.misfit == OPTIONAL && (f.mf.obs == nullptr) != (f.mf.misfit == nullptr))
         return fail(FIVEEQ_E_INVALID, "obs and misfit go together: both NULL (no misfit) or both set (obs=%p misfit=%p)",
                     (const void*)f.mf.obs, (void*)f.mf.misfit);
@@ -622,21 +653,24 @@ int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan
 }
 
 // one kernel family: one launch per step, or the fused kernel over spans of k_steps steps
-template <typename T, bool MISFIT, bool SCEN, bool FORC>
+template <typename T, bool MISFIT, bool SCEN, bool FORC, bool MFORC = false>
 int run_family(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
     if (form == FIVEEQ_FORM_PER_STEP)
-        return each_step(a, [&](int t) { return launch_step<T, false, MISFIT, SCEN, FORC>(a, t, st); });
+        return each_step(a, [&](int t) { return launch_step<T, false, MISFIT, SCEN, FORC, MFORC>(a, t, st); });
     return each_span(a, k_steps,
-                     [&](int t0, int t1) { return launch_fused<T, false, false, false, MISFIT, SCEN, FORC>(a, t0, t1, st); });
+                     [&](int t0, int t1) { return launch_fused<T, false, false, false, MISFIT, SCEN, FORC, MFORC>(a, t0, t1, st); });
 }
 
-// the forward model in the family prepare() found: plain, MISFIT, SCEN, FORC, FORC + MISFIT or SCEN + FORC (the six that
-// are compiled) — picked once per C call, outside the launch loops
+// the forward model in the family prepare() found: plain, MISFIT, SCEN, FORC, FORC + MISFIT, SCEN + FORC, or FORC + MFORC with or
+// without MISFIT (the eight that are compiled) — picked once per C call, outside the launch loops
 template <typename T>
 int run_form(const RunArgs<T>& a, int32_t form, int32_t k_steps, hipStream_t st) {
     const bool forc = a.fc.fscale != nullptr, misfit = a.mf.misfit != nullptr;
     if (a.scen)
         return forc ? run_family<T, false, true, true>(a, form, k_steps, st) : run_family<T, false, true, false>(a, form, k_steps, st);
+    if (a.mforc != nullptr)
+        return misfit ? run_family<T, true, false, true, true>(a, form, k_steps, st)
+                      : run_family<T, false, false, true, true>(a, form, k_steps, st);
     if (forc)
         return misfit ? run_family<T, true, false, true>(a, form, k_steps, st) : run_family<T, false, false, true>(a, form, k_steps, st);
     return misfit ? run_family<T, true, false, false>(a, form, k_steps, st) : run_family<T, false, false, false>(a, form, k_steps, st);
@@ -860,6 +894,45 @@ int plan_create(const BaseArgs<T>& b, const Features<T>& f, void** plan_out) {
         return fail(FIVEEQ_E_INVALID, "out of host memory");
     }
     *plan_out = p;
+    return FIVEEQ_OK;
+}
+
+// what fiveeq_run_mforc / fiveeq_plan_create_mforc carry: fiveeq_run_forc's features (the scales, the optional misfit) and the
+// member-forcing rows
+template <typename T>
+Features<T> mforc_features(const ForcRows<T>& fc, const MisfitRows& mf, const T* mforc, int32_t n_mforc_rows) {
+    Features<T> f;
+    f.forc = true;
+    f.fc = fc;
+    f.misfit = OPTIONAL;
+    f.mf = mf;
+    f.mforc = true;
+    f.mforc_rows = mforc;
+    f.n_mforc_rows = n_mforc_rows;
+    return f;
+}
+
+// ---- per-member AR(1) noise rows (noise_rows_kernel): every check, then one launch ---------------------------------------
+// [t_begin, t_end) = [-1, 0) is the start call (fiveeq_noise.hpp): it stores no row, so rows may be NULL there.
+template <typename T>
+int noise_rows(uint64_t seed, int64_t m0, int64_t n, int64_t ld, int32_t t_begin, int32_t t_end, const T* phi, const T* s,
+               double* xi_state, T* rows, void* stream) {
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (m0 < 0) return fail(FIVEEQ_E_INVALID, "m0=%lld must be >= 0", (long long)m0);
+    const bool start = t_begin == -1;
+    if (t_begin < -1 || t_end < t_begin || (start && t_end != 0))
+        return fail(FIVEEQ_E_INVALID, "step range [%d,%d): want 0 <= t_begin <= t_end, or [-1,0) for the stationary start", t_begin,
+                    t_end);
+    if (int rc = check_not_null({{"phi", phi}, {"s", s}, {"xi_state", xi_state}, {"rows", rows, 1, !start}})) return rc;
+    if (int rc = check_aligned({{"phi", phi, sizeof(T)}, {"s", s, sizeof(T)}, {"xi_state", xi_state, 8}, {"rows", rows, sizeof(T)}}))
+        return rc;
+    if (t_begin == t_end) return FIVEEQ_OK;
+    unsigned blocks;
+    if (int rc = grid_blocks(n, FIVEEQ_BLOCK, blocks)) return rc;
+    hipLaunchKernelGGL((noise_rows_kernel<T>), dim3(blocks), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, seed, m0, n, ld, (int)t_begin,
+                       (int)t_end, phi, s, xi_state, rows);
+    HIP_TRY(hipGetLastError());
     return FIVEEQ_OK;
 }
 
@@ -1209,6 +1282,46 @@ int fiveeq_plan_create_forc_f32(const fiveeq_model* model, int64_t n_members, in
                                 int32_t n_fext, const double* obs, double* misfit, void** plan_out) {
     return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
                               {false, 1, true, {fscale, fext, n_fext}, OPTIONAL, {obs, misfit}}, plan_out);
+}
+int fiveeq_run_mforc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                         int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
+                         double* T_traj, int32_t n_rows, double* T_stats, const double* fscale, const double* fext, int32_t n_fext,
+                         const double* obs, double* misfit, const double* mforc, int32_t n_mforc_rows, int32_t form, int32_t k_steps,
+                         void* stream) {
+    return run_forward<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                            mforc_features<double>({fscale, fext, n_fext}, {obs, misfit}, mforc, n_mforc_rows), form, k_steps, 0, stream);
+}
+int fiveeq_plan_create_mforc_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                                 int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* C_traj,
+                                 double* T_traj, int32_t n_rows, double* T_stats, const double* fscale, const double* fext,
+                                 int32_t n_fext, const double* obs, double* misfit, const double* mforc, int32_t n_mforc_rows,
+                                 void** plan_out) {
+    return plan_create<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                            mforc_features<double>({fscale, fext, n_fext}, {obs, misfit}, mforc, n_mforc_rows), plan_out);
+}
+int fiveeq_noise_rows_f64(uint64_t seed, int64_t m0, int64_t n_members, int64_t ld, int32_t t_begin, int32_t t_end, const double* phi,
+                          const double* s, double* xi_state, double* rows, void* stream) {
+    return noise_rows<double>(seed, m0, n_members, ld, t_begin, t_end, phi, s, xi_state, rows, stream);
+}
+int fiveeq_run_mforc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                         int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
+                         float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext, int32_t n_fext,
+                         const double* obs, double* misfit, const float* mforc, int32_t n_mforc_rows, int32_t form, int32_t k_steps,
+                         void* stream) {
+    return run_forward<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                            mforc_features<float>({fscale, fext, n_fext}, {obs, misfit}, mforc, n_mforc_rows), form, k_steps, 0, stream);
+}
+int fiveeq_plan_create_mforc_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                                 int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* C_traj,
+                                 float* T_traj, int32_t n_rows, double* T_stats, const float* fscale, const float* fext,
+                                 int32_t n_fext, const double* obs, double* misfit, const float* mforc, int32_t n_mforc_rows,
+                                 void** plan_out) {
+    return plan_create<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, C_traj, T_traj, n_rows, T_stats},
+                            mforc_features<float>({fscale, fext, n_fext}, {obs, misfit}, mforc, n_mforc_rows), plan_out);
+}
+int fiveeq_noise_rows_f32(uint64_t seed, int64_t m0, int64_t n_members, int64_t ld, int32_t t_begin, int32_t t_end, const float* phi,
+                          const float* s, double* xi_state, float* rows, void* stream) {
+    return noise_rows<float>(seed, m0, n_members, ld, t_begin, t_end, phi, s, xi_state, rows, stream);
 }
 int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     return fiveeq_layout_supported(n_gas, n_pools) && forcing_layout(layout_code(n_gas, n_pools)) ? 1 : 0;

@@ -12,6 +12,7 @@
 // The kernels, by the header that holds them:
 //   fiveeq_step.hpp     1   step_kernel        one timestep per launch — the north-star form; HBM-bound, A = w(2SP + 4G + 7) per member-step
 //                       1s  step_scen_kernel   the same under several emission scenarios
+//                       1m  step_mforc_kernel  the same with a per-member forcing row per step (2m: fused_mforc_kernel)
 //   fiveeq_fused.hpp    2   fused_kernel       time-fused (and, INV = true, concentration-driven); state in registers; VALU-bound
 //   fiveeq_small.hpp    2c  small_kernel       small ensembles: one member per quad of lanes (pool per lane), the model in registers
 //                       2d  small_multi_kernel, small_octet_kernel: the same for several gases
@@ -27,6 +28,7 @@
 //   fiveeq_score.hpp    11  score_rows_kernel   the misfit accumulators of stored rows against observed records, live rows only
 //   fiveeq_forcrows.hpp 12 forcing_rows_kernel the forcing, energy imbalance and heat uptake of a run recomputed from its stored rows
 //   fiveeq_pulse.hpp    13 pulse_response_kernel the forcing, warming and concentration response to emission pulses, summed to horizons
+//   fiveeq_noise.hpp    14 noise_rows_kernel    per-member AR(1) noise rows from a counter-based integer deviate (member_forcing rows)
 // and what they share: fiveeq_math.hpp (the model struct, lane types, fe_* math), fiveeq_stats.hpp (per-wave statistics, the bin
 // rule), fiveeq_member.hpp (member_step(), gas_forcing(), the misfit update, the lane's member span and row access).
 // All model arithmetic is member_step(): every kernel that steps the model gives the same bits.
@@ -78,3 +80,4 @@ constexpr int DRIVE_STRIDE = 8;
 #include "fiveeq_score.hpp"
 #include "fiveeq_forcrows.hpp"
 #include "fiveeq_pulse.hpp"
+#include "fiveeq_noise.hpp"

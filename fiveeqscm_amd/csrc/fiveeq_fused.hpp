@@ -243,4 +243,142 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Kernel 2m — fused_kernel<V, P0, P1, P2, false, false, false, MISFIT, false, true> WITH A PER-MEMBER FORCING ROW PER STEP
+// (member_step<.., MFORC>; fiveeq_run_mforc_*, include/fiveeq.h "MEMBER FORCING"): mforc [n_steps][ld].  The row is STREAMED,
+// not resident: the lane loads its element of row t + 1 while it computes step t (one step ahead, as the small kernels read the
+// drive record ahead) — w bytes per member-step in this form too; a packed fp32 lane loads its two members as one 8-byte
+// access.  Everything else — the scales and where they live (FusedForc), the staged drive and table chunks, the misfit slot,
+// the statistics tile, the stores — is fused_kernel's forward FORC form, statement for statement.
+// A KERNEL OF ITS OWN, not one more flag of fused_kernel and not a body the two share: a template parameter would rename
+// every fused_kernel symbol, and moving fused_kernel's text into a shared force-inlined body reordered the instructions of
+// all 199 of its instantiations (profiles/r25/member_forcing_isa.txt).  This way every kernel that existed keeps its symbol
+// and its machine code.  The {4} and 4 + 1 + 1 layouts, with and without the misfit.
+// ---------------------------------------------------------------------------------
+template <typename V, int P0, int P1, int P2, bool MISFIT = false>
+__global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_mforc_kernel(
+    const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps,
+    const int t_begin, const int t_end, const int64_t n, const int64_t ld,
+    const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
+    typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
+    typename Lane<V>::S* __restrict__ C_traj /* [n_rows][G][ld] or nullptr */,
+    typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
+    const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */,
+    const typename Lane<V>::S* __restrict__ fscale /* [G + n_fext][ld] */,
+    const typename Lane<V>::S* __restrict__ fext /* [n_steps][MAX_FEXT] */, const int n_fext,
+    const typename Lane<V>::S* __restrict__ mforc /* [n_steps][ld] */) {
+    using L = Layout<P0, P1, P2>;
+    using T = typename Lane<V>::S;
+    constexpr int W = Lane<V>::W;                 // members per lane
+    constexpr int CHUNK = FusedForc<V, L, MISFIT, true>::CHUNK;       // steps staged per refill
+    constexpr bool FS_LDS = FusedForc<V, L, MISFIT, true>::FS_LDS;    // the scales in a lane-private LDS slot
+    __shared__ T drv[CHUNK * DRIVE_STRIDE];
+    __shared__ T xs[CHUNK * MAX_FEXT];                                // the table chunk
+    __shared__ V fs_s[FS_LDS ? (L::G + MAX_FEXT) * FIVEEQ_BLOCK : 1];  // FS_LDS: [G + MAX_FEXT][FIVEEQ_BLOCK], lane-private
+    __shared__ double acc_s[MISFIT ? 3 * W * FIVEEQ_BLOCK : 1];       // MISFIT: [3 W][FIVEEQ_BLOCK], lane-private
+    __shared__ V stat_tile[FIVEEQ_BLOCK / 64][STAT_STEPS * STAT_ROW];
+    __shared__ KModel<T> km_s;
+    static_assert(!FS_LDS || sizeof(drv) + sizeof(xs) + sizeof(fs_s) + sizeof(acc_s) + sizeof(stat_tile) + sizeof(km_s) <=
+                                 LDS_PER_CU / FusedForc<V, L, MISFIT, true>::WGS,
+                  "FS_LDS form: the workgroups it is there to keep no longer fit a CU's LDS");
+    stage_model(&km_s);
+    const KModel<T>& kmr = km_s;
+
+    const auto [m, active, full, mm] = lane_span<W, FIVEEQ_BLOCK, PARK_FIRST>(n);    // idle tail lanes shadow member 0 and store nothing
+    const int64_t n_rec = (n + 63) >> 6;                                             // statistics records: one per 64 members
+    const int64_t wave = (int64_t)blockIdx.x * (FIVEEQ_BLOCK / 64) + (threadIdx.x >> 6);
+    const bool wave_live = stats != nullptr && wave * W < n_rec;
+    V* const tile = stat_tile[threadIdx.x >> 6];
+    const int n_valid = (int)min((int64_t)64 * W, n - wave * 64 * W);               // members of this wave (<= 0: none)
+    int ks = 0;                                                                      // steps parked in the tile
+
+    V rr[3 * L::G], qq[2], Rv[L::SP], Sv[2], Cv[L::G], Tn;
+    V no_cum[L::G], no_Rlo[L::SP];                       // never touched: INV = COMP = false
+#pragma unroll
+    for (int k = 0; k < L::SP; ++k) Rv[k] = load_lane<V>(R + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) Sv[k] = load_lane<V>(S + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_lane<V>(r + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) qq[k] = load_lane<V>(q + k * ld + mm);
+    V fs_r[!FS_LDS ? L::G + MAX_FEXT : 1];
+    V* const fs = FS_LDS ? &fs_s[threadIdx.x] : fs_r;    // scale j of this lane at fs[j * FS_STRIDE]
+    constexpr int FS_STRIDE = FS_LDS ? FIVEEQ_BLOCK : 1;
+#pragma unroll
+    for (int k = 0; k < L::G + MAX_FEXT; ++k)
+        fs[k * FS_STRIDE] = k < L::G + n_fext ? load_lane<V>(fscale + k * ld + mm) : (V)T(0);
+    double* const acc = &acc_s[threadIdx.x];             // MISFIT: word k of member j of this lane at acc[(3 j + k) * FIVEEQ_BLOCK]
+    if constexpr (MISFIT) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const int64_t mj = (j == 0 || full) ? mm + j : mm;    // a packed lane's missing second member shadows the first
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc[(3 * j + k) * FIVEEQ_BLOCK] = misfit[k * ld + mj];
+        }
+    }
+    // the lane's element of the NEXT step's row, loaded a step ahead (an idle lane reads member 0's: mm; t < t_end <= n_mforc_rows)
+    V mf_next = V();
+    if (t_begin < t_end) mf_next = load_lane<V>(mforc + (int64_t)t_begin * ld + mm);
+
+    for (int tc = t_begin; tc < t_end; tc += CHUNK) {
+        const int nt = min(CHUNK, t_end - tc);
+        __syncthreads();                                  // previous chunk fully consumed
+        for (int i = threadIdx.x; i < nt * DRIVE_STRIDE; i += FIVEEQ_BLOCK)
+            drv[i] = drive[(int64_t)tc * DRIVE_STRIDE + i];
+        // n_fext == 0: member_step reads no record and fext is not a table — nothing is staged (a wave-uniform test)
+        if (n_fext > 0)
+            for (int i = threadIdx.x; i < nt * MAX_FEXT; i += FIVEEQ_BLOCK) xs[i] = fext[(int64_t)tc * MAX_FEXT + i];
+        __syncthreads();
+        for (int k = 0; k < nt; ++k) {
+            const T* d = &drv[k * DRIVE_STRIDE];
+            const V mf = mf_next;
+            if (tc + k + 1 < t_end) mf_next = load_lane<V>(mforc + (int64_t)(tc + k + 1) * ld + mm);
+            member_step<V, L, false, false, true, NoGasHook, 0, true>(kmr, d, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, FS_STRIDE,
+                                                                      &xs[k * MAX_FEXT], n_fext, NoGasHook{}, mf);
+            if constexpr (MISFIT) misfit_step(obs + (int64_t)(tc + k) * 4, Tn, acc, 3 * FIVEEQ_BLOCK, FIVEEQ_BLOCK, true);
+            const int row = __builtin_amdgcn_readfirstlane((int)d[7]);      // wave-uniform: a scalar branch, scalar row offsets
+            if (row >= 0 && row < n_rows) {
+                if (active) {
+                    if (C_traj != nullptr) {
+                        T* c = C_traj + (int64_t)row * L::G * ld + m;
+#pragma unroll
+                        for (int g = 0; g < L::G; ++g) store_lane(c + g * ld, Cv[g], full);
+                    }
+                    if (T_traj != nullptr) store_lane(T_traj + (int64_t)row * ld + m, Tn, full);
+                }
+            }
+            if (wave_live) {
+                tile[ks * STAT_ROW + (threadIdx.x & 63)] = Tn;
+                if (++ks == STAT_STEPS || tc + k + 1 == t_end) {
+                    const int64_t t_first = (int64_t)(tc + k + 1 - ks);
+                    if constexpr (W == 1) {
+                        wave_stats_flush(tile, ks, n_valid, stats + (wave * n_steps + t_first) * 4, 4);
+                    } else {
+                        wave_stats_flush(tile, ks, n_valid, stats + (2 * wave * n_steps + t_first) * 4,
+                                         2 * wave + 1 < n_rec ? stats + ((2 * wave + 1) * n_steps + t_first) * 4 : nullptr, 4);
+                    }
+                    ks = 0;
+                }
+            }
+        }
+    }
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < L::SP; ++k) store_lane(R + k * ld + m, Rv[k], full);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) store_lane(S + k * ld + m, Sv[k], full);
+        if constexpr (MISFIT) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                if (j == 0 || full) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) misfit[k * ld + m + j] = acc[(3 * j + k) * FIVEEQ_BLOCK];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace fiveeq

@@ -158,16 +158,21 @@ struct NoGasHook {
     template <int g>
     __device__ __forceinline__ void operator()(GasTag<g>) const {}
 };
-template <typename V, typename L, bool INV, bool COMP, bool FORC = false, typename Hook = NoGasHook, int OWN = 0>
+// MFORC = true (with FORC): the member also carries its OWN forcing series, one value per step (member_forcing rows, mf): the
+// step opens F = drive[t][6] + mf — one add — and goes on with the category and gas fmas exactly as FORC does.  A zero mf gives
+// the FORC step bit for bit (x + 0 = x for every x but -0).  MFORC = false is the code as it was.
+template <typename V, typename L, bool INV, bool COMP, bool FORC = false, typename Hook = NoGasHook, int OWN = 0, bool MFORC = false>
 __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& km, const typename Lane<V>::S* __restrict__ drv,
                                             const V (&rr)[3 * L::G], const V (&qq)[2],
                                             V (&R)[L::SP], V (&S)[2], V (&out)[L::G], V& Tnew, V (&cum)[L::G],
                                             V (&Rlo)[L::SP], const V* fs = nullptr, const int fs_stride = 1,
                                             const typename Lane<V>::S* xr = nullptr, const int n_fext = 0,
-                                            const Hook after_gas = Hook{}) {
+                                            const Hook after_gas = Hook{}, const V mf = V()) {
     static_assert(!FORC || !COMP, "the forcing scales are not carried by the compensated form");
+    static_assert(!MFORC || (FORC && !INV), "the per-member forcing row is carried by the forward forcing-scale forms only");
     const V T_old = S[0] + S[1];
     V F = (V)drv[6];
+    if constexpr (MFORC) F = F + mf;
     if constexpr (FORC) {
 #pragma unroll
         for (int k = 0; k < MAX_FEXT; ++k)

@@ -54,7 +54,10 @@ struct UniformRows {
 };
 // The body of step_kernel and step_uniform_kernel (force-inlined: step_kernel's code is what it was when it spelt this out,
 // profiles/r16/uniform_rows_isa.txt).
-template <typename V, int P0, int P1, int P2, bool BINS, bool NT, bool MISFIT, bool FORC, bool UNI>
+// MFORC = true (with FORC; step_mforc_kernel below): the lane also loads its element of THIS step's member_forcing row
+// mforc [n_steps][ld] — one more coalesced row load, issued with the lane's other rows (where F opens: beside the category
+// scales), w bytes more per member-step; a packed fp32 lane loads its two members as one 8-byte access.
+template <typename V, int P0, int P1, int P2, bool BINS, bool NT, bool MISFIT, bool FORC, bool UNI, bool MFORC = false>
 __device__ __forceinline__ void step_body(
     const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
     const int64_t n, const int64_t ld,
@@ -67,7 +70,7 @@ __device__ __forceinline__ void step_body(
     const double* __restrict__ obs, double* __restrict__ misfit,
     const typename Lane<V>::S* __restrict__ fscale,
     const typename Lane<V>::S* __restrict__ fext, const int n_fext,
-    const UniformRows<typename Lane<V>::S>& uni) {
+    const UniformRows<typename Lane<V>::S>& uni, const typename Lane<V>::S* __restrict__ mforc = nullptr) {
     using L = Layout<P0, P1, P2>;
     using T = typename Lane<V>::S;
     constexpr int W = Lane<V>::W;                 // members per lane
@@ -78,6 +81,7 @@ __device__ __forceinline__ void step_body(
     constexpr bool SPREAD = sizeof(T) == 8;
     static_assert(!FORC || (!BINS && !NT), "the forcing scales: no histogram ring, default row policy");
     static_assert(!UNI || (!BINS && !MISFIT && !FORC), "the single-valued rows: the plain forward form only");
+    static_assert(!MFORC || FORC, "the per-member forcing row: a form of the forcing-scale family");
     __shared__ T drv[DRIVE_STRIDE];
     // idle tail lanes load a valid (aligned) member and store nothing
     const LaneSpan span = lane_span<W, FIVEEQ_STEP_BLOCK, PARK_LAST>(n);
@@ -98,6 +102,7 @@ __device__ __forceinline__ void step_body(
 
     V rr[3 * L::G], qq[2], Rv[L::SP], Sv[2], Cv[L::G];
     V fs[FORC ? L::G + MAX_FEXT : 1];             // FORC: the lane's scales, gas rows first (rows past n_fext are never read)
+    V mf = V();                                   // MFORC: the lane's element of this step's member_forcing row
     // one parameter row: the load, or (UNI, bit set) the single value from the kernel arguments
     const auto par_row = [&](const T* __restrict__ rows, const int k, const int bit) -> V {
         if constexpr (UNI) {
@@ -110,6 +115,7 @@ __device__ __forceinline__ void step_body(
         // scale, q last — so that gas 0 can start when ITS rows have landed, behind a partial vmcnt wait, with the later rows in flight.
 #pragma unroll
         for (int k = 0; k < 2; ++k) Sv[k] = load_row<V, NT>(S + k * ld + mm);
+        if constexpr (MFORC) mf = load_row<V, NT>(mforc + (int64_t)t * ld + mm);
         if constexpr (FORC) {
 #pragma unroll
             for (int k = L::G; k < L::G + MAX_FEXT; ++k) fs[k] = k < L::G + n_fext ? load_row<V, NT>(fscale + k * ld + mm) : (V)T(0);
@@ -137,6 +143,7 @@ __device__ __forceinline__ void step_body(
 #pragma unroll
             for (int k = 0; k < L::G + MAX_FEXT; ++k) fs[k] = k < L::G + n_fext ? load_row<V, NT>(fscale + k * ld + mm) : (V)T(0);
         }
+        if constexpr (MFORC) mf = load_row<V, NT>(mforc + (int64_t)t * ld + mm);
     }
 
     if (threadIdx.x < NW) reinterpret_cast<T*>(&km_s)[threadIdx.x] = stage_v;
@@ -160,7 +167,13 @@ __device__ __forceinline__ void step_body(
     };
     V Tn = (V)T(0);
     V no_cum[L::G], no_Rlo[L::SP];                // never touched: INV = COMP = false
-    if constexpr (SPREAD)
+    if constexpr (MFORC && SPREAD)
+        member_step<V, L, false, false, true, decltype(store_gas), 0, true>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, 1,
+                                                                            fext + (int64_t)t * MAX_FEXT, n_fext, store_gas, mf);
+    else if constexpr (MFORC)
+        member_step<V, L, false, false, true, NoGasHook, 0, true>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, 1,
+                                                                  fext + (int64_t)t * MAX_FEXT, n_fext, NoGasHook{}, mf);
+    else if constexpr (SPREAD)
         member_step<V, L, false, false, FORC>(kmr, drv, rr, qq, Rv, Sv, Cv, Tn, no_cum, no_Rlo, fs, 1,
                                               FORC ? fext + (int64_t)t * MAX_FEXT : nullptr, n_fext, store_gas);
     else
@@ -215,6 +228,27 @@ __global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_kerne
     step_body<V, P0, P1, P2, BINS, NT, MISFIT, FORC, false>(drive, n_steps, t, n, ld, r, q, R, S, C_traj, T_traj, n_rows, stats,
                                                             bin_ring, ring_rows, hist_lo, hist_inv_w, n_bins, obs, misfit, fscale,
                                                             fext, n_fext, UniformRows<typename Lane<V>::S>{});
+}
+
+// Kernel 1m — step_kernel<V, P0, P1, P2, false, false, MISFIT, true> WITH a per-member forcing row per step (MFORC above;
+// fiveeq_run_mforc_*, include/fiveeq.h "MEMBER FORCING").  A kernel of its own name: every instantiation of step_kernel keeps
+// its symbol and its machine code.  The {4} and 4 + 1 + 1 layouts, with and without the misfit, default row policy.
+template <typename V, int P0, int P1, int P2, bool MISFIT = false>
+__global__ __launch_bounds__(FIVEEQ_STEP_BLOCK) FIVEEQ_STEP_ATTR void step_mforc_kernel(
+    const KModel<typename Lane<V>::S> km, const typename Lane<V>::S* __restrict__ drive, const int n_steps, const int t,
+    const int64_t n, const int64_t ld,
+    const typename Lane<V>::S* __restrict__ r, const typename Lane<V>::S* __restrict__ q,
+    typename Lane<V>::S* __restrict__ R, typename Lane<V>::S* __restrict__ S,
+    typename Lane<V>::S* __restrict__ C_traj /* [n_rows][G][ld] or nullptr */,
+    typename Lane<V>::S* __restrict__ T_traj /* [n_rows][ld] or nullptr */,
+    const int n_rows, double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */,
+    const double* __restrict__ obs /* MISFIT: [n_steps][4] */, double* __restrict__ misfit /* MISFIT: [3][ld] */,
+    const typename Lane<V>::S* __restrict__ fscale /* [G + n_fext][ld] */,
+    const typename Lane<V>::S* __restrict__ fext /* [n_steps][MAX_FEXT] */, const int n_fext,
+    const typename Lane<V>::S* __restrict__ mforc /* [n_steps][ld] */) {
+    step_body<V, P0, P1, P2, false, false, MISFIT, true, false, true>(drive, n_steps, t, n, ld, r, q, R, S, C_traj, T_traj, n_rows,
+                                                                      stats, nullptr, 0, 0.0, 0.0, 0, obs, misfit, fscale, fext,
+                                                                      n_fext, UniformRows<typename Lane<V>::S>{}, mforc);
 }
 
 // Kernel 1u — step_kernel<V, P0, P1, P2, false, NT> WITHOUT the loads of the parameter rows the caller declared single-valued

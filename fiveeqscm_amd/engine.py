@@ -119,7 +119,7 @@ class EnsembleEngine(CheckpointMixin):
                  collect_stats=False, hist=None, hist_ring_steps="auto", concentration_driven=False,
                  chunk_members="auto", per_step_streams="auto", fused_span="auto", small_lanes="auto", compensated=False,
                  R0=None, S0=None, lib_path=None, observations=None, scenario_names=None, forcing=None,
-                 uniform_rows="auto"):
+                 uniform_rows="auto", member_forcing=None):
         """store_trajectory / output_steps: True stores C, T of every step; a list of step indices
         stores only those (rows in increasing step order, see `out_steps`); False stores nothing.
         store_concentrations=False keeps only the T rows (a 100M-member fp32 run then stores 4 B instead
@@ -195,7 +195,15 @@ class EnsembleEngine(CheckpointMixin):
         `r` and `q` are READ-ONLY after construction: nothing in the package writes into them (checkpoints restore state
         only, resampled() builds a new engine); a caller who overwrites them anyway calls refresh_uniform_rows() afterwards.
         False keeps every load.  Pool layouts without the form ({4} and 4 + 1 + 1 have it) and the other families (scenario
-        axis, observations=, forcing=, hist=) report the rows and run as before."""
+        axis, observations=, forcing=, hist=) report the rows and run as before.
+        member_forcing: a tensor [n_steps, N] on the engine's device and in its dtype — a forcing series of each member's OWN
+        that changes every step (include/fiveeq.h "MEMBER FORCING"): internal variability (forcing.ar1_noise_rows), or a
+        member's own aerosol or volcanic history.  Step t of member m opens its forcing F = F_ext[t] + member_forcing[t, m]
+        (one add), then the category and gas terms of forcing= as above.  Alone (unit scales, no category) or with forcing=
+        and / or observations=; modes 'per_step', 'graph', 'fused', 'ksteps' and 'auto' (never 'small'), the same bits in each;
+        all-zero rows are the forcing= run bit for bit.  The rows are kept as given (not copied when contiguous), are read-only
+        to the engine, and take n_steps N w bytes; a checkpoint names them by sha256.  Pool layouts {4} and 4 + 1 + 1; not with
+        the scenario axis, compensated=True, hist= or concentration_driven=True."""
         if dtype not in _DTYPES:
             raise ValueError("dtype must be torch.float64 or torch.float32")
         self.lib = _capi.load(lib_path)    # raises if the HIP library is not built
@@ -356,7 +364,25 @@ class EnsembleEngine(CheckpointMixin):
                     raise ValueError("f_scale / fx_scale: non-finite scale factors")
             elif "f_scale" in params or "fx_scale" in params:
                 raise ValueError("f_scale / fx_scale need forcing= (ExternalForcings; a table without categories will do)")
-        n_frows = 0 if self.fscale is None else int(self.fscale.shape[0])
+            self.member_forcing, self._unit_fscale = None, None
+            if member_forcing is not None:
+                for flag, why in ((self.scenario_axis, "emissions of several scenarios (the scenario axis)"),
+                                  (self.compensated, "compensated=True"), (hist is not None, "hist="),
+                                  (self.concentration_driven, "concentration_driven=True")):
+                    if flag:
+                        raise ValueError(f"member_forcing= cannot be combined with {why}: the per-member forcing rows are "
+                                         "carried by the plain forward forms (with or without forcing= and observations=) only")
+                if not self.lib.fiveeq_forcing_layout_supported(G, n_pools):
+                    raise ValueError(f"member_forcing=: pool layout {self.pools} has no member-forcing form (pools [4] and "
+                                     "[4, 1, 1] have)")
+                mf = member_forcing
+                if (not isinstance(mf, torch.Tensor) or tuple(mf.shape) != (self.n_steps, N) or mf.dtype != dt_
+                        or mf.device != dev):
+                    raise ValueError(f"member_forcing: want a tensor of shape [{self.n_steps}, {N}] ({dt_}) on {dev}")
+                self.member_forcing = mf.contiguous()
+                if self.fscale is None:                          # without forcing=: unit gas scales, no category
+                    self._unit_fscale = torch.ones((G, N), dtype=dt_, device=dev)
+        n_frows = self._n_scale_rows()
         if chunk_members == "auto":
             chunk_members = self.auto_chunk(N, SP, G, dtype, n_scenarios=Sc, extra_rows=n_frows)
         self.chunk_members = int(chunk_members or 0) // 256 * 256
@@ -386,6 +412,15 @@ class EnsembleEngine(CheckpointMixin):
         self.refresh_uniform_rows()
         with torch.cuda.device(self.device):
             self.probe_streams()            # construction is synchronous anyway: the one place the probe may clock streams
+
+    def _scale_rows(self):
+        """The scale rows the forcing kernels load: `fscale` of forcing=, or the unit rows of a member_forcing= engine without
+        it; None for an engine with neither."""
+        return self.fscale if self.fscale is not None else self._unit_fscale
+
+    def _n_scale_rows(self):
+        rows = self._scale_rows()
+        return 0 if rows is None else int(rows.shape[0])
 
     def refresh_uniform_rows(self):
         """Scan `r` and `q` again for single-valued rows (fiveeq_uniform_rows_*: one device pass, synchronous) — for a caller
@@ -484,6 +519,9 @@ class EnsembleEngine(CheckpointMixin):
              "mode 'small' does not carry the forcing scales of forcing=: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'"),
             (self.observations is not None, forward,
              "mode 'small' does not carry the misfit of observations=: use 'per_step', 'graph', 'fused', 'ksteps' or 'auto'"),
+            (self.member_forcing is not None, forward,
+             "mode 'small' does not carry the per-member forcing rows of member_forcing=: use 'per_step', 'graph', 'fused', "
+             "'ksteps' or 'auto'"),
         )
         return next((text for has, modes, text in rules if has and mode not in modes), None)
 
@@ -592,24 +630,30 @@ class EnsembleEngine(CheckpointMixin):
     def _forward_calls(self):
         """The C calls of this engine's forward run, with the arguments of its feature bound: n_scen (the scenario axis, whose
         strides derive from ld = N), (obs, misfit) (observations=), (fscale, fext, n_fext) (forcing=, after n_scen's or before
-        the misfit's) or none.  Returns
+        the misfit's), (mforc, n_mforc_rows) (member_forcing=, behind the misfit's: fiveeq_run_mforc, which takes fiveeq_run_forc's
+        arguments first — unit scale rows and no category without forcing=) or none.  Returns
           per_step(t_begin, t_end, m0, n, stream)  one launch per step for members [m0, m0 + n);
           fused(t_begin, t_end, k, stream)         the fused kernel over spans of k steps, all members;
           plan(t_begin, t_end, m0, n, plan_out)    the per-step launches of members [m0, m0 + n) captured into a plan."""
-        scen, forc, obs = self.scenario_axis, self.forcing is not None, self.observations is not None
+        scen, obs, mforc = self.scenario_axis, self.observations is not None, self.member_forcing is not None
+        forc = self.forcing is not None or mforc
 
         def args(t_begin, t_end, m0=0, n=None):
             a = self._run_args(t_begin, t_end, m0, n, n_scen=self.n_scenarios if scen else None)
             if forc:                                            # with scenarios: the scale rows shared, the tables [S, n_steps, 4]
-                a += (self._ptr(self.fscale, m0 * self._w), self._ptr(self.fext), self.forcing.n_categories)
+                a += (self._ptr(self._scale_rows(), m0 * self._w), self._ptr(self.fext),
+                      0 if self.forcing is None else self.forcing.n_categories)
             if obs:
                 a += self._obs_args(m0)
             elif forc and not scen:                             # fiveeq_run_forc's (obs, misfit): both NULL without observations=
                 a += (None, None)
+            if mforc:
+                a += (self._ptr(self.member_forcing, m0 * self._w), self.n_steps)
             return a
 
         if scen or forc or obs:
-            sfx = "_".join(word for word, on in (("scen", scen), ("forc", forc), ("obs", obs and not forc)) if on)
+            sfx = "mforc" if mforc else "_".join(
+                word for word, on in (("scen", scen), ("forc", forc), ("obs", obs and not forc)) if on)
             run, plan = self._fn("run_" + sfx), self._fn("plan_create_" + sfx)
 
             def per_step(t, t1, m0, n, s):
@@ -1117,6 +1161,9 @@ class EnsembleEngine(CheckpointMixin):
             raise ValueError("forcing_rows: a concentration-driven engine stores the diagnosed EMISSIONS in its C rows, not "
                              "concentrations; the forcing of its target concentrations is not diagnosed here")
         self._need_stored_C("forcing_rows", "; the stored C rows cannot reproduce that F", "F is recomputed from the stored C rows")
+        if self.member_forcing is not None:
+            raise ValueError("forcing_rows: the pass recomputes F from the shared tables and the scale rows; the per-member rows "
+                             "of member_forcing= are not part of it")
         sel = _stored_rows_slice(rows)
         steps = self.out_steps[sel]
         if replay and (steps.size == 0 or steps[0] != 0 or np.any(np.diff(steps) != 1)):
@@ -1215,7 +1262,10 @@ class EnsembleEngine(CheckpointMixin):
         forcing=) replaced by gathers of the engine's own device rows, in its dtype; R0 / S0 are gathers of the state R / S
         as it stands (the scenario axis is kept: [S, SP, M] / [S, 2, M]).  One fiveeq_gather_rows_* launch each.
         plan.n_members differs per rank and can be 0 — an engine needs at least one member.  Concentration-driven engines are
-        refused: their cumulative emissions (cumE) are per-member state that would have to travel too."""
+        refused: their cumulative emissions (cumE) are per-member state that would have to travel too.
+        An engine with member_forcing= returns a FOURTH item: the drawn members' columns of its rows, [n_steps, M], for the new
+        engine's member_forcing= — the continued run then reads, for its member k, the series of this engine's member
+        plan.src[k]."""
         if self.concentration_driven:
             raise ValueError("resampled: a concentration-driven engine carries cumE, which the resampled triple does not hold")
         if not isinstance(plan.src, torch.Tensor) or plan.src.device != self.device or plan.n_source != self.n_members:
@@ -1232,6 +1282,8 @@ class EnsembleEngine(CheckpointMixin):
                 params["f_scale"] = fs[:G]
                 if fs.shape[0] > G:
                     params["fx_scale"] = fs[G:]
+            if self.member_forcing is not None:
+                return params, plan.gather(self.R), plan.gather(self.S), plan.gather(self.member_forcing)
             return params, plan.gather(self.R), plan.gather(self.S)
 
     def T_histogram(self, lo, hi, n_bins=4096, rows=None, out=None, stream=None, scenario=None):
@@ -1271,6 +1323,14 @@ class EnsembleEngine(CheckpointMixin):
         import hashlib                                           # (not cached: `fscale` is the caller's to edit between runs)
         return hashlib.sha256(self.fscale.double().cpu().numpy().tobytes()).hexdigest()
 
+    def member_forcing_sha256(self):
+        """sha256 (hex) of the member_forcing rows as fp64 host bytes, [n_steps, N] (None without member_forcing=): what a
+        checkpoint names the engine's per-member forcing series by."""
+        if self.member_forcing is None:
+            return None
+        import hashlib                                           # (not cached, like fscale_sha256)
+        return hashlib.sha256(self.member_forcing.double().cpu().numpy().tobytes()).hexdigest()
+
     # -- accounting ----------------------------------------------------------------------
     def bytes_per_member_step(self, mode="per_step", k_steps=None):
         """ALGORITHMIC HBM bytes per member-timestep — every parameter row counted as loaded: a plain
@@ -1289,10 +1349,15 @@ class EnsembleEngine(CheckpointMixin):
         scenarios, w (2 SP + 4 + (G + 1) stored) + w (3G + 2) / S (with `forcing=`: w (3G + 2 + G + K) / S, the scale rows
         too are read once per member).
         With `forcing=` the G + K scale rows are parameter rows like r and q: per_step w (G + K) more per member-step, the
-        fused forms w (G + K) more per member and launch."""
+        fused forms w (G + K) more per member and launch.
+        With `member_forcing=` the member's row element is read at EVERY step in every form — the rows are streamed, not
+        resident: w more per member-step for per_step and the fused forms alike (and, without forcing=, the G unit scale rows
+        count like forcing='s)."""
         w, G, SP = self._w, self.n_gas, self.sum_pools
-        fr = 0 if self.fscale is None else int(self.fscale.shape[0])
+        fr = self._n_scale_rows()
         out = ((G if self.C is not None else 0) + 1) * self.n_rows / self.n_steps      # stored rows only
+        if self.member_forcing is not None:
+            out += 1                                             # one row element per member-step, like a stored row
         extra = (32.0 / 64.0) if self.collect_stats else 0.0
         ring = 4.0 if (self.T_hist is not None and mode in ("fused", "per_step")) else 0.0
         if self.observations is not None:

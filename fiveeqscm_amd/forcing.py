@@ -166,3 +166,114 @@ class ScenarioForcings:
         if not paths:
             raise ValueError("from_csvs: no scenario files")
         return cls([ExternalForcings.from_csv(p, names, run_years) for p in paths])
+
+
+# ------------------------------------------------------------------------------------
+# Per-member AR(1) internal variability: rows [n_steps, N] for EnsembleEngine(member_forcing=...).  xi_t = phi xi_{t-1} + s z_t
+# with s = sigma sqrt(1 - phi^2) and z_t(M) a counter-based deviate that is a pure function of (seed, M, t), computed in
+# integer arithmetic (include/fiveeq.h, "AR(1) NOISE ROWS"; csrc/fiveeq_noise.hpp): a rank computes exactly its shard — on its
+# GPU through fiveeq_noise_rows_*, or on the host with the NumPy twin below, bit for bit the same numbers — and the rows do
+# not depend on the world size or on how the steps are cut into calls.
+# ------------------------------------------------------------------------------------
+NOISE_SEED = 20261020
+
+
+def _noise_deviates(seed, members, steps):
+    """z [len(steps), len(members)] fp64: the deviate of member M at counter t (t >= -1), the key construction of
+    csrc/fiveeq_noise.hpp (noise_member_key, noise_key, noise_deviate) in wrapping uint64 arithmetic."""
+    from .params import _mix64
+    M = np.asarray(members, dtype=np.uint64).reshape(1, -1)
+    t = np.asarray(steps, dtype=np.int64).reshape(-1, 1)
+    if t.size and t.min() < -1:
+        raise ValueError("noise deviates: counters start at t = -1")
+    with np.errstate(over="ignore"):
+        mk = _mix64(np.uint64(seed) + np.uint64(0x9E3779B97F4A7C15) * (M + np.uint64(1)))
+        total = np.zeros((t.shape[0], M.shape[1]), dtype=np.uint64)
+        for j in range(6):
+            counter = (t + 1).astype(np.uint64) * np.uint64(6) + np.uint64(j + 1)
+            word = _mix64(mk ^ (np.uint64(0xD1342543DE82EF95) * counter))
+            total += (word >> np.uint64(32)) + (word & np.uint64(0xFFFFFFFF))
+    return (total.astype(np.int64) - np.int64(6 * 0xFFFFFFFF)).astype(np.float64) * 2.0 ** -32
+
+
+def ar1_noise_steps_host(seed, members, t_begin, t_end, phi, s, xi_state, dtype=np.float64):
+    """The twin of ONE fiveeq_noise_rows_* call: steps [t_begin, t_end) of `members` (global indices) from xi_state (fp64, not
+    modified).  phi and s are taken in `dtype` (the kernel precision) and widened.  Returns (rows [t_end - t_begin, n] in
+    dtype, xi_state after); [-1, 0) is the start call, which returns no rows."""
+    members = np.asarray(members)
+    ph = np.asarray(phi, dtype=dtype).astype(np.float64)
+    sm = np.asarray(s, dtype=dtype).astype(np.float64)
+    xi = np.array(xi_state, dtype=np.float64, copy=True)
+    start = t_begin == -1
+    if t_begin < -1 or t_end < t_begin or (start and t_end != 0):
+        raise ValueError(f"step range [{t_begin},{t_end}): want 0 <= t_begin <= t_end, or [-1,0) for the stationary start")
+    z = _noise_deviates(seed, members, np.arange(t_begin, t_end))
+    rows = np.empty((0 if start else t_end - t_begin, members.size), dtype=dtype)
+    for i in range(t_end - t_begin):
+        w = sm * z[i]
+        xi = ph * xi + w
+        if not start:
+            rows[i] = xi.astype(dtype)
+    return rows, xi
+
+
+def _member_rows(x, n_total, lo, hi, name):
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 0:
+        return np.full(hi - lo, float(x))
+    if x.shape == (n_total,):
+        return x[lo:hi].copy()
+    if x.shape == (hi - lo,):
+        return x.copy()
+    raise ValueError(f"{name}: a scalar, or a row of the {n_total} members of the design or of the {hi - lo} of the shard")
+
+
+def _ar1_setup(n_total, n_steps, sigma, phi, lo, hi):
+    hi = n_total if hi is None else hi
+    if not 0 <= lo <= hi <= n_total:
+        raise ValueError(f"members [{lo}, {hi}) outside [0, {n_total})")
+    if n_steps < 0:
+        raise ValueError(f"n_steps={n_steps} must be >= 0")
+    sg, ph = _member_rows(sigma, n_total, lo, hi, "sigma"), _member_rows(phi, n_total, lo, hi, "phi")
+    if not (np.isfinite(sg).all() and (sg >= 0).all()):
+        raise ValueError("sigma: want finite values >= 0")
+    if not (np.abs(ph) < 1).all():
+        raise ValueError("phi: want |phi| < 1 (a stationary AR(1) process)")
+    return hi, sg, ph, sg * np.sqrt(1.0 - ph * ph)           # s = sigma sqrt(1 - phi^2), in fp64 on the host
+
+
+def ar1_noise_rows_host(n_total, n_steps, sigma, phi, lo=0, hi=None, seed=NOISE_SEED, dtype=np.float64):
+    """[n_steps, hi - lo]: the rows of ar1_noise_rows computed on the host with NumPy, bit for bit (dtype np.float64 or
+    np.float32)."""
+    hi, sg, ph, s = _ar1_setup(n_total, n_steps, sigma, phi, lo, hi)
+    members = np.arange(lo, hi)
+    _, xi = ar1_noise_steps_host(seed, members, -1, 0, ph, sg, np.zeros(hi - lo), dtype)     # xi_{-1} = sigma z_{-1}
+    return ar1_noise_steps_host(seed, members, 0, n_steps, ph, s, xi, dtype)[0]
+
+
+def ar1_noise_rows(n_total, n_steps, sigma, phi, lo=0, hi=None, seed=NOISE_SEED, device=None, dtype=None):
+    """[n_steps, hi - lo] on `device`: per-member AR(1) noise for members [lo, hi) of an n_total-member ensemble, stationary
+    with standard deviation sigma and lag-1 autocorrelation phi (scalars, or per-member rows over the design or the shard;
+    W m-2 when the rows go into EnsembleEngine(member_forcing=...)).  The start is the draw at counter t = -1 times sigma.
+    One HIP pass (fiveeq_noise_rows_*), two calls: the start, then the steps.  dtype: torch.float64 (default) or
+    torch.float32 — the recursion runs in fp64 either way and fp32 rows are rounded once.  Memory: n_steps (hi - lo) w bytes."""
+    import torch
+
+    from ._rowargs import call, ptr
+    dtype = torch.float64 if dtype is None else dtype
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError("dtype must be torch.float64 or torch.float32")
+    hi, sg, ph, s = _ar1_setup(n_total, n_steps, sigma, phi, lo, hi)
+    dev = torch.device("cuda" if device is None else device)
+    n = hi - lo
+    rows = torch.empty((n_steps, n), dtype=dtype, device=dev)
+    if n == 0 or n_steps == 0:
+        return rows
+    up = lambda a: torch.from_numpy(a).to(dev, dtype)                               # noqa: E731
+    ph_d, s_d, sg_d = up(ph), up(s), up(sg)
+    xi = torch.zeros(n, dtype=torch.float64, device=dev)
+    lib = _capi.load()
+    call(lib, _capi, "fiveeq_noise_rows", dtype, dev, int(seed), int(lo), n, n, -1, 0, ptr(ph_d), ptr(sg_d), ptr(xi), None)
+    call(lib, _capi, "fiveeq_noise_rows", dtype, dev, int(seed), int(lo), n, n, 0, int(n_steps), ptr(ph_d), ptr(s_d), ptr(xi),
+         ptr(rows))
+    return rows

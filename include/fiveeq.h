@@ -336,6 +336,76 @@ int fiveeq_plan_create_forc_f32(const fiveeq_model *model, int64_t n_members, in
                                 float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
                                 const float *fscale, const float *fext, int32_t n_fext,
                                 const double *obs, double *misfit, void **plan_out);
+/* MEMBER FORCING — a per-member forcing series that changes every step (new; ADDITIVE: FIVEEQ_ABI_VERSION stays 13, no existing
+ * prototype or struct changes, sizeof(fiveeq_model) stays 448).  What carries internal variability (fiveeq_noise_rows_* below)
+ * or a member's own aerosol or volcanic history.  The arguments of fiveeq_run_forc_* up to misfit, then
+ *   mforc        dev [n_mforc_rows][ld]   kernel precision: the forcing member m adds during step t at [t][m]; row t is read
+ *                                         by step t, so rows [t_begin, t_end) are read by a call
+ *   n_mforc_rows                          rows of mforc, >= t_end
+ * then form, k_steps, stream (or plan_out).  Step t of member m opens its forcing with ONE add,
+ *     F = drive[t][6] + mforc[t][m]
+ * and goes on with the category fmas and the gas fmas exactly as FORCING SCALES above; nothing else of the step differs.
+ * All-zero rows give fiveeq_run_forc_* bit for bit (no drive[t][6] being -0); rows uniform over the members, x_t, give
+ * fiveeq_run_forc_* on a drive table with F_ext'[t] = fl(drive[t][6] + x_t) formed in kernel precision.  fscale is required
+ * as there; unit scale rows with n_fext == 0 (fext NULL) run the rows alone.
+ *   form FIVEEQ_FORM_PER_STEP: the row is one more coalesced row load issued with the lane's other rows, w bytes more per
+ *       member-step;
+ *   form FIVEEQ_FORM_FUSED: the lane loads its element of row t + 1 while it computes step t; w bytes per member-step here too
+ *       (the row is streamed, not resident).
+ * Packed fp32 lanes load their two members as one 8-byte access (mforc 8-byte aligned and ld even, else the scalar kernels:
+ * the same bits).  Every form gives the same bits.  Pool layouts {4} and 4 + 1 + 1, with and without obs / misfit; not under
+ * the scenario axis, nor in the small-ensemble, compensated, histogram-ring or concentration-driven forms.  FIVEEQ_E_INVALID
+ * for everything fiveeq_run_forc_* refuses, a NULL or misaligned mforc and n_mforc_rows < t_end — before anything is launched. */
+int fiveeq_run_mforc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                         const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                         const double *r, const double *q, double *R, double *S,
+                         double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                         const double *fscale, const double *fext, int32_t n_fext,
+                         const double *obs, double *misfit, const double *mforc, int32_t n_mforc_rows,
+                         int32_t form, int32_t k_steps, void *stream);
+int fiveeq_run_mforc_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                         const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                         const float *r, const float *q, float *R, float *S,
+                         float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                         const float *fscale, const float *fext, int32_t n_fext,
+                         const double *obs, double *misfit, const float *mforc, int32_t n_mforc_rows,
+                         int32_t form, int32_t k_steps, void *stream);
+/* fiveeq_plan_create_* of the per-step form above; the plan bakes in fscale, fext, obs, misfit and mforc too */
+int fiveeq_plan_create_mforc_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                 const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                 const double *r, const double *q, double *R, double *S,
+                                 double *C_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                                 const double *fscale, const double *fext, int32_t n_fext,
+                                 const double *obs, double *misfit, const double *mforc, int32_t n_mforc_rows,
+                                 void **plan_out);
+int fiveeq_plan_create_mforc_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                                 const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                                 const float *r, const float *q, float *R, float *S,
+                                 float *C_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                                 const float *fscale, const float *fext, int32_t n_fext,
+                                 const double *obs, double *misfit, const float *mforc, int32_t n_mforc_rows,
+                                 void **plan_out);
+/* AR(1) NOISE ROWS — shard-computable per-member internal variability (new; additive): rows[t - t_begin][m] = xi_t of member
+ * M = m0 + m for t_begin <= t < t_end, 0 <= m < n_members,
+ *     xi_t = phi_m xi_{t-1} + s_m z_t(M)
+ * with z_t(M) a counter-based deviate computed in INTEGER arithmetic from (seed, M, t) alone: six splitmix64 words
+ * mix64(mix64(seed + 0x9e3779b97f4a7c15 (M + 1)) ^ 0xd1342543de82ef95 (6 (t + 1) + j + 1)), j = 0..5, their twelve 32-bit halves
+ * summed (< 2^36, exact), z = (sum - 6 (2^32 - 1)) 2^-32 converted to fp64 exactly: |z| <= 6, mean 0, variance 1 - 2^-64,
+ * excess kurtosis -0.1.  The recursion runs in fp64, w = s_m z_t then xi_t = phi_m xi_{t-1} + w, each operation rounded on its
+ * own (no fma).  The bits depend on (seed, M, t, phi_m, s_m) only: not on the launch shape, ld, the m0 split, or how the steps
+ * are cut into calls.  Layouts:
+ *   phi, s    dev [ld]   kernel precision (widened exactly); s = sigma sqrt(1 - phi^2) gives a stationary standard deviation sigma
+ *   xi_state  dev [ld]   fp64, in/out: xi_{t_begin - 1} in, xi_{t_end - 1} out
+ *   rows      dev [t_end - t_begin][ld]   kernel precision; _f32 rounds xi_t once on store and keeps the fp64 xi_state
+ * THE STATIONARY START is the draw at counter t = -1 times sigma_m: the call with [t_begin, t_end) = [-1, 0) runs that one
+ * step through the same recursion and stores no row (rows may be NULL); with xi_state zeroed and s = sigma it leaves
+ * xi_state = sigma_m z_{-1}(M).  Columns [n_members, ld) of rows and xi_state are not touched.  FIVEEQ_E_INVALID for
+ * n_members outside 1..2^31-1, n_members > ld, m0 < 0, a range that is neither 0 <= t_begin <= t_end nor [-1, 0), NULL or
+ * misaligned pointers — before anything is launched.  Host twin (bit-identical): fiveeqscm_amd.forcing.ar1_noise_rows_host. */
+int fiveeq_noise_rows_f64(uint64_t seed, int64_t m0, int64_t n_members, int64_t ld, int32_t t_begin, int32_t t_end,
+                          const double *phi, const double *s, double *xi_state, double *rows, void *stream);
+int fiveeq_noise_rows_f32(uint64_t seed, int64_t m0, int64_t n_members, int64_t ld, int32_t t_begin, int32_t t_end,
+                          const float *phi, const float *s, double *xi_state, float *rows, void *stream);
 /* FORCING SCALES UNDER THE SCENARIO AXIS (new; additive, FIVEEQ_ABI_VERSION stays 13): fiveeq_run_scen_* / fiveeq_plan_create_scen_*
  * with the forcing scales of fiveeq_run_forc_*.  The arguments of the scenario calls, then
  *   fscale dev [G + n_fext][ld]          SHARED by the scenarios, like r and q
