@@ -5,7 +5,7 @@ The record is the synthetic one committed for the tests (tests/golden/obs_synthe
 tests/golden/make_obs_synthetic.py: one known member plus 0.1 K noise over 1900..2069).  Needs an MI355X.
 
     python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing] [--co2-record] [--concentration-driven]
-                                           [--variability SIGMA PHI]
+                                           [--co2-emission-driven] [--variability SIGMA PHI]
 
 --forcing adds forcing uncertainty (EnsembleEngine(forcing=), fiveeqscm_amd/forcing.py): an aerosol-like cooling scaled per
 member, and the accepted range of ECS with a shared and with a sampled scale.
@@ -15,6 +15,11 @@ carbon-cycle parameter r0 of CO2 with and without the CO2 record.
 --concentration-driven runs the calibration the other way round (ConcentrationDrivenEngine): the history 1750..2019 is driven by
 "observed" concentrations, every member carries its own aerosol scale and is scored against the warming record in-loop; the
 weighted ensemble then branches into an emission-driven projection to 2499 through R0 / S0.
+--co2-emission-driven (with --concentration-driven) keeps CO2 emission-driven in that history (MixedDriveEngine with
+concentration_gases=(1, 2)): CH4 and N2O still follow the "observed" concentrations, CO2 takes the scenario's emissions, so each
+member's carbon-cycle parameters show in its CO2 concentration and through it in the warming it is scored on, instead of only
+in diagnosed CO2 emissions; the spread of CO2 at the cut is printed, and the projection continues the scenario's own
+cumulative CO2 emissions (the mean diagnosed cumE is used for CH4 and N2O only).
 --variability SIGMA PHI gives every member its own AR(1) forcing noise (standard deviation SIGMA W m-2, lag-1 autocorrelation
 PHI; forcing.ar1_noise_rows, EnsembleEngine(member_forcing=)), constrains with the in-loop misfit and prints the accepted
 fraction and the 5-95 % range of the final T with and without the variability.
@@ -43,6 +48,8 @@ def main():
                     help="also score the stored CO2 rows against a synthetic CO2 record and print what it does to r0 of CO2")
     ap.add_argument("--concentration-driven", action="store_true",
                     help="also constrain a concentration-driven history with an aerosol scale per member and branch into a projection")
+    ap.add_argument("--co2-emission-driven", action="store_true",
+                    help="with --concentration-driven: keep CO2 emission-driven in the history (CH4 and N2O prescribed)")
     ap.add_argument("--variability", nargs=2, type=float, metavar=("SIGMA", "PHI"),
                     help="also give every member AR(1) forcing noise (W m-2, lag-1 autocorrelation) and constrain with it")
     a = ap.parse_args()
@@ -71,8 +78,10 @@ def main():
         forcing_uncertainty(p, N, n_steps, dtype, obs)
     if a.co2_record:
         co2_record(p, N, n_steps, dtype, obs, run_years, years)
+    if a.co2_emission_driven and not a.concentration_driven:
+        ap.error("--co2-emission-driven is an option of --concentration-driven")
     if a.concentration_driven:
-        concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma)
+        concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma, co2_emission_driven=a.co2_emission_driven)
     if a.variability:
         internal_variability(p, N, n_steps, dtype, obs, run_years, *a.variability)
 
@@ -103,14 +112,15 @@ def co2_record(p, N, n_steps, dtype, obs, run_years, years, truth=12345, sigma_p
     eng.close()
 
 
-def concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma, cut=270):
+def concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma, cut=270, co2_emission_driven=False):
     """--concentration-driven: the concentrations of the default member's forward run stand in for the observed record up to
     2019 (step `cut`).  History: every member reaches exactly those concentrations (its own emissions are diagnosed), scales the
     aerosol-like cooling by its own factor and accumulates its misfit against the warming observed up to 2019.  Projection: a
     forward forcing= engine with the same scale rows starts from the history's pools and boxes (R0 / S0) at step `cut`; its
     drive table continues the cumulative emissions from the ensemble mean of the history's diagnosed cumE (the first `cut` rows
-    of its emissions hold that mean rate; they are not run)."""
-    from fiveeqscm_amd.engine import ConcentrationDrivenEngine
+    of its emissions hold that mean rate; they are not run).  co2_emission_driven: the history is a MixedDriveEngine with CH4 and
+    N2O prescribed and CO2 from the scenario's emissions, whose rows the projection keeps."""
+    from fiveeqscm_amd.engine import ConcentrationDrivenEngine, MixedDriveEngine
     from fiveeqscm_amd.forcing import ExternalForcings
     E = emissions.rcp_like_emissions(n_steps, 3)
     base = params.default_params("multigas")
@@ -124,8 +134,11 @@ def concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, 
     seen = years < run_years[cut]
     obs = constrain.Observations.from_years(run_years[:cut], years[seen], T_obs[seen], np.broadcast_to(sigma, years.shape)[seen],
                                             baseline=(1900, 1950))
-    hist = ConcentrationDrivenEngine(ps, N, conc, dtype=dtype, forcing=ExternalForcings(aerosol[:cut], ("aerosol",)),
-                                     observations=obs, store_trajectory=False, device="cuda:0")
+    kw = dict(dtype=dtype, forcing=ExternalForcings(aerosol[:cut], ("aerosol",)), observations=obs, device="cuda:0")
+    if co2_emission_driven:
+        hist = MixedDriveEngine(ps, N, E[:cut], conc, (1, 2), output_steps=[cut - 1], **kw)
+    else:
+        hist = ConcentrationDrivenEngine(ps, N, conc, store_trajectory=False, **kw)
     hist.run()
     chi2 = hist.chi2()
     w = constrain.importance_weights(chi2)
@@ -134,6 +147,11 @@ def concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, 
           f"effective sample size {ess:.0f} of {N}")
     E_proj = E.copy()
     E_proj[:cut] = hist.cumE.double().mean(1).cpu().numpy()[None, :] / cut          # the drive's cumulative emissions at the cut
+    if co2_emission_driven:
+        co2 = hist.X[0, 0].double()
+        print(f"  CO2 emission-driven: CO2({int(run_years[cut - 1])}) spans {float(co2.min()):.1f} .. {float(co2.max()):.1f} ppm over the "
+              f"members (prescribed: {conc[cut - 1, 0]:.1f})")
+        E_proj[:cut, 0] = E[:cut, 0]                                                # CO2 went by the scenario: its own cumulative sum
     last = n_steps - 1
     proj = EnsembleEngine(ps, N, E_proj, dtype=dtype, forcing=ExternalForcings(aerosol, ("aerosol",)), R0=hist.R, S0=hist.S,
                           output_steps=[last], store_concentrations=False, device="cuda:0")

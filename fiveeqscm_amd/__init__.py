@@ -5,13 +5,13 @@ hand-written HIP kernel per timestep on gfx950.  No CPU fallback for the engine.
 """
 from .concentrations import calculate_hfc_conc  # noqa: F401  (reference-compatible, NumPy)
 
-__all__ = ["calculate_hfc_conc", "ConcentrationDrivenEngine"]
+__all__ = ["calculate_hfc_conc", "ConcentrationDrivenEngine", "MixedDriveEngine"]
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
     # the engine classes need torch and the built HIP library: imported when first asked for, not with the package
-    if name in ("ConcentrationDrivenEngine", "EnsembleEngine"):
+    if name in ("ConcentrationDrivenEngine", "EnsembleEngine", "MixedDriveEngine"):
         from . import engine
         return getattr(engine, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -112,6 +112,7 @@ _RUNS = {
     "run_fused_bins": _run_args(_RING + _ST),
     "run_inverse": _run_args(_ST, cumE=True),
     "run_inverse_forc": _run_args(_FORC + _OBS + _ST, cumE=True),
+    "run_mixed": _run_args([_i32] + _FORC + _OBS + _ST, cumE=True),       # conc_mask behind T_stats
     "plan_create": _run_args(_PLAN),
     "run_obs": _run_args(_OBS + _FORM),
     "plan_create_obs": _run_args(_OBS + _PLAN),
@@ -153,6 +154,7 @@ SIGNATURES = {
     "fiveeq_misfit_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32)]),
     "fiveeq_max_scenarios": (_i32, []),
     "fiveeq_forcing_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32)]),
+    "fiveeq_mixed_layout_supported": (ctypes.c_int, [_i32, ctypes.POINTER(_i32), _i32]),
     "fiveeq_max_fext": (_i32, []),
     "fiveeq_small_lanes": (_i32, [_i32, ctypes.POINTER(_i32)]),
     "fiveeq_set_f32_packing": (ctypes.c_int, [ctypes.c_int]),

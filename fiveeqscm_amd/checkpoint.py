@@ -34,6 +34,8 @@ class CheckpointMixin:
             out["fscale_sha256"] = self.fscale_sha256()
         if getattr(self, "member_forcing", None) is not None:    # which per-member series the state was run under
             out["member_forcing_sha256"] = self.member_forcing_sha256()
+        if getattr(self, "conc_mask", None) is not None:         # a mixed-drive engine: which gases cumE and the rows belong to
+            out["conc_mask"] = int(self.conc_mask)
         if self.scenario_axis:                                   # which scenario set the per-scenario state belongs to
             out["n_scenarios"] = int(self.n_scenarios)
             out["drive_sha256"] = self.drive_sha256
@@ -82,6 +84,11 @@ class CheckpointMixin:
         theirs = (int(state["n_scenarios"]), state.get("drive_sha256")) if "n_scenarios" in state else None
         if theirs != mine:
             raise ValueError(f"checkpoint scenario set (n_scenarios, drive sha256) {theirs!r} is not this engine's {mine!r}")
+        mine = getattr(self, "conc_mask", None)
+        theirs = None if state.get("conc_mask") is None else int(state["conc_mask"])
+        if theirs != mine:
+            raise ValueError(f"checkpoint conc_mask {theirs!r} is not this engine's conc_mask {mine!r}: the cumulative emissions "
+                             "and the stored rows belong to other concentration-driven gases")
         if "T_stats" in state and self.collect_stats:
             self._wave_stats()                                   # the checkpoint carries wave records: make room for them (no state touched)
         staged = {}

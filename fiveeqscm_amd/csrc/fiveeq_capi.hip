@@ -282,6 +282,7 @@ struct RunArgs : BaseArgs<T> {
     bool scen = false;           // the call is of a scenario family (step_scen_kernel, fused_kernel<.., SCEN>), whatever n_scen
     int n_scen;                  // scenarios (the scenario forms; 1 without the scenario axis)
     T* cumE = nullptr;           // the inverse form's cumulative emissions
+    int conc_mask = 0;           // the mixed drive's per-gas mask (fiveeq_run_mixed: bit g set = gas g concentration-driven)
     BinRing br;                  // the histogram forms' ring (else none)
     MisfitRows mf;               // the constrained forms' accumulators (else none)
     ForcRows<T> fc;              // the forcing forms' scale rows and table (else none)
@@ -346,6 +347,8 @@ constexpr bool forcing_layout(int code) { return misfit_layout(code); }
 // the layouts with step_uniform_kernel instantiations: the same line again
 constexpr bool uniform_layout(int p0, int p1, int p2) { return misfit_layout(p0, p1, p2); }
 constexpr bool uniform_layout(int code) { return misfit_layout(code); }
+// the layouts with fused_mixed_kernel instantiations (a proper per-gas drive mask): 4 + 1 + 1
+constexpr bool mixed_layout(int code) { return code == 411; }
 
 // ---- the two launchers: one step of the per-step kernel, one span [t_begin, t_end) of the time-fused kernel ----------------
 // The compile-time flags pick the kernel family; packing, the row policy and the pool layout are decided here per launch.
@@ -588,6 +591,16 @@ int check_uniform(RunArgs<T>& a, uint32_t mask, const T* values) {
     return FIVEEQ_OK;
 }
 
+// the per-gas drive mask of fiveeq_run_mixed: bit g set = gas g is concentration-driven; no bit at or above the model's n_gas
+template <typename T>
+int check_conc_mask(RunArgs<T>& a, int32_t conc_mask) {
+    if (conc_mask < 0) return fail(FIVEEQ_E_INVALID, "conc_mask=%d must be >= 0", conc_mask);
+    if (conc_mask >> a.n_gas)
+        return fail(FIVEEQ_E_INVALID, "conc_mask=0x%x has bits at or above n_gas=%d", (unsigned)conc_mask, a.n_gas);
+    a.conc_mask = conc_mask;
+    return FIVEEQ_OK;
+}
+
 // the scenario axis: one parameter ensemble under n_scen emission scenarios (step_scen_kernel, fused_kernel<.., SCEN>)
 constexpr int MAX_SCENARIOS = 64;
 int check_scen(int32_t n_scen) {
@@ -625,12 +638,15 @@ struct Features {
     bool mforc = false;          // fiveeq_run_mforc / fiveeq_plan_create_mforc (a forcing family: forc is set too): the rows are the caller's
     const T* mforc_rows = nullptr;
     int32_t n_mforc_rows = 0;
+    bool mixed = false;          // fiveeq_run_mixed: conc_mask is the caller's (inv is set when it names a gas)
+    int32_t conc_mask = 0;
 };
 
 // Every check of a forward call but its last (the form of a run, the range of a plan), in the ONE order every family reports
 // in (tests/test_forward_precedence_cpu.py): the scenario count, [a plan: plan_out, cleared before anything else,] the base
 // arguments, the forcing rows, obs and misfit given together, the misfit rows; the single-valued rows of the plain family's
-// uniform twins come right behind the base arguments, and so does the cumE of fiveeq_run_inverse_forc.
+// uniform twins come right behind the base arguments, and so does the cumE of fiveeq_run_inverse_forc — with the drive mask of
+// fiveeq_run_mixed in front of it — and a proper mask on a layout without the mixed form (FIVEEQ_E_UNSUPPORTED) comes last.
 template <typename T>
 int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan = false, void** plan_out = nullptr) {
     if (plan_out) *plan_out = nullptr;
@@ -638,6 +654,7 @@ int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan
     if (plan && !plan_out) return fail(FIVEEQ_E_INVALID, "plan_out is NULL");
     if (int rc = make_args(a, b, f.n_scen)) return rc;
     a.scen = f.scen;
+    if (int rc = f.mixed ? check_conc_mask(a, f.conc_mask) : FIVEEQ_OK) return rc;
     if (f.inv) {
         if (!f.cumE) return fail(FIVEEQ_E_INVALID, "cumE is NULL");
         a.cumE = f.cumE;
@@ -648,7 +665,11 @@ int prepare(RunArgs<T>& a, const BaseArgs<T>& b, const Features<T>& f, bool plan
     if (f.misfit == OPTIONAL && (f.mf.obs == nullptr) != (f.mf.misfit == nullptr))
         return fail(FIVEEQ_E_INVALID, "obs and misfit go together: both NULL (no misfit) or both set (obs=%p misfit=%p)",
                     (const void*)f.mf.obs, (void*)f.mf.misfit);
-    if (f.misfit == REQUIRED || (f.misfit == OPTIONAL && f.mf.obs)) return check_misfit(a, f.mf.obs, f.mf.misfit);
+    if (f.misfit == REQUIRED || (f.misfit == OPTIONAL && f.mf.obs))
+        if (int rc = check_misfit(a, f.mf.obs, f.mf.misfit)) return rc;
+    if (f.mixed && a.conc_mask != 0 && a.conc_mask != (1 << a.n_gas) - 1 && !mixed_layout(a.code))
+        return fail(FIVEEQ_E_UNSUPPORTED, "pool layout %03d has no mixed-drive form for conc_mask=0x%x (pools 4+1+1 have)", a.code,
+                    (unsigned)a.conc_mask);
     return FIVEEQ_OK;
 }
 
@@ -706,6 +727,18 @@ int run_inverse(const BaseArgs<T>& b, T* cumE, void* stream) {        // (C_traj
     return each_span(a, 0, [&](int t0, int t1) { return launch_fused<T, true>(a, t0, t1, st); });
 }
 
+// the inverse kernel in the carrier prepare() found (plain, MISFIT, FORC, FORC + MISFIT): one launch for the span
+template <typename T>
+int run_inverse_span(const RunArgs<T>& a, hipStream_t st) {
+    const bool forc = a.fc.fscale != nullptr, misfit = a.mf.misfit != nullptr;
+    return each_span(a, 0, [&](int t0, int t1) {
+        if (forc)
+            return misfit ? launch_fused<T, true, false, false, true, false, true>(a, t0, t1, st)
+                          : launch_fused<T, true, false, false, false, false, true>(a, t0, t1, st);
+        return misfit ? launch_fused<T, true, false, false, true>(a, t0, t1, st) : launch_fused<T, true>(a, t0, t1, st);
+    });
+}
+
 // the concentration-driven form with the forcing scales and / or the misfit: fscale NULL = no scales (then n_fext must be 0: a
 // count without rows is check_forcing's "fscale is NULL"), obs and misfit both NULL = no misfit, all three NULL = the plain
 // inverse kernel.  Validated by prepare() in the order of the forward families, cumE right behind the base arguments; one
@@ -721,13 +754,57 @@ int run_inverse_forc(const BaseArgs<T>& b, T* cumE, const ForcRows<T>& fc, const
     f.inv = true;
     f.cumE = cumE;
     if (int rc = prepare(a, b, f)) return rc;
+    return run_inverse_span(a, (hipStream_t)stream);
+}
+
+// ---- the mixed drive: a per-gas mask of concentration-driven gases (fused_mixed_kernel) ---------------------------------------
+// one span of the mixed kernel of a.conc_mask (a proper mask, and a layout with the form: prepare() has seen to both)
+template <typename T, bool MISFIT, bool FORC>
+int launch_mixed(const RunArgs<T>& a, int t_begin, int t_end, hipStream_t st) {
+    unsigned blocks;
+    if (int rc = grid_blocks(a.n, FIVEEQ_BLOCK, blocks)) return rc;
+    const dim3 grid(blocks), block(FIVEEQ_BLOCK);
+    switch (a.conc_mask) {
+#define X(cm)                                                                                                                    \
+    case cm:                                                                                                                     \
+        hipLaunchKernelGGL((fused_mixed_kernel<T, 4, 1, 1, cm, MISFIT, FORC>), grid, block, FIVEEQ_FUSED_DYN_LDS, st, a.km, a.drive, \
+                           a.n_steps, t_begin, t_end, a.n, a.ld, a.r, a.q, a.R, a.S, a.cumE, a.C_traj, a.T_traj, a.n_rows, a.stats, \
+                           a.mf.obs, a.mf.misfit, a.fc.fscale, a.fc.fext, a.fc.n_fext);                                            \
+        break;
+        X(1) X(2) X(3) X(4) X(5) X(6)
+#undef X
+        default:
+            return fail(FIVEEQ_E_UNSUPPORTED, "conc_mask=0x%x has no mixed-drive kernel", (unsigned)a.conc_mask);
+    }
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+
+// fiveeq_run_mixed: validated by prepare() like fiveeq_run_inverse_forc, the mask in front of cumE; then by the mask
+//   0            the forward time-fused call on these arguments (fiveeq_run_fused, or fiveeq_run_forc / fiveeq_run_obs with
+//                FIVEEQ_FORM_FUSED and k_steps = 0: run_form), one launch for the range, cumE untouched;
+//   every gas    fiveeq_run_inverse_forc's launches;
+//   proper       the mixed kernel in the carrier (plain, FORC, MISFIT, FORC + MISFIT) those two pick among.
+template <typename T>
+int run_mixed(const BaseArgs<T>& b, T* cumE, int32_t conc_mask, const ForcRows<T>& fc, const MisfitRows& mf, void* stream) {
+    RunArgs<T> a;
+    Features<T> f;
+    f.forc = fc.fscale != nullptr || fc.n_fext != 0;
+    f.fc = fc;
+    f.misfit = OPTIONAL;
+    f.mf = mf;
+    f.mixed = true;
+    f.conc_mask = conc_mask;
+    f.inv = conc_mask != 0;
+    f.cumE = cumE;
+    if (int rc = prepare(a, b, f)) return rc;
     hipStream_t st = (hipStream_t)stream;
+    if (a.conc_mask == 0) return run_form(a, FIVEEQ_FORM_FUSED, 0, st);
     const bool forc = a.fc.fscale != nullptr, misfit = a.mf.misfit != nullptr;
+    if (a.conc_mask == (1 << a.n_gas) - 1) return run_inverse_span(a, st);
     return each_span(a, 0, [&](int t0, int t1) {
-        if (forc)
-            return misfit ? launch_fused<T, true, false, false, true, false, true>(a, t0, t1, st)
-                          : launch_fused<T, true, false, false, false, false, true>(a, t0, t1, st);
-        return misfit ? launch_fused<T, true, false, false, true>(a, t0, t1, st) : launch_fused<T, true>(a, t0, t1, st);
+        if (forc) return misfit ? launch_mixed<T, true, true>(a, t0, t1, st) : launch_mixed<T, false, true>(a, t0, t1, st);
+        return misfit ? launch_mixed<T, true, false>(a, t0, t1, st) : launch_mixed<T, false, false>(a, t0, t1, st);
     });
 }
 
@@ -1124,6 +1201,26 @@ int fiveeq_run_inverse_forc_f32(const fiveeq_model* model, int64_t n_members, in
                                 void* stream) {
     return run_inverse_forc<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, E_traj, T_traj, n_rows, T_stats},
                                    cumE, {fscale, fext, n_fext}, {obs, misfit}, stream);
+}
+
+int fiveeq_run_mixed_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive, int32_t n_steps,
+                         int32_t t_begin, int32_t t_end, const double* r, const double* q, double* R, double* S, double* cumE,
+                         double* X_traj, double* T_traj, int32_t n_rows, double* T_stats, int32_t conc_mask, const double* fscale,
+                         const double* fext, int32_t n_fext, const double* obs, double* misfit, void* stream) {
+    return run_mixed<double>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, X_traj, T_traj, n_rows, T_stats},
+                             cumE, conc_mask, {fscale, fext, n_fext}, {obs, misfit}, stream);
+}
+int fiveeq_run_mixed_f32(const fiveeq_model* model, int64_t n_members, int64_t ld, const float* drive, int32_t n_steps,
+                         int32_t t_begin, int32_t t_end, const float* r, const float* q, float* R, float* S, float* cumE,
+                         float* X_traj, float* T_traj, int32_t n_rows, double* T_stats, int32_t conc_mask, const float* fscale,
+                         const float* fext, int32_t n_fext, const double* obs, double* misfit, void* stream) {
+    return run_mixed<float>({model, n_members, ld, drive, n_steps, t_begin, t_end, r, q, R, S, X_traj, T_traj, n_rows, T_stats},
+                            cumE, conc_mask, {fscale, fext, n_fext}, {obs, misfit}, stream);
+}
+int fiveeq_mixed_layout_supported(int32_t n_gas, const int32_t* n_pools, int32_t conc_mask) {
+    if (!fiveeq_layout_supported(n_gas, n_pools) || conc_mask < 0 || conc_mask >> n_gas) return 0;
+    if (conc_mask == 0 || conc_mask == (1 << n_gas) - 1) return 1;              // the forward and the inverse kernels: every layout
+    return mixed_layout(layout_code(n_gas, n_pools)) ? 1 : 0;
 }
 
 int fiveeq_run_ksteps_f64(const fiveeq_model* model, int64_t n_members, int64_t ld, const double* drive,

@@ -381,4 +381,137 @@ __global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_mforc_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Kernel 2x — THE MIXED DRIVE (fiveeq_run_mixed_*, include/fiveeq.h "MIXED DRIVE"): fused_kernel's concentration-driven form
+// with a PER-GAS drive mask CM (member_step<.., CM>): bit g set, gas g follows the target concentrations in drive[t][g], its
+// cumulative emissions cumE[g] are the member's own and row g of X_traj receives the diagnosed E; bit g clear, gas g takes the
+// emissions drive[t][g] and the shared cumulative emissions drive[t][3 + g] like a forward run and row g receives C.
+// cumE [G][ld]: only the rows of concentration-driven gases are loaded and stored — the row of an emission-driven gas is never
+// read and never written.  CM is a PROPER mask (neither 0 nor all gases: those two are the forward and the inverse kernel, which
+// the host dispatches to); scalar lanes, one launch per span; MISFIT and FORC are the carriers of the inverse forms, in the
+// places FusedForc gives them (the fp64 4 + 1 + 1 FORC forms keep the scales in the LDS slot and stage 25 steps per refill).
+// A KERNEL OF ITS OWN, for fused_mforc_kernel's reason: one more template parameter would rename every fused_kernel symbol.  Its
+// step functions are instantiated with OWN = 2, which no other kernel uses, so no kernel that existed shares one with it
+// (member_step(): sharing moved the plain inverse kernel's schedule once).  profiles/r26/NOTES.md has the register counts.
+// ---------------------------------------------------------------------------------
+template <typename V, int P0, int P1, int P2, int CM, bool MISFIT = false, bool FORC = false>
+__global__ __launch_bounds__(FIVEEQ_BLOCK) void fused_mixed_kernel(
+    const KModel<V> km, const V* __restrict__ drive, const int n_steps, const int t_begin, const int t_end, const int64_t n,
+    const int64_t ld, const V* __restrict__ r, const V* __restrict__ q, V* __restrict__ R, V* __restrict__ S,
+    V* __restrict__ cumE /* [G][ld]: rows of the gases in CM only */, V* __restrict__ X_traj /* [n_rows][G][ld] or nullptr */,
+    V* __restrict__ T_traj /* [n_rows][ld] or nullptr */, const int n_rows,
+    double* __restrict__ stats /* [ceil(n/64)][n_steps][4] or nullptr */, const double* __restrict__ obs /* MISFIT: [n_steps][4] */,
+    double* __restrict__ misfit /* MISFIT: [3][ld] */, const V* __restrict__ fscale /* FORC: [G + n_fext][ld] */,
+    const V* __restrict__ fext /* FORC: [n_steps][MAX_FEXT] */, const int n_fext) {
+    using L = Layout<P0, P1, P2>;
+    using T = V;
+    static_assert(Lane<V>::W == 1, "the mixed drive has no packed instantiation");
+    static_assert(CM > 0 && CM < (1 << L::G) - 1, "a proper mask: some gas concentration-driven, some gas emission-driven");
+    constexpr int OWN = 2;                                                  // see member_step(): step functions of its own
+    constexpr int CHUNK = FusedForc<V, L, MISFIT, FORC>::CHUNK;             // steps staged per refill
+    constexpr bool FS_LDS = FusedForc<V, L, MISFIT, FORC>::FS_LDS;          // FORC: the scales in a lane-private LDS slot
+    __shared__ T drv[CHUNK * DRIVE_STRIDE];
+    __shared__ T xs[FORC ? CHUNK * MAX_FEXT : 1];                     // FORC: the table chunk
+    __shared__ V fs_s[FS_LDS ? (L::G + MAX_FEXT) * FIVEEQ_BLOCK : 1];  // FS_LDS: [G + MAX_FEXT][FIVEEQ_BLOCK], lane-private
+    __shared__ double acc_s[MISFIT ? 3 * FIVEEQ_BLOCK : 1];           // MISFIT: [3][FIVEEQ_BLOCK], lane-private
+    __shared__ V stat_tile[FIVEEQ_BLOCK / 64][STAT_STEPS * STAT_ROW];
+    __shared__ KModel<T> km_s;
+    static_assert(!FS_LDS || sizeof(drv) + sizeof(xs) + sizeof(fs_s) + sizeof(acc_s) + sizeof(stat_tile) + sizeof(km_s) <=
+                                 LDS_PER_CU / FusedForc<V, L, MISFIT, FORC>::WGS,
+                  "FS_LDS form: the workgroups it is there to keep no longer fit a CU's LDS");
+    stage_model(&km_s);
+    const KModel<T>& kmr = km_s;
+
+    const auto [m, active, full, mm] = lane_span<1, FIVEEQ_BLOCK, PARK_FIRST>(n);    // idle tail lanes shadow member 0 and store nothing
+    const int64_t n_rec = (n + 63) >> 6;                                             // statistics records: one per 64 members
+    const int64_t wave = (int64_t)blockIdx.x * (FIVEEQ_BLOCK / 64) + (threadIdx.x >> 6);
+    const bool wave_live = stats != nullptr && wave < n_rec;
+    V* const tile = stat_tile[threadIdx.x >> 6];
+    const int n_valid = (int)min((int64_t)64, n - wave * 64);                        // members of this wave (<= 0: none)
+    int ks = 0;                                                                      // steps parked in the tile
+
+    V rr[3 * L::G], qq[2], Rv[L::SP], Sv[2], Xv[L::G], Tn, cum[L::G];
+    V no_Rlo[L::SP];                                      // never touched: COMP = false
+#pragma unroll
+    for (int g = 0; g < L::G; ++g) {
+        if (CM >> g & 1) cum[g] = cumE[g * ld + mm];      // an emission-driven gas: its row is not read, cum[g] is not used
+    }
+#pragma unroll
+    for (int k = 0; k < L::SP; ++k) Rv[k] = load_lane<V>(R + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) Sv[k] = load_lane<V>(S + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 3 * L::G; ++k) rr[k] = load_lane<V>(r + k * ld + mm);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) qq[k] = load_lane<V>(q + k * ld + mm);
+    V fs_r[FORC && !FS_LDS ? L::G + MAX_FEXT : 1];
+    V* const fs = FS_LDS ? &fs_s[threadIdx.x] : fs_r;    // FORC: scale j of this lane at fs[j * FS_STRIDE]
+    constexpr int FS_STRIDE = FS_LDS ? FIVEEQ_BLOCK : 1;
+    if constexpr (FORC) {
+#pragma unroll
+        for (int k = 0; k < L::G + MAX_FEXT; ++k)
+            fs[k * FS_STRIDE] = k < L::G + n_fext ? load_lane<V>(fscale + k * ld + mm) : (V)T(0);
+    }
+    double* const acc = &acc_s[threadIdx.x];             // MISFIT: word k of this lane's member at acc[k * FIVEEQ_BLOCK]
+    if constexpr (MISFIT) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc[k * FIVEEQ_BLOCK] = misfit[k * ld + mm];
+    }
+
+    for (int tc = t_begin; tc < t_end; tc += CHUNK) {
+        const int nt = min(CHUNK, t_end - tc);
+        __syncthreads();                                  // previous chunk fully consumed
+        for (int i = threadIdx.x; i < nt * DRIVE_STRIDE; i += FIVEEQ_BLOCK)
+            drv[i] = drive[(int64_t)tc * DRIVE_STRIDE + i];
+        if constexpr (FORC) {
+            // n_fext == 0: member_step reads no record and fext is not a table — nothing is staged (a wave-uniform test)
+            if (n_fext > 0)
+                for (int i = threadIdx.x; i < nt * MAX_FEXT; i += FIVEEQ_BLOCK) xs[i] = fext[(int64_t)tc * MAX_FEXT + i];
+        }
+        __syncthreads();
+        for (int k = 0; k < nt; ++k) {
+            const T* d = &drv[k * DRIVE_STRIDE];
+            if constexpr (FORC)
+                member_step<V, L, true, false, true, NoGasHook, OWN, false, CM>(kmr, d, rr, qq, Rv, Sv, Xv, Tn, cum, no_Rlo, fs,
+                                                                                FS_STRIDE, &xs[k * MAX_FEXT], n_fext);
+            else
+                member_step<V, L, true, false, false, NoGasHook, OWN, false, CM>(kmr, d, rr, qq, Rv, Sv, Xv, Tn, cum, no_Rlo);
+            if constexpr (MISFIT) misfit_step(obs + (int64_t)(tc + k) * 4, Tn, acc, 3 * FIVEEQ_BLOCK, FIVEEQ_BLOCK, true);
+            const int row = __builtin_amdgcn_readfirstlane((int)d[7]);      // wave-uniform: a scalar branch, scalar row offsets
+            if (row >= 0 && row < n_rows) {
+                if (active) {
+                    if (X_traj != nullptr) {
+                        T* c = X_traj + (int64_t)row * L::G * ld + m;
+#pragma unroll
+                        for (int g = 0; g < L::G; ++g) store_lane(c + g * ld, Xv[g], full);
+                    }
+                    if (T_traj != nullptr) store_lane(T_traj + (int64_t)row * ld + m, Tn, full);
+                }
+            }
+            if (wave_live) {
+                tile[ks * STAT_ROW + (threadIdx.x & 63)] = Tn;
+                if (++ks == STAT_STEPS || tc + k + 1 == t_end) {
+                    const int64_t t_first = (int64_t)(tc + k + 1 - ks);
+                    wave_stats_flush(tile, ks, n_valid, stats + (wave * n_steps + t_first) * 4, 4);
+                    ks = 0;
+                }
+            }
+        }
+    }
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < L::SP; ++k) store_lane(R + k * ld + m, Rv[k], full);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) store_lane(S + k * ld + m, Sv[k], full);
+#pragma unroll
+        for (int g = 0; g < L::G; ++g) {
+            if (CM >> g & 1) cumE[g * ld + m] = cum[g];   // an emission-driven gas: its row is not written
+        }
+        if constexpr (MISFIT) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) misfit[k * ld + m] = acc[k * FIVEEQ_BLOCK];
+        }
+    }
+}
+
 }  // namespace fiveeq

@@ -161,7 +161,14 @@ struct NoGasHook {
 // MFORC = true (with FORC): the member also carries its OWN forcing series, one value per step (member_forcing rows, mf): the
 // step opens F = drive[t][6] + mf — one add — and goes on with the category and gas fmas exactly as FORC does.  A zero mf gives
 // the FORC step bit for bit (x + 0 = x for every x but -0).  MFORC = false is the code as it was.
-template <typename V, typename L, bool INV, bool COMP, bool FORC = false, typename Hook = NoGasHook, int OWN = 0, bool MFORC = false>
+// CM is the PER-GAS DRIVE MASK: bit g set = gas g is concentration-driven (gas_step<.., g, INV = true>: its target is drv[g], its
+// cumulative emissions cum[g] the member's own, out[g] = E), bit g clear = emission-driven (the forward gas step: drv[g] = E_g,
+// drv[3 + g] the shared cumulative emissions before the step, cum[g] neither read nor written, out[g] = C_g).  The default is what
+// INV alone meant — every gas or none — so every call that does not name it instantiates the step functions it did; a proper
+// mask (the mixed drive, fused_mixed_kernel) comes with an OWN value of its own, so that it shares no instantiation of the two
+// step functions with a kernel that existed (see OWN above).  F, the forcing fmas and the thermal step do not know the mask.
+template <typename V, typename L, bool INV, bool COMP, bool FORC = false, typename Hook = NoGasHook, int OWN = 0, bool MFORC = false,
+          int CM = (INV ? (1 << L::G) - 1 : 0)>
 __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& km, const typename Lane<V>::S* __restrict__ drv,
                                             const V (&rr)[3 * L::G], const V (&qq)[2],
                                             V (&R)[L::SP], V (&S)[2], V (&out)[L::G], V& Tnew, V (&cum)[L::G],
@@ -170,6 +177,7 @@ __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& k
                                             const Hook after_gas = Hook{}, const V mf = V()) {
     static_assert(!FORC || !COMP, "the forcing scales are not carried by the compensated form");
     static_assert(!MFORC || (FORC && !INV), "the per-member forcing row is carried by the forward forcing-scale forms only");
+    static_assert(CM >= 0 && CM < (1 << L::G) && (INV || CM == 0), "a drive mask names gases of the layout, and a forward step none");
     const V T_old = S[0] + S[1];
     V F = (V)drv[6];
     if constexpr (MFORC) F = F + mf;
@@ -182,20 +190,20 @@ __device__ __forceinline__ void member_step(const KModel<typename Lane<V>::S>& k
     // ~45 being hoisted to the kernel top (VGPR pressure) or out of the fused time loop.  (Issuing gas
     // g+1's reads before gas g's arithmetic was tried: +-1 %, 133 VGPRs; not kept.)
     asm volatile("" ::: "memory");
-    const V F0 = gas_step<V, L, 0, INV, COMP, OWN>(km, km.gas[0], drv, rr, T_old, R, out, cum, Rlo);
+    const V F0 = gas_step<V, L, 0, bool(CM >> 0 & 1), COMP, OWN>(km, km.gas[0], drv, rr, T_old, R, out, cum, Rlo);
     if constexpr (FORC) F = fe_fma(fs[0 * fs_stride], F0, F);
     else F += F0;
     after_gas(GasTag<0>{});
     if constexpr (L::G > 1) {
         asm volatile("" ::: "memory");
-        const V F1 = gas_step<V, L, 1, INV, COMP, OWN>(km, km.gas[1], drv, rr, T_old, R, out, cum, Rlo);
+        const V F1 = gas_step<V, L, 1, bool(CM >> 1 & 1), COMP, OWN>(km, km.gas[1], drv, rr, T_old, R, out, cum, Rlo);
         if constexpr (FORC) F = fe_fma(fs[1 * fs_stride], F1, F);
         else F += F1;
         after_gas(GasTag<1>{});
     }
     if constexpr (L::G > 2) {
         asm volatile("" ::: "memory");
-        const V F2 = gas_step<V, L, 2, INV, COMP, OWN>(km, km.gas[2], drv, rr, T_old, R, out, cum, Rlo);
+        const V F2 = gas_step<V, L, 2, bool(CM >> 2 & 1), COMP, OWN>(km, km.gas[2], drv, rr, T_old, R, out, cum, Rlo);
         if constexpr (FORC) F = fe_fma(fs[2 * fs_stride], F2, F);
         else F += F2;
         after_gas(GasTag<2>{});

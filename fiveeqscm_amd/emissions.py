@@ -37,14 +37,58 @@ def emissions_sha256(E):
     return hashlib.sha256(np.ascontiguousarray(E, dtype=np.float64).tobytes()).hexdigest()
 
 
-def make_drive(emissions, F_ext=None, dt=1.0, output_steps=None, concentration_driven=False):
+def concentration_mask(concentration_gases, n_gas):
+    """The per-gas drive mask of a mixed run (include/fiveeq.h "MIXED DRIVE"): bit g set for every gas index in
+    `concentration_gases` (a sequence of distinct integers in 0 .. n_gas - 1; empty: every gas emission-driven)."""
+    try:
+        gases = [int(g) for g in concentration_gases]
+        exact = all(g == x for g, x in zip(gases, concentration_gases))
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"concentration_gases={concentration_gases!r}: want a sequence of gas indices") from exc
+    if not exact or any(not 0 <= g < n_gas for g in gases):
+        raise ValueError(f"concentration_gases={list(concentration_gases)!r}: want gas indices in 0..{n_gas - 1}")
+    if len(set(gases)) != len(gases):
+        raise ValueError(f"concentration_gases={gases!r}: a gas is named twice")
+    return sum(1 << g for g in gases)
+
+
+def make_drive(emissions, F_ext=None, dt=1.0, output_steps=None, concentration_driven=False, *, concentrations=None,
+               concentration_gases=None):
     """emissions [n_steps, G] (or [n_steps]) -> drive [n_steps, 8] fp64 (include/fiveeq.h):
     cols 0..2 E_g, cols 3..5 cumulative emissions BEFORE the step, col 6 F_ext, col 7 the output
     row the step's C/T are stored at (-1: not stored).  output_steps=None stores every step at
     row t; otherwise the listed steps are stored at rows 0, 1, ... in increasing step order.
     concentration_driven=True: `emissions` holds target concentrations (end of step) for the
-    inverse mode; cols 3..5 stay zero."""
-    E = np.asarray(emissions, dtype=np.float64)
+    inverse mode; cols 3..5 stay zero.
+    THE PER-GAS FORM (concentration_gases= a sequence of gas indices, with concentrations= [n_steps, G]; the mixed drive):
+    cols g and 3 + g of every other gas are built from `emissions` as for a forward run (col 3 + g the cumulative emissions
+    before the step); col g of a gas in concentration_gases holds its target from `concentrations` and its col 3 + g is zero.
+    The `emissions` column of a concentration-driven gas and the `concentrations` column of an emission-driven one are
+    ignored (NaN allowed there); `emissions` may be None when every gas is named, `concentrations` when none is."""
+    if concentration_gases is not None:
+        if concentration_driven:
+            raise ValueError("concentration_gases= is the per-gas form: leave concentration_driven False")
+        given = [np.asarray(x, dtype=np.float64) for x in (emissions, concentrations) if x is not None]
+        given = [x[:, None] if x.ndim == 1 else x for x in given]
+        if not given or any(x.ndim != 2 or x.shape != given[0].shape for x in given):
+            raise ValueError("emissions and concentrations: want two arrays of one shape [n_steps, G]")
+        G = given[0].shape[1] if 1 <= given[0].shape[1] <= MAX_GAS else 0
+        mask = concentration_mask(concentration_gases, G) if G else 0
+        src = {False: emissions, True: concentrations}
+        for conc in (False, True):
+            if src[conc] is None and any(bool(mask >> g & 1) == conc for g in range(G)):
+                raise ValueError(f"{'concentrations' if conc else 'emissions'} is None, but a gas is "
+                                 f"{'concentration' if conc else 'emission'}-driven")
+        E = np.zeros(given[0].shape)
+        for g in range(G):
+            x = np.asarray(src[bool(mask >> g & 1)], dtype=np.float64)
+            E[:, g] = x if x.ndim == 1 else x[:, g]
+        forward = [g for g in range(G) if not mask >> g & 1]     # the gases whose cols g, 3 + g are a forward run's
+    else:
+        forward = None
+        if concentrations is not None:
+            raise ValueError("concentrations= needs concentration_gases=")
+        E = np.asarray(emissions, dtype=np.float64)
     if E.ndim == 1:
         E = E[:, None]
     if E.ndim != 2 or not 1 <= E.shape[1] <= MAX_GAS or E.shape[0] < 1:
@@ -54,7 +98,9 @@ def make_drive(emissions, F_ext=None, dt=1.0, output_steps=None, concentration_d
     n_steps, G = E.shape
     drive = np.zeros((n_steps, DRIVE_STRIDE), dtype=np.float64)
     drive[:, :G] = E
-    if not concentration_driven:          # inverse mode: cumulative emissions are per-member state
+    if forward is not None:               # the per-gas form: the emission-driven gases' columns only
+        drive[1:, [3 + g for g in forward]] = np.cumsum(E[:, forward] * dt, axis=0)[:-1]
+    elif not concentration_driven:        # inverse mode: cumulative emissions are per-member state
         drive[1:, 3:3 + G] = np.cumsum(E * dt, axis=0)[:-1]
     if F_ext is not None:
         F_ext = np.asarray(F_ext, dtype=np.float64).reshape(-1)

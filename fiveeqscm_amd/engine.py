@@ -27,7 +27,7 @@ import torch
 from . import _capi
 from ._rowargs import bool_mask, int_weights
 from .checkpoint import CheckpointMixin
-from .emissions import emissions_sha256, make_drive, make_scenario_drive
+from .emissions import concentration_mask, emissions_sha256, make_drive, make_scenario_drive
 from .forcing import ScenarioForcings
 from .params import make_model, n_gas_of, pools_of
 from .tuning import (_env_choice, _env_positive, calibrate, concurrent_side_streams,  # noqa: F401  (calibrate: part of this
@@ -255,7 +255,7 @@ class EnsembleEngine(CheckpointMixin):
         else:
             if scenario_names is not None:
                 raise ValueError("scenario_names= needs emissions of several scenarios ([S, n_steps, G])")
-            drive = make_drive(emissions, F_ext, dt, output_steps, self.concentration_driven)
+            drive = self._make_drive(emissions, F_ext, dt, output_steps)
             self.n_scenarios = Sc = 1
             self.scenario_names = None
             row_map = drive
@@ -412,6 +412,10 @@ class EnsembleEngine(CheckpointMixin):
         self.refresh_uniform_rows()
         with torch.cuda.device(self.device):
             self.probe_streams()            # construction is synchronous anyway: the one place the probe may clock streams
+
+    def _make_drive(self, emissions, F_ext, dt, output_steps):
+        """The drive table [n_steps, 8] of an engine without the scenario axis (MixedDriveEngine builds its per-gas form)."""
+        return make_drive(emissions, F_ext, dt, output_steps, self.concentration_driven)
 
     def _scale_rows(self):
         """The scale rows the forcing kernels load: `fscale` of forcing=, or the unit rows of a member_forcing= engine without
@@ -1415,6 +1419,58 @@ class ConcentrationDrivenEngine(EnsembleEngine):
         obs = (None, None) if self.misfit is None else self._obs_args()
         return self._fn("run_inverse_forc")(*self._run_args(t_begin, t_end, cumE=self._ptr(self.cumE)), *forc, *obs,
                                             self._stream(stream))
+
+
+class MixedDriveEngine(ConcentrationDrivenEngine):
+    """An ensemble whose gases are driven EACH ITS OWN WAY in one run: the gases named in `concentration_gases` follow the
+    target concentrations `concentrations` [n_steps, G] (end of each step, shared by all members) and have their emissions
+    diagnosed, every other gas takes the emissions `emissions` [n_steps, G] as a forward run does.  CO2 emission-driven with
+    CH4 and N2O prescribed — MixedDriveEngine(params, N, E, C, (1, 2)) — is the "esm-hist" set-up and the history leg of a
+    carbon-cycle calibration: r0 / rC / rT show in C of CO2 and in T; the converse, (0,), is a concentration pathway of CO2
+    with its compatible emissions beside short-lived gases from inventories.  The `emissions` column of a
+    concentration-driven gas and the `concentrations` column of an emission-driven gas are ignored (NaN allowed there).
+        conc_mask   bit g set = gas g is concentration-driven (include/fiveeq.h "MIXED DRIVE");
+        out_kind    per gas what its rows hold, e.g. ("C", "E", "E");
+        X           [n_rows, G, N]: C of an emission-driven gas, the diagnosed E of a concentration-driven one (`C` and `E` are
+                    the same tensor, as on every concentration-driven engine);
+        cumE        [G, N]: the cumulative emissions of the concentration-driven gases; the rows of emission-driven gases stay
+                    zero (the kernel neither reads nor writes them: their cumulative emissions are the drive table's).
+    One time-fused launch per run() call (fiveeq_run_mixed_*).  An empty `concentration_gases` runs the forward time-fused
+    kernel and a full one the inverse kernel, bit for bit; a proper selection needs pools [4, 1, 1].  forcing=,
+    observations= and everything ConcentrationDrivenEngine offers on its rows work as there (fscale, misfit, chi2(), score()
+    of T, stats(), gather_summary() of T, parameter_rows(), drivers(), reset_state(), bytes_per_member_step());
+    state_dict() carries `conc_mask`, and load_state_dict() refuses a checkpoint of another mask.  Refused as for every
+    concentration-driven engine: the scenario axis, hist=, compensated=True, mode 'small', forcing_rows(), resampled(),
+    gas= summaries and gas records in score().  A projection branches off through R0 / S0 as from ConcentrationDrivenEngine."""
+
+    def __init__(self, params, n_members, emissions, concentrations, concentration_gases, *, forcing=None, observations=None,
+                 **kw):
+        if _is_scenario_set(emissions) or _is_scenario_set(concentrations):
+            raise ValueError("a mixed-drive engine runs one scenario: emissions and concentrations are [n_steps, G] (the "
+                             "scenario axis is carried by the plain emission-driven forms only)")
+        G = n_gas_of(params)
+        self.conc_mask = concentration_mask(concentration_gases, G)
+        self.concentration_gases = tuple(g for g in range(G) if self.conc_mask >> g & 1)
+        self.out_kind = tuple("E" if self.conc_mask >> g & 1 else "C" for g in range(G))
+        self._mixed_series = (emissions, concentrations)
+        make_drive(emissions, kw.get("F_ext"), kw.get("dt", 1.0), kw.get("output_steps"), concentrations=concentrations,
+                   concentration_gases=self.concentration_gases)          # the table's own refusals, before a device is asked for
+        super().__init__(params, n_members, None, forcing=forcing, observations=observations, **kw)
+        self.X = self.C
+        n_pools = (ctypes.c_int32 * G)(*self.pools)
+        if not self.lib.fiveeq_mixed_layout_supported(G, n_pools, self.conc_mask):
+            raise _capi.FiveEqError(_capi.E_UNSUPPORTED, f"pool layout {self.pools} has no mixed-drive form for "
+                                    f"concentration_gases={self.concentration_gases} (pools [4, 1, 1] have)")
+
+    def _make_drive(self, emissions, F_ext, dt, output_steps):
+        E, C = self._mixed_series
+        return make_drive(E, F_ext, dt, output_steps, concentrations=C, concentration_gases=self.concentration_gases)
+
+    def _run_inverse(self, t_begin, t_end, stream):
+        forc = (None, None, 0) if self.fscale is None else (self._ptr(self.fscale), self._ptr(self.fext), self.forcing.n_categories)
+        obs = (None, None) if self.misfit is None else self._obs_args()
+        return self._fn("run_mixed")(*self._run_args(t_begin, t_end, cumE=self._ptr(self.cumE)), self.conc_mask, *forc, *obs,
+                                     self._stream(stream))
 
 
 def run_ensemble(emissions, params, n_members, *, F_ext=None, dt=1.0, dtype=torch.float64, device=None,

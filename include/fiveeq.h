@@ -576,6 +576,44 @@ int fiveeq_run_inverse_forc_f32(const fiveeq_model *model, int64_t n_members, in
                                 const float *fscale, const float *fext, int32_t n_fext,
                                 const double *obs, double *misfit, void *stream);
 
+/* MIXED DRIVE — emission-driven and concentration-driven gases in one run (new; ADDITIVE: FIVEEQ_ABI_VERSION stays 13, no existing
+ * prototype or struct changes, sizeof(fiveeq_model) stays 448).  conc_mask selects the driver of each gas: bit g set, gas g is
+ * CONCENTRATION-DRIVEN; bit g clear, EMISSION-DRIVEN.  The arguments are those of fiveeq_run_inverse_forc_* with conc_mask behind
+ * T_stats.  One drive table [n_steps][8] as everywhere:
+ *   an emission-driven gas       drive[t][g] = E_g, drive[t][3 + g] = the shared cumulative emissions BEFORE step t (the forward
+ *                                convention); row g of X_traj [n_rows][G][ld] receives C_g; cumE row g is NEVER READ AND NEVER
+ *                                WRITTEN;
+ *   a concentration-driven gas   drive[t][g] = the target concentration at the end of step t, drive[t][3 + g] is not read (the
+ *                                inverse convention); cumE row g is the member's cumulative emissions (in/out, start at 0); row g
+ *                                of X_traj receives the diagnosed E_g.
+ * Each gas takes the forward or the inverse gas step exactly as it stands; the forcing is accumulated in the order of the other
+ * forms (drive[t][6], the categories, then gases 0 .. G-1), the thermal step is unchanged.  fscale, fext, n_fext, obs and misfit
+ * follow the NULL rules of fiveeq_run_inverse_forc_*.  Time-fused: one launch for the span, one member per lane in both
+ * precisions.  By the mask:
+ *   conc_mask == 0             the call IS the forward time-fused call on these arguments — fiveeq_run_fused_*, or
+ *                              fiveeq_run_forc_* (with scales) / fiveeq_run_obs_* (misfit alone) with FIVEEQ_FORM_FUSED and
+ *                              k_steps = 0 — bit for bit; cumE may be NULL;
+ *   conc_mask == (1 << G) - 1  the call IS fiveeq_run_inverse_forc_*, bit for bit;
+ *   a proper mask              the mixed kernels: pool layout 4 + 1 + 1, all six masks, with and without the scales and the misfit.
+ * Refused before anything is launched, in this order: FIVEEQ_E_INVALID for the base arguments as fiveeq_run_inverse_* reports
+ * them; a negative conc_mask; a conc_mask with a bit at or above n_gas; a NULL cumE with a non-zero conc_mask; then every refusal
+ * of fiveeq_run_inverse_forc_* from n_fext on, in its order; last, FIVEEQ_E_UNSUPPORTED for a proper mask on a pool layout without
+ * the mixed form.  fiveeq_mixed_layout_supported: 1 when fiveeq_run_mixed_* runs conc_mask on the layout (masks 0 and all-gases
+ * on every compiled layout), else 0 — a negative mask or one with a bit at or above n_gas included. */
+int fiveeq_run_mixed_f64(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                         const double *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                         const double *r, const double *q, double *R, double *S, double *cumE,
+                         double *X_traj, double *T_traj, int32_t n_rows, double *T_stats,
+                         int32_t conc_mask, const double *fscale, const double *fext, int32_t n_fext,
+                         const double *obs, double *misfit, void *stream);
+int fiveeq_run_mixed_f32(const fiveeq_model *model, int64_t n_members, int64_t ld,
+                         const float *drive, int32_t n_steps, int32_t t_begin, int32_t t_end,
+                         const float *r, const float *q, float *R, float *S, float *cumE,
+                         float *X_traj, float *T_traj, int32_t n_rows, double *T_stats,
+                         int32_t conc_mask, const float *fscale, const float *fext, int32_t n_fext,
+                         const double *obs, double *misfit, void *stream);
+int fiveeq_mixed_layout_supported(int32_t n_gas, const int32_t *n_pools, int32_t conc_mask);
+
 /* Ensemble form of the reference's one function,
  *   calculate_hfc_conc(emissions, time, lifetime) = emissions[0]*exp(-time)
  * (U_FaIR/concentrations.py:4-5): out[k][m] = e0[m] * exp(-time[k]).
