@@ -30,7 +30,12 @@ those are branched into the scenarios (EnsembleEngine.resampled) and summarised,
 they explain (EnsembleEngine.drivers: eta2, the first-order sensitivity index, with the correlation) — once over all projected
 members and once under the posterior the run uses (weights, accepted, or the resampled members, which are their own posterior).
 
+--metrics LEVELS --smooth W judges the warming levels and the peak on the running mean over W stored rows
+(EnsembleEngine.running_mean, dated at the window's centre) instead of on single rows — what a warming level means once
+members carry internal variability.
+
     python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights] [--resample M] [--drivers]
+                                           [--metrics LEVELS [--smooth W]]
 """
 import argparse
 import os
@@ -58,6 +63,8 @@ def main():
     ap.add_argument("--resample", type=int, default=0, metavar="M", help="project only M resampled equal-weight members")
     ap.add_argument("--metrics", default="", metavar="LEVELS", help="comma-separated warming levels (K): also print, per scenario, "
                     "peak warming, P(exceed level) and the crossing year, from one pass over the stored rows")
+    ap.add_argument("--smooth", type=int, default=0, metavar="W", help="with --metrics: judge the levels and the peak on the running mean "
+                    "over W stored rows (dated at the window's centre) instead of on single rows")
     ap.add_argument("--forcing-rows", action="store_true", help="also print, per scenario, the percentiles of the forcing F and the "
                     "energy imbalance N at the last summary year (diagnosed from the stored rows: the projection then stores C too)")
     ap.add_argument("--drivers", action="store_true", help="rank the parameters by the share of the spread of T they explain")
@@ -116,7 +123,13 @@ def main():
         from fiveeqscm_amd import metrics
         from fiveeqscm_amd.distributed import gather_summary, gather_weighted_summary
         levels = tuple(float(v) for v in a.metrics.split(","))
-        m = proj.trajectory_metrics(levels=levels)              # all scenarios in one launch, stored steps only
+        what, when = "peak warming", "first stored year at or above"
+        if a.smooth:                                            # the W-row running mean of the evenly stored rows, dated at its centre
+            sm = proj.running_mean(a.smooth, rows=slice(0, len(range(t_branch, n_steps, 10))))
+            m = metrics.trajectory_metrics(sm.rows, sm.steps, levels=levels)
+            what, when = f"peak of the {a.smooth}-row mean", f"centre year of the first {a.smooth}-row mean at or above"
+        else:
+            m = proj.trajectory_metrics(levels=levels)          # all scenarios in one launch, stored steps only
         w = how.get("weights")
         for s, name in enumerate(proj.scenario_names):
             peak = m.peak[s].reshape(1, -1)
@@ -124,13 +137,13 @@ def main():
                 q = gather_weighted_summary(peak, w, pct)["percentiles"][0].tolist()
             else:
                 q = gather_summary(peak[:, how["accepted"]].contiguous() if "accepted" in how else peak, pct)["percentiles"][0].tolist()
-            print(f"  {name:5s} peak warming 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} K")
+            print(f"  {name:5s} {what} 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} K")
             first = m.first[s] if "accepted" not in how else m.first[s][:, how["accepted"]]
             for l, (crossed, total) in enumerate(metrics.exceedance(first, weights=w)):
                 line = f"        P(T >= {levels[l]:g} K) = {crossed / total:.4f}"
                 if crossed:
                     c = metrics.crossing_summary(first[l], run_years, pct, weights=w)["percentiles"][0].tolist()
-                    line += f"; first stored year at or above, among those that cross, 5/50/95 %: {c[0]:.0f} / {c[1]:.0f} / {c[2]:.0f}"
+                    line += f"; {when}, among those that cross, 5/50/95 %: {c[0]:.0f} / {c[1]:.0f} / {c[2]:.0f}"
                 print(line)
     if a.forcing_rows:
         from fiveeqscm_amd.distributed import gather_summary, gather_weighted_summary

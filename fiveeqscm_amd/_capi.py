@@ -24,6 +24,7 @@ METRICS_TILE_F64 = 512              # members per workgroup of traj_metrics_kern
 METRICS_TILE_F32 = 1024
 METRICS_UNROLL = 8                  # rows whose loads its row loop issues before it uses the first (16-byte loads)
 METRICS_UNROLL_NARROW = 2           # the same on the element-load path; load() checks all four against the library
+MAX_SMOOTH_WINDOW = 32              # FIVEEQ_MAX_SMOOTH_WINDOW of fiveeq_running_mean_* (fiveeq_smooth.hpp); load() checks it
 MAX_JOINT_ROWS = 32                 # fiveeq_max_joint_rows() / fiveeq_max_cond_bins() of the joint statistics (fiveeq_joint.hpp)
 MAX_COND_BINS = 32
 # fiveeq_joint_tile(0..7): x rows, y rows per workgroup of the co-moment pass; members per chunk; members per lane and load of
@@ -196,6 +197,15 @@ SIGNATURES = {
     "fiveeq_metrics_unroll": (_i32, [_i32]),
     "fiveeq_traj_metrics_f64": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _i32, _p]),
     "fiveeq_traj_metrics_f32": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _p, _i32, _p]),
+    "fiveeq_max_smooth_window": (_i32, []),
+    "fiveeq_smooth_tile": (_i32, [_i32]),
+    "fiveeq_smooth_unroll": (_i32, [_i32]),
+    # (n_scen, n_rows, n_members, ld, rows, scen_stride, window, n_tail, tail, tail_scen_stride, out, out_scen_stride, stream)
+    "fiveeq_running_mean_f64": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _i32, _i32, _p, _i64, _p, _i64, _p]),
+    "fiveeq_running_mean_f32": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _i32, _i32, _p, _i64, _p, _i64, _p]),
+    # (n_scen, n_rows, n_members, ld, rows, scen_stride, steps, n_windows, windows, tsum, first_call, stream)
+    "fiveeq_window_trends_f64": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _p, _i32, _p]),
+    "fiveeq_window_trends_f32": (ctypes.c_int, [_i32, _i32, _i64, _i64, _p, _i64, _p, _i32, _p, _p, _i32, _p]),
     "fiveeq_max_joint_rows": (_i32, []),
     "fiveeq_max_cond_bins": (_i32, []),
     "fiveeq_joint_tile": (_i32, [_i32]),
@@ -232,7 +242,8 @@ _lib = None
 SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
-    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp", "fiveeq_noise.hpp")) + (
+    "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp", "fiveeq_noise.hpp",
+    "fiveeq_smooth.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 
@@ -294,6 +305,9 @@ def load(path=None):
     pulse = (lib.fiveeq_max_pulses(), lib.fiveeq_max_horizons())
     if pulse != (MAX_PULSES, MAX_HORIZONS):
         raise ImportError(f"{lib_path}: pulse_response_kernel's limits are {pulse}, the binding's constants say otherwise")
+    if lib.fiveeq_max_smooth_window() != MAX_SMOOTH_WINDOW:
+        raise ImportError(f"{lib_path}: running_mean_kernel's window limit is {lib.fiveeq_max_smooth_window()}, the binding's constant "
+                          "says otherwise")
     # The library must have been compiled from the sources lying next to this file: a prebuilt .so that travelled to
     # another box, or survived a source edit, is refused instead of tested.  (FIVEEQ_ALLOW_STALE_LIB=1: experiment
     # variants built from patched sources, tools/ only.)

@@ -2011,6 +2011,114 @@ int fiveeq_traj_metrics_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, i
     return traj_metrics<float>(n_scen, n_rows, n_members, ld, rows, scen_stride, steps, n_levels, levels, n_windows, windows, fmet, imet,
                                first_call, stream);
 }
+// ---- running means and linear-trend sums of stored rows (kernels 15a / 15b) -------------------------------------------------
+}  // extern "C"
+namespace {
+static_assert(fiveeq::SMOOTH_MAX_WINDOW == FIVEEQ_MAX_SMOOTH_WINDOW, "fiveeq_smooth.hpp and fiveeq.h disagree");
+static_assert((size_t)fiveeq::SMOOTH_BLOCK * 16 * FIVEEQ_MAX_SMOOTH_WINDOW <= 64 * 1024,
+              "running_mean_kernel's ring outgrows the default dynamic-LDS limit: the launcher would have to raise it");
+// what both passes check first, in the order include/fiveeq.h lists it
+int smooth_check(int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, int64_t scen_stride) {
+    if (int rc = check_scen(n_scen)) return rc;
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (n_scen > 1 && scen_stride < (int64_t)n_rows * ld)
+        return fail(FIVEEQ_E_INVALID, "scen_stride=%lld < n_rows * ld = %lld", (long long)scen_stride, (long long)((int64_t)n_rows * ld));
+    return FIVEEQ_OK;
+}
+template <typename T>
+int running_mean(int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, const T* rows, int64_t scen_stride, int32_t window, int32_t n_tail,
+                 const T* tail, int64_t tail_scen_stride, double* out, int64_t out_scen_stride, void* stream) {
+    if (int rc = smooth_check(n_scen, n_rows, n, ld, scen_stride)) return rc;
+    if (window < 1 || window > FIVEEQ_MAX_SMOOTH_WINDOW)
+        return fail(FIVEEQ_E_INVALID, "window=%d outside 1..%d", window, FIVEEQ_MAX_SMOOTH_WINDOW);
+    if (n_tail < 0 || n_tail > window - 1) return fail(FIVEEQ_E_INVALID, "n_tail=%d outside 0..window-1 = %d", n_tail, window - 1);
+    const int64_t total = (int64_t)n_tail + n_rows, n_out = total >= window ? total - window + 1 : 0;
+    if (n_scen > 1 && tail_scen_stride < (int64_t)n_tail * ld)
+        return fail(FIVEEQ_E_INVALID, "tail_scen_stride=%lld < n_tail * ld = %lld", (long long)tail_scen_stride, (long long)((int64_t)n_tail * ld));
+    if (n_scen > 1 && out_scen_stride < n_out * ld)
+        return fail(FIVEEQ_E_INVALID, "out_scen_stride=%lld < n_out * ld = %lld", (long long)out_scen_stride, (long long)(n_out * ld));
+    const NamedPtrs ptrs = {{"rows", rows, sizeof(T), n_rows > 0}, {"tail", tail, sizeof(T), n_tail > 0}, {"out", out, 8, n_out > 0}};
+    if (int rc = check_not_null(ptrs)) return rc;
+    if (int rc = check_aligned(ptrs)) return rc;
+    if (n_out == 0) return FIVEEQ_OK;                          // fewer rows than a window: no output
+    // every row the pass touches starts at base + s stride + k ld: 16-byte accesses where all of them are aligned (out is
+    // fp64: two elements per 16 bytes, which ld % PER16<T> == 0 covers for either T)
+    const bool many = n_scen > 1;
+    const bool wide = ld % PER16<T> == 0 && !misaligned(out, 16) && (!many || out_scen_stride % 2 == 0) &&
+                      (n_rows == 0 || (!misaligned(rows, 16) && (!many || scen_stride % PER16<T> == 0))) &&
+                      (n_tail == 0 || (!misaligned(tail, 16) && (!many || tail_scen_stride % PER16<T> == 0)));
+    const size_t lds = (size_t)fiveeq::SMOOTH_BLOCK * 16 * (size_t)window;
+    launch_split(wide_members<T>(wide, n), n, [&](auto vec, int64_t m0, int64_t members) {
+        const dim3 grid((unsigned)((members + fiveeq::SMOOTH_TILE<T> - 1) / fiveeq::SMOOTH_TILE<T>), (unsigned)n_scen);
+        hipLaunchKernelGGL((fiveeq::running_mean_kernel<T, decltype(vec)::value>), grid, dim3(fiveeq::SMOOTH_BLOCK), lds, (hipStream_t)stream,
+                           n_rows, (int)members, ld, rows ? rows + m0 : rows, scen_stride, window, n_tail, tail ? tail + m0 : tail,
+                           tail_scen_stride, out + m0, out_scen_stride);
+    });
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+template <typename T>
+int window_trends(int32_t n_scen, int32_t n_rows, int64_t n, int64_t ld, const T* rows, int64_t scen_stride, const int32_t* steps,
+                  int32_t n_windows, const int32_t* windows, double* tsum, int32_t first_call, void* stream) {
+    if (int rc = smooth_check(n_scen, n_rows, n, ld, scen_stride)) return rc;
+    if (n_windows < 0 || n_windows > FIVEEQ_MAX_WINDOWS)
+        return fail(FIVEEQ_E_INVALID, "n_windows=%d outside 0..%d", n_windows, FIVEEQ_MAX_WINDOWS);
+    if (n_windows > 0 && !windows) return fail(FIVEEQ_E_INVALID, "windows is NULL with n_windows=%d", n_windows);
+    const NamedPtrs ptrs = {{"rows", rows, sizeof(T), n_rows > 0}, {"steps", steps, 4, n_rows > 0}, {"tsum", tsum, 8, n_windows > 0}};
+    if (int rc = check_not_null(ptrs)) return rc;
+    if (int rc = check_aligned(ptrs)) return rc;
+    fiveeq::TrendSpec sp = {};
+    for (int w = 0; w < n_windows; ++w) {
+        const int32_t a = windows[2 * w], b = windows[2 * w + 1];
+        if (a < 0 || a > b) return fail(FIVEEQ_E_INVALID, "windows[%d] = [%d, %d): want 0 <= a <= b", w, a, b);
+        sp.win[w][0] = a, sp.win[w][1] = b;
+    }
+    sp.n_windows = n_windows;
+    if (n_windows == 0 || (n_rows == 0 && !first_call)) return FIVEEQ_OK;         // no state, or nothing to fold into it
+    const bool wide = !misaligned(rows, 16) && ld % PER16<T> == 0 && (n_scen == 1 || scen_stride % PER16<T> == 0);
+    launch_split(wide_members<T>(wide, n), n, [&](auto vec, int64_t m0, int64_t members) {
+        const dim3 grid((unsigned)((members + fiveeq::TREND_TILE<T> - 1) / fiveeq::TREND_TILE<T>), (unsigned)n_scen);
+        const auto launch = [&](auto first) {
+            hipLaunchKernelGGL((fiveeq::window_trend_kernel<T, decltype(first)::value, decltype(vec)::value>), grid, dim3(FIVEEQ_BLOCK), 0,
+                               (hipStream_t)stream, n_rows, (int)members, ld, rows ? rows + m0 : rows, scen_stride, steps, sp, tsum + m0);
+        };
+        if (first_call) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int32_t fiveeq_max_smooth_window(void) { return FIVEEQ_MAX_SMOOTH_WINDOW; }
+int32_t fiveeq_smooth_tile(int32_t elem_bytes) {
+    return elem_bytes == 8 ? fiveeq::SMOOTH_TILE<double> : elem_bytes == 4 ? fiveeq::SMOOTH_TILE<float> : 0;
+}
+int32_t fiveeq_smooth_unroll(int32_t wide) { return wide ? fiveeq::METRICS_UNROLL : fiveeq::METRICS_UNROLL_NARROW; }
+int fiveeq_running_mean_f64(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const double* rows, int64_t scen_stride,
+                            int32_t window, int32_t n_tail, const double* tail, int64_t tail_scen_stride, double* out,
+                            int64_t out_scen_stride, void* stream) {
+    return running_mean<double>(n_scen, n_rows, n_members, ld, rows, scen_stride, window, n_tail, tail, tail_scen_stride, out,
+                                out_scen_stride, stream);
+}
+int fiveeq_running_mean_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const float* rows, int64_t scen_stride,
+                            int32_t window, int32_t n_tail, const float* tail, int64_t tail_scen_stride, double* out,
+                            int64_t out_scen_stride, void* stream) {
+    return running_mean<float>(n_scen, n_rows, n_members, ld, rows, scen_stride, window, n_tail, tail, tail_scen_stride, out,
+                               out_scen_stride, stream);
+}
+int fiveeq_window_trends_f64(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const double* rows, int64_t scen_stride,
+                             const int32_t* steps, int32_t n_windows, const int32_t* windows, double* tsum, int32_t first_call,
+                             void* stream) {
+    return window_trends<double>(n_scen, n_rows, n_members, ld, rows, scen_stride, steps, n_windows, windows, tsum, first_call, stream);
+}
+int fiveeq_window_trends_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const float* rows, int64_t scen_stride,
+                             const int32_t* steps, int32_t n_windows, const int32_t* windows, double* tsum, int32_t first_call,
+                             void* stream) {
+    return window_trends<float>(n_scen, n_rows, n_members, ld, rows, scen_stride, steps, n_windows, windows, tsum, first_call, stream);
+}
 // ---- joint statistics of per-member rows (kernels 10a / 10b) ----------------------------------------------------------------
 }  // extern "C"
 namespace {

@@ -29,6 +29,7 @@
 //   fiveeq_forcrows.hpp 12 forcing_rows_kernel the forcing, energy imbalance and heat uptake of a run recomputed from its stored rows
 //   fiveeq_pulse.hpp    13 pulse_response_kernel the forcing, warming and concentration response to emission pulses, summed to horizons
 //   fiveeq_noise.hpp    14 noise_rows_kernel    per-member AR(1) noise rows from a counter-based integer deviate (member_forcing rows)
+//   fiveeq_smooth.hpp   15 running_mean_kernel, window_trend_kernel: per-member running means and linear-trend sums of stored rows
 // and what they share: fiveeq_math.hpp (the model struct, lane types, fe_* math), fiveeq_stats.hpp (per-wave statistics, the bin
 // rule), fiveeq_member.hpp (member_step(), gas_forcing(), the misfit update, the lane's member span and row access).
 // All model arithmetic is member_step(): every kernel that steps the model gives the same bits.
@@ -75,6 +76,7 @@ constexpr int DRIVE_STRIDE = 8;
 #include "fiveeq_wsummary.hpp"
 #include "fiveeq_resample.hpp"
 #include "fiveeq_metrics.hpp"
+#include "fiveeq_smooth.hpp"
 #include "fiveeq_joint.hpp"
 #include "fiveeq_diag.hpp"
 #include "fiveeq_score.hpp"

@@ -1078,6 +1078,45 @@ class EnsembleEngine(CheckpointMixin):
         with torch.cuda.device(self.device):
             return trajectory_metrics(rows, self.out_steps, levels=levels, windows=windows, state=state)
 
+    def _rows_to_smooth(self, what, scenario, gas, rows=None):
+        """(rows, steps) of the stored T rows — or of gas `gas`'s stored C rows — for running_mean / window_trends."""
+        if self.T is None or self.n_rows == 0:
+            raise RuntimeError(f"no stored T rows: {what} needs output_steps")
+        if gas is not None:
+            if self.C is None or self.concentration_driven:
+                raise RuntimeError(f"no stored C rows: {what} of a gas needs stored concentrations")
+            if isinstance(gas, bool) or not isinstance(gas, (int, np.integer)) or not 0 <= int(gas) < self.n_gas:
+                raise ValueError(f"gas {gas!r}: the parameter set has gases 0..{self.n_gas - 1}")
+        sel = _stored_rows_slice(rows)
+        _joined(self)
+        stored = self.T if gas is None else self.C
+        if self.scenario_axis and scenario is not None:
+            stored = stored[self._scen(scenario)]
+        stored = stored[..., sel, :] if gas is None else stored[..., sel, int(gas), :]
+        return stored, self.out_steps[sel]
+
+    def running_mean(self, window, align="centre", scenario=None, rows=None, gas=None):
+        """The running mean over `window` consecutive stored T rows (gas=g: that gas's stored C rows), per member —
+        smooth.running_mean over the stored rows and self.out_steps, which must be evenly spaced: one streaming HIP pass, every
+        output summed afresh from its own rows.  rows: a slice of the stored rows (default: all).  With the scenario axis,
+        scenario=None covers all scenarios in one launch and the result carries a leading [S] axis.  Returns
+        smooth.SmoothedRows: `sm.rows, sm.steps` go where stored rows go — trajectory_metrics(sm.rows, sm.steps, levels=...)
+        dates a warming level by the mean, not by the first warm year.  Only reads the engine."""
+        from .smooth import running_mean
+        stored, steps = self._rows_to_smooth("running_mean", scenario, gas, rows)
+        with torch.cuda.device(self.device):
+            return running_mean(stored, steps, window, align=align)
+
+    def window_trends(self, windows, scenario=None, gas=None):
+        """Least-squares linear trends of the stored T rows (gas=g: that gas's stored C rows) over up to 4 step windows
+        [a, b), per member — smooth.window_trends over the stored rows, self.out_steps and the run's dt: slope in units per
+        year, mean, and the sums they come from.  With the scenario axis, scenario=None covers all scenarios in one launch.
+        Returns smooth.WindowTrends.  Only reads the engine."""
+        from .smooth import window_trends
+        stored, steps = self._rows_to_smooth("window_trends", scenario, gas)
+        with torch.cuda.device(self.device):
+            return window_trends(stored, steps, windows, dt=self.dt)
+
     def score(self, records, scenario=None):
         """Score the STORED rows against observed records (constrain.score_rows; include/fiveeq.h, "SCORING STORED ROWS").
         records: {"T": Observations, gas index: Observations, ...} — a record of warming against the stored T rows, a record of

@@ -826,6 +826,71 @@ int fiveeq_traj_metrics_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, i
                             int32_t n_windows, const int32_t *windows, double *fmet, int32_t *imet, int32_t first_call,
                             void *stream);
 
+/* new — RUNNING MEANS AND TRENDS: the two noise-robust reductions of a member's stored rows — the running mean over `window`
+ * consecutive rows (a warming level is the first 20-year MEAN at or above it, not the first warm year of a member with
+ * internal variability) and, per step window, the sums a least-squares trend is formed from — DESIGN.md section 3.22; host
+ * side: fiveeqscm_amd/smooth.py, EnsembleEngine.running_mean / window_trends.  Additive: no symbol above changes,
+ * FIVEEQ_ABI_VERSION stays 13.
+ *
+ * Both are streaming passes over rows dev [n_scen][n_rows][ld] (scenario blocks scen_stride elements apart; with n_scen == 1
+ * no scenario stride is used), per member and scenario, every value widened exactly to fp64.
+ *
+ * (a) RUNNING MEAN.  tail dev [n_scen][n_tail][ld] (blocks tail_scen_stride apart), 0 <= n_tail <= window - 1: the rows that
+ * precede row 0, kept from an earlier call; tail and rows are ONE sequence x[0 .. n_tail + n_rows).  out dev
+ * [n_scen][n_out][ld] fp64 (blocks out_scen_stride apart), n_out = max(0, n_tail + n_rows - window + 1); ONE ld for rows, tail
+ * and out.  1 <= window <= fiveeq_max_smooth_window() (FIVEEQ_MAX_SMOOTH_WINDOW).
+ * DEFINITION, operation for operation, for every k in [0, n_out):
+ *     s = (double) x[k]                                    exact
+ *     for i = 1 .. window - 1:  s = s + (double) x[k + i]  one rounded fp64 add each, ASCENDING row order
+ *     out[k] = s / (double) window                         one correctly rounded IEEE division (no reciprocal multiply)
+ * Every output is summed afresh from its own `window` rows in a fixed order — there is no sliding add / subtract update —
+ * so launch shape, row split (through tail) and member split cannot change a bit: rows [0, k) in one call and rows [k, n)
+ * with tail = the last min(window - 1, k) rows in a second give, concatenated, the bits of one call.  A NaN row makes exactly
+ * the `window` outputs that contain it NaN, for that member only; window == 1 returns the rows widened.  n_out == 0:
+ * nothing is launched.  Columns [n_members, ld) of out are never written.
+ *
+ * (b) WINDOW TREND SUMS.  steps dev [n_rows] int32: entry k is the model step row k holds.  windows HOST [n_windows][2] int32 =
+ * [a_w, b_w), 0 <= n_windows <= fiveeq_max_windows(); copied by the call.  The state of member m of scenario s:
+ *     tsum dev [n_scen][2 n_windows][ld] fp64:      (sx[w], stx[w]) per window, scenario blocks 2 n_windows ld apart
+ * DEFINITION.  For every row k in row order, t = steps[k], Tw the value widened, for each window w with a_w <= t < b_w:
+ *     u      = (double) (t - a_w)                          exact
+ *     sx[w]  = sx[w] + Tw                                  one rounded add
+ *     stx[w] = stx[w] + (u * Tw)                           the product rounded, THEN the add rounded: no fused multiply-add
+ * NaN propagates.  first_call != 0: the call starts from 0 and does NOT read tsum; first_call == 0: it continues the state it
+ * is handed; rows [0, k) in one call and rows [k, n) in the next give the bits of one call.  n_rows == 0 with first_call: the
+ * state is zeroed; without: nothing is done; n_windows == 0: nothing is done.  Columns [n_members, ld) of tsum are never
+ * written.  The least-squares slope over window w, with n, su = sum u and suu = sum u^2 over the stored steps inside it
+ * (integers the caller knows): (n stx - su sx) / (n suu - su^2) per step.
+ * THE CALLER OWES: (a) rows evenly spaced in time, in time order, tail the rows directly before them (a mean over unevenly
+ * stored rows is not a mean over time; fiveeqscm_amd/smooth.py checks the steps); (b) steps in row order across the calls of
+ * one state.
+ * FIVEEQ_E_INVALID, before anything is launched, for: n_scen outside 1..fiveeq_max_scenarios(); n_rows < 0; n_members < 1 or
+ * >= 2^31; ld < n_members; with n_scen > 1 scen_stride < n_rows * ld, tail_scen_stride < n_tail * ld or out_scen_stride <
+ * n_out * ld; window outside 1..FIVEEQ_MAX_SMOOTH_WINDOW; n_tail outside 0..window - 1; n_windows outside
+ * 0..FIVEEQ_MAX_WINDOWS; a window with a > b or a < 0; a NULL pointer that is needed (rows / steps are not with n_rows == 0,
+ * tail with n_tail == 0, out with n_out == 0, windows / tsum with n_windows == 0); a pointer not aligned to its element (rows,
+ * tail; steps 4; out, tsum 8).  Rows, tail and out aligned to 16 bytes with ld (and the scenario strides) a multiple of 16
+ * bytes get 16-byte accesses — an optimisation, not a contract. */
+#define FIVEEQ_MAX_SMOOTH_WINDOW 32
+int32_t fiveeq_max_smooth_window(void);
+/* the kernels' shape, for tests that pick their sizes at its edges: members per workgroup of the running mean for rows of
+ * elem_bytes (8 or 4; 0 for anything else), and the rows whose loads both row loops issue before they use the first
+ * (wide != 0: the 16-byte loads; 0: the element loads) */
+int32_t fiveeq_smooth_tile(int32_t elem_bytes);
+int32_t fiveeq_smooth_unroll(int32_t wide);
+int fiveeq_running_mean_f64(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const double *rows,
+                            int64_t scen_stride, int32_t window, int32_t n_tail, const double *tail, int64_t tail_scen_stride,
+                            double *out, int64_t out_scen_stride, void *stream);
+int fiveeq_running_mean_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const float *rows,
+                            int64_t scen_stride, int32_t window, int32_t n_tail, const float *tail, int64_t tail_scen_stride,
+                            double *out, int64_t out_scen_stride, void *stream);
+int fiveeq_window_trends_f64(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const double *rows,
+                             int64_t scen_stride, const int32_t *steps, int32_t n_windows, const int32_t *windows, double *tsum,
+                             int32_t first_call, void *stream);
+int fiveeq_window_trends_f32(int32_t n_scen, int32_t n_rows, int64_t n_members, int64_t ld, const float *rows,
+                             int64_t scen_stride, const int32_t *steps, int32_t n_windows, const int32_t *windows, double *tsum,
+                             int32_t first_call, void *stream);
+
 /* new — JOINT STATISTICS: co-moments and conditional sums of per-member rows, for covariances, correlations, regression slopes
  * and first-order variance-based sensitivity indices of outputs against parameters, under the integer weights of WEIGHTED
  * SUMMARY — DESIGN.md section 3.14; host side: fiveeqscm_amd/joint.py, EnsembleEngine.drivers.  Additive: no symbol above
