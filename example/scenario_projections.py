@@ -34,8 +34,11 @@ members and once under the posterior the run uses (weights, accepted, or the res
 (EnsembleEngine.running_mean, dated at the window's centre) instead of on single rows — what a warming level means once
 members carry internal variability.
 
+--carbon prints, per scenario at the last stored step, the percentiles of the CO2 airborne fraction and of the CH4 lifetime
+scaling alpha (EnsembleEngine.carbon_rows on one-row blocks of the stored rows; weighted where weights are in use).
+
     python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights] [--resample M] [--drivers]
-                                           [--metrics LEVELS [--smooth W]]
+                                           [--metrics LEVELS [--smooth W]] [--carbon]
 """
 import argparse
 import os
@@ -67,6 +70,9 @@ def main():
                     "over W stored rows (dated at the window's centre) instead of on single rows")
     ap.add_argument("--forcing-rows", action="store_true", help="also print, per scenario, the percentiles of the forcing F and the "
                     "energy imbalance N at the last summary year (diagnosed from the stored rows: the projection then stores C too)")
+    ap.add_argument("--carbon", action="store_true", help="also print, per scenario, the percentiles of the CO2 airborne fraction and "
+                    "of the CH4 lifetime scaling alpha at the last summary year (diagnosed from the stored rows: the projection then "
+                    "stores C too)")
     ap.add_argument("--drivers", action="store_true", help="rank the parameters by the share of the spread of T they explain")
     a = ap.parse_args()
     n_steps, N = 750, a.members
@@ -101,7 +107,7 @@ def main():
             else constrain.resample(keep, a.resample, seed=constrain.ACCEPT_SEED)
         (p_proj, R0, S0), n_proj, how = hist.resampled(plan), plan.n_members, {}
         print(f"resampled {N} members into {n_proj} equal-weight ones ({int(torch.unique(plan.src).numel())} distinct sources)")
-    proj = EnsembleEngine(p_proj, n_proj, E_s, R0=R0, S0=S0, output_steps=out_steps, store_concentrations=a.forcing_rows,
+    proj = EnsembleEngine(p_proj, n_proj, E_s, R0=R0, S0=S0, output_steps=out_steps, store_concentrations=a.forcing_rows or a.carbon,
                           scenario_names=list(SCENARIOS), forcing=sf, device="cuda:0")
     proj.run(t_branch, n_steps, mode="auto")
     pct = (5.0, 50.0, 95.0)
@@ -157,6 +163,20 @@ def main():
                 else:
                     q = gather_summary(row[:, how["accepted"]].contiguous() if "accepted" in how else row, pct)["percentiles"][0].tolist()
                 print(f"  {name:5s} {what}({int(run_years[-1])}) 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} {unit}")
+    if a.carbon:
+        from fiveeqscm_amd.distributed import gather_summary, gather_weighted_summary
+        last = slice(proj.n_rows - 1, proj.n_rows)              # one-row blocks of the last stored step; nothing is carried
+        af = proj.carbon_rows(want=("fraction",), gases=(0,), rows=last).fraction
+        al = proj.carbon_rows(want=("alpha",), gases=(1,), rows=last).alpha
+        w = how.get("weights")
+        for s, name in enumerate(proj.scenario_names):
+            for what, rows in (("CO2 airborne fraction", af[s, :, 0]), ("CH4 alpha", al[s, :, 0])):
+                row = rows.contiguous()
+                if w is not None:
+                    q = gather_weighted_summary(row, w, pct)["percentiles"][0].tolist()
+                else:
+                    q = gather_summary(row[:, how["accepted"]].contiguous() if "accepted" in how else row, pct)["percentiles"][0].tolist()
+                print(f"  {name:5s} {what}({int(run_years[-1])}) 5/50/95 %: {q[0]:.4f} / {q[1]:.4f} / {q[2]:.4f}")
     if a.drivers:
         names = proj.parameter_rows()[0]
         peak = proj.trajectory_metrics().peak

@@ -131,6 +131,9 @@ _RUNS = {
 # fiveeq_forcing_rows_*: (model, n_rows, n_members, ld, C_rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive,
 # n_steps, q, fscale, n_fext, fext, F, F_gas, N, H, ld_out, H_io, S_io, n_mismatch, stream)
 _FORCROWS = [_mp, _i32, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]
+# fiveeq_carbon_rows_*: (model, n_rows, n_members, ld, rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive, cum_end,
+# n_steps, r, conc_mask, gas_mask, airborne, cumE, uptake, fraction, iirf, alpha, sink, ld_out, cum_io, ga_io, stream)
+_CARBON = [_mp, _i32, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p]
 # fiveeq_pulse_response_*: (model, n_scen, n_rows, n_members, ld, C_rows, c_scen_stride, c_row_stride, c_gas_stride, T_rows,
 # t_scen_stride, t_row_stride, steps, drive, n_steps, fscale, n_fext, fext, base, n_pulses, pulse_scen, pulse_gas, n_horizons,
 # horizons, row0, out, ld_out, io, stream); pulse_scen, pulse_gas and horizons are HOST arrays of int32
@@ -223,6 +226,11 @@ SIGNATURES = {
     "fiveeq_forcing_rows_tile": (_i32, [_i32]),
     "fiveeq_forcing_rows_f64": (ctypes.c_int, _FORCROWS),
     "fiveeq_forcing_rows_f32": (ctypes.c_int, _FORCROWS),
+    "fiveeq_carbon_rows_tile": (_i32, [_i32]),
+    "fiveeq_carbon_rows_unroll": (_i32, [_i32, _i32]),
+    "fiveeq_carbon_rows_yrows": (_i32, []),
+    "fiveeq_carbon_rows_f64": (ctypes.c_int, _CARBON),
+    "fiveeq_carbon_rows_f32": (ctypes.c_int, _CARBON),
     "fiveeq_max_pulses": (_i32, []),
     "fiveeq_max_horizons": (_i32, []),
     "fiveeq_pulse_response_f64": (ctypes.c_int, _PULSE),
@@ -243,7 +251,7 @@ SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
     "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp", "fiveeq_noise.hpp",
-    "fiveeq_smooth.hpp")) + (
+    "fiveeq_smooth.hpp", "fiveeq_carbon.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

@@ -2461,5 +2461,102 @@ int fiveeq_pulse_response_f32(const fiveeq_model* model, int32_t n_scen, int32_t
                                  t_scen_stride, t_row_stride, steps, drive, n_steps, fscale, n_fext, fext, base, n_pulses, pulse_scen,
                                  pulse_gas, n_horizons, horizons, row0, out, ld_out, io, stream);
 }
+// ---- airborne fraction, uptake, alpha and sinks from stored rows (kernel 16) --------------------------------------------------
+}  // extern "C"
+namespace {
+template <typename T>
+int carbon_rows(const fiveeq_model* model, int32_t n_rows, int64_t n, int64_t ld, const T* rows, int64_t c_row, int64_t c_gas, const T* Trows,
+                int64_t t_row, const int32_t* steps, const T* drive, const T* cum_end, int32_t n_steps, const T* r, int32_t conc_mask,
+                int32_t gas_mask, T* airborne, T* cumE, T* uptake, T* fraction, T* iirf, T* alpha, T* sink, int64_t ld_out, T* cum_io,
+                T* ga_io, void* stream) {
+    if (int rc = check_model(model)) return rc;
+    const int G = model->n_gas, all = (1 << G) - 1;
+    const bool outs = airborne || cumE || uptake || fraction || iirf || alpha || sink;
+    const bool want_alpha = iirf || alpha;
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (int rc = outs ? check_ld("ld_out", ld_out, n) : FIVEEQ_OK) return rc;
+    if (int rc = n_rows > 1 ? check_ld("c_row_stride", c_row, n) : FIVEEQ_OK) return rc;
+    if (int rc = G > 1 ? check_stride("c_gas_stride", c_gas, n) : FIVEEQ_OK) return rc;
+    if (int rc = Trows && n_rows > 1 ? check_ld("t_row_stride", t_row, n) : FIVEEQ_OK) return rc;
+    if (conc_mask < 0 || conc_mask > all) return fail(FIVEEQ_E_INVALID, "conc_mask=%d names a gas outside the model's %d", conc_mask, G);
+    if (gas_mask < 1 || gas_mask > all) return fail(FIVEEQ_E_INVALID, "gas_mask=%d: want at least one gas, and none outside the model's %d", gas_mask, G);
+    if (want_alpha && !Trows) return fail(FIVEEQ_E_INVALID, "iirf / alpha need T_rows: T_rows is NULL");
+    if (want_alpha && !r) return fail(FIVEEQ_E_INVALID, "iirf / alpha need the r rows: r is NULL");
+    if (sink && !ga_io) return fail(FIVEEQ_E_INVALID, "sink needs ga_io (G_a before the first row): ga_io is NULL");
+    if ((gas_mask & conc_mask) && (cumE || uptake || fraction || want_alpha) && !cum_io)
+        return fail(FIVEEQ_E_INVALID, "cumE, uptake, fraction, iirf and alpha of a concentration-driven gas need cum_io: cum_io is NULL");
+    if ((gas_mask & ~conc_mask) && (cumE || uptake || fraction || want_alpha) && !cum_end)
+        return fail(FIVEEQ_E_INVALID, "cumE, uptake, fraction, iirf and alpha of an emission-driven gas need cum_end: cum_end is NULL");
+    if (n_steps < 1) return fail(FIVEEQ_E_INVALID, "n_steps=%d must be >= 1", n_steps);
+    if (int rc = check_not_null({{"rows", rows, 1, n_rows > 0}, {"steps", steps, 4, n_rows > 0}, {"drive", drive}})) return rc;
+    const void* elem[] = {rows, Trows, drive, cum_end, r, airborne, cumE, uptake, fraction, iirf, alpha, sink, cum_io, ga_io};
+    for (const void* p : elem)
+        if (misaligned(p, sizeof(T))) return fail(FIVEEQ_E_INVALID, "a row pointer (%p) is not %d-byte aligned", p, (int)sizeof(T));
+    if (int rc = check_aligned({{"steps", steps, 4}})) return rc;
+    if (n_rows == 0) return FIVEEQ_OK;                         // no row: no output row, and the carried state stays what it is
+    const bool seq = cum_io || ga_io;
+    int n_sel = 0;
+    for (int g = 0; g < G; ++g) n_sel += gas_mask >> g & 1;
+    fiveeq::CarbonArgs<T> a;
+    a.n_gas = G, a.n_rows = n_rows, a.n = 0, a.n_steps = n_steps, a.conc_mask = conc_mask, a.gas_mask = gas_mask, a.n_sel = n_sel;
+    a.rows = rows, a.c_row = n_rows > 1 ? c_row : 0, a.c_gas = G > 1 ? c_gas : 0;
+    a.Trows = want_alpha ? Trows : nullptr, a.t_row = n_rows > 1 ? t_row : 0;         // the T rows are read only when something needs them
+    a.steps = steps, a.drive = drive, a.cum_end = cum_end, a.r = want_alpha ? r : nullptr, a.ld = ld;
+    T* const out[fiveeq::CARBON_N_OUT] = {airborne, cumE, uptake, fraction, iirf, alpha, sink};
+    bool wide = !misaligned(rows, 16) && !misaligned(a.Trows, 16) && a.c_row % PER16<T> == 0 && a.c_gas % PER16<T> == 0 &&
+                (!a.Trows || a.t_row % PER16<T> == 0) && (!outs || ld_out % PER16<T> == 0);
+    for (int o = 0; o < fiveeq::CARBON_N_OUT; ++o) a.out[o] = out[o], wide = wide && !misaligned(out[o], 16);
+    a.ld_out = ld_out, a.cum_io = cum_io, a.ga_io = ga_io;
+    const KModel<T> km = make_kmodel<T>(model);
+    const unsigned gy = seq ? 1u : (unsigned)((n_rows + fiveeq::CARBON_YROWS - 1) / fiveeq::CARBON_YROWS);
+    if (gy > 65535u) return fail(FIVEEQ_E_INVALID, "n_rows=%d too many for one row-parallel launch: at most %d", n_rows, 65535 * fiveeq::CARBON_YROWS);
+    launch_split(wide_members<T>(wide, n), n, [&](auto vec, int64_t m0, int64_t members) {
+        fiveeq::CarbonArgs<T> b = a;
+        b.n = (int)members;
+        b.rows += m0;
+        if (b.Trows) b.Trows += m0;
+        if (b.r) b.r += m0;
+        for (int o = 0; o < fiveeq::CARBON_N_OUT; ++o)
+            if (b.out[o]) b.out[o] += m0;
+        if (b.cum_io) b.cum_io += m0;
+        if (b.ga_io) b.ga_io += m0;
+        const dim3 grid((unsigned)((members + fiveeq::CARBON_TILE<T> - 1) / fiveeq::CARBON_TILE<T>), gy);
+        constexpr bool VEC = decltype(vec)::value;
+        if (seq) hipLaunchKernelGGL((fiveeq::carbon_rows_kernel<T, VEC, true>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
+        else hipLaunchKernelGGL((fiveeq::carbon_rows_kernel<T, VEC, false>), grid, dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, km, b);
+    });
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+}  // namespace
+extern "C" {
+int32_t fiveeq_carbon_rows_tile(int32_t elem_bytes) {
+    return elem_bytes == 8 ? fiveeq::CARBON_TILE<double> : elem_bytes == 4 ? fiveeq::CARBON_TILE<float> : 0;
+}
+int32_t fiveeq_carbon_rows_unroll(int32_t wide, int32_t seq) {
+    return wide ? (seq ? fiveeq::CARBON_UNROLL<true, true> : fiveeq::CARBON_UNROLL<true, false>)
+                : (seq ? fiveeq::CARBON_UNROLL<false, true> : fiveeq::CARBON_UNROLL<false, false>);
+}
+int32_t fiveeq_carbon_rows_yrows(void) { return fiveeq::CARBON_YROWS; }
+int fiveeq_carbon_rows_f64(const fiveeq_model* model, int32_t n_rows, int64_t n_members, int64_t ld, const double* rows, int64_t c_row_stride,
+                           int64_t c_gas_stride, const double* T_rows, int64_t t_row_stride, const int32_t* steps, const double* drive,
+                           const double* cum_end, int32_t n_steps, const double* r, int32_t conc_mask, int32_t gas_mask, double* airborne,
+                           double* cumE, double* uptake, double* fraction, double* iirf, double* alpha, double* sink, int64_t ld_out,
+                           double* cum_io, double* ga_io, void* stream) {
+    return carbon_rows<double>(model, n_rows, n_members, ld, rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive, cum_end,
+                               n_steps, r, conc_mask, gas_mask, airborne, cumE, uptake, fraction, iirf, alpha, sink, ld_out, cum_io, ga_io,
+                               stream);
+}
+int fiveeq_carbon_rows_f32(const fiveeq_model* model, int32_t n_rows, int64_t n_members, int64_t ld, const float* rows, int64_t c_row_stride,
+                           int64_t c_gas_stride, const float* T_rows, int64_t t_row_stride, const int32_t* steps, const float* drive,
+                           const float* cum_end, int32_t n_steps, const float* r, int32_t conc_mask, int32_t gas_mask, float* airborne,
+                           float* cumE, float* uptake, float* fraction, float* iirf, float* alpha, float* sink, int64_t ld_out,
+                           float* cum_io, float* ga_io, void* stream) {
+    return carbon_rows<float>(model, n_rows, n_members, ld, rows, c_row_stride, c_gas_stride, T_rows, t_row_stride, steps, drive, cum_end,
+                              n_steps, r, conc_mask, gas_mask, airborne, cumE, uptake, fraction, iirf, alpha, sink, ld_out, cum_io, ga_io,
+                              stream);
+}
 
 }  // extern "C"

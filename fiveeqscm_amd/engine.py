@@ -264,6 +264,9 @@ class EnsembleEngine(CheckpointMixin):
         if drive[..., G:3].any():
             raise ValueError("emissions carry more gases than the parameter set")
         self.n_steps = int(row_map.shape[0])
+        # the cumulative emissions at the END of each step, fp64 [(S,) n_steps, G] — what column 3 + g of step t + 1 holds, with
+        # the last step's: the shared table of carbon_rows() (the columns of concentration-driven gases are not used)
+        self._cum_end = np.cumsum(drive[..., :G] * float(dt), axis=-2)
         lead = (Sc,) if self.scenario_axis else ()          # the leading scenario axis of the state, rows and records
 
         dev, dt_ = self.device, dtype
@@ -1236,6 +1239,71 @@ class EnsembleEngine(CheckpointMixin):
                               else torch.stack([getattr(p, name) for p in parts]))
         return ForcingRows(stack("F"), stack("F_gas"), stack("N"), stack("H"), stack("S_end"),
                            [p.replay_mismatches for p in parts] if replay else None)
+
+    def carbon_rows(self, want=("fraction",), gases=None, rows=None, scenario=None):
+        """The carbon-cycle quantities of the STORED rows — carbon.carbon_rows wired to this engine's stored rows, T, out_steps,
+        r rows, the scenario's drive table and its cumulative emissions, the drive mask, dt and the initial pools
+        (include/fiveeq.h, "CARBON ROWS"): one streaming HIP pass.
+        want: any of "airborne" (G_a), "cumE", "uptake" (G_u), "fraction" (the airborne fraction G_a / cumE), "iirf", "alpha"
+        (the values the NEXT step uses: they are formed from the row's own C and T) and "sink" (E - dG_a / dt).  gases: the gas
+        indices to diagnose, increasing (default: all); axis 1 of every result.  rows: a slice of the stored rows (default: all).
+        With the scenario axis, scenario=None covers every scenario (one launch each) and the results carry a leading [S] axis;
+        an index covers that scenario.
+        A concentration-driven engine is served too: its rows hold the diagnosed emissions, its cumulative emissions are
+        carried per member with the stepping kernel's own fma — carbon_rows(want=("cumE",)).cumE[-1] of a run with every step
+        stored is `cumE`, bit for bit.
+        "sink" and the cumE / uptake / fraction / iirf / alpha of a concentration-driven gas carry state through the rows: they
+        need stored rows of consecutive steps FROM STEP 0 (ValueError otherwise: the engine does not keep G_a and the cumulative
+        emissions of a later step; carbon.carbon_rows takes them as cum0= / airborne0=).  G_a before the first row comes from
+        the initial pools (R0; 0 without).
+        Where the rows go: constrain.score_rows(res.sink[:, 0], steps, Observations...) against a carbon-budget record;
+        res.fraction[k:k + 1, 0] into gather_summary / gather_weighted_summary; any row into drivers().
+        ValueError without stored concentrations and for compensated=True.  Joins unjoined per-step streams first.  Reads the
+        engine; writes nothing into it.  Returns carbon.CarbonRows."""
+        from .carbon import _NEED_CUM, CarbonRows, carbon_rows
+        want = tuple(want)
+        self._need_stored_C("carbon_rows", "; the stored C rows are the rounded sums", "the pass reads the stored C rows")
+        G = self.n_gas
+        conc_mask = getattr(self, "conc_mask", (1 << G) - 1 if self.concentration_driven else 0)
+        conc = tuple(g for g in range(G) if conc_mask >> g & 1)
+        picked = range(G) if gases is None else gases
+        sel = _stored_rows_slice(rows)
+        steps = self.out_steps[sel]
+        carried = "sink" in want or (any(w in _NEED_CUM for w in want) and any(g in conc for g in picked))
+        if carried and steps.size and steps[0] != 0:
+            raise ValueError("carbon_rows: the sink flux and the cumulative emissions of a concentration-driven gas are carried "
+                             f"through the rows from the run's initial state: they need rows from step 0 (first row: step "
+                             f"{int(steps[0])}); carbon.carbon_rows takes the state of a later step as cum0= / airborne0=")
+        _joined(self)
+
+        def one(sc):
+            pick = (lambda t: t) if sc is None else (lambda t: t[sc])
+            ga0 = None
+            if "sink" in want:
+                ga0 = torch.zeros((G, self.n_members), dtype=self.dtype, device=self.device)
+                if self._R0 is not None:
+                    R0 = torch.from_numpy(np.ascontiguousarray(self._R0 if sc is None else self._R0[sc])).to(self.device, self.dtype)
+                    off = 0
+                    for g in range(G):
+                        total = R0[off]
+                        for i in range(1, self.pools[g]):
+                            total = total + R0[off + i]
+                        ga0[g] = total * torch.tensor(1.0 / float(self.model.gas[g].emis2conc), dtype=torch.float64).to(self.dtype)
+                        off += self.pools[g]
+            with torch.cuda.device(self.device):
+                return carbon_rows(pick(self.C)[sel], steps, self.params, r=self.r, drive=pick(self.drive), dt=self.dt,
+                                   T_rows=pick(self.T)[sel], concentration_gases=conc, gases=gases, want=want, airborne0=ga0,
+                                   cum_table=self._cum_end if sc is None else self._cum_end[sc])
+
+        if not self.scenario_axis:
+            return one(None)
+        if scenario is not None:
+            return one(self._scen(scenario))
+        parts = [one(s) for s in range(self.n_scenarios)]
+        stack = lambda name: (None if getattr(parts[0], name) is None                                    # noqa: E731
+                              else torch.stack([getattr(p, name) for p in parts]))
+        return CarbonRows(*(stack(name) for name in ("airborne", "cumE", "uptake", "fraction", "iirf", "alpha", "sink", "cum_end",
+                                                     "airborne_end")), gases=parts[0].gases)
 
     def pulse_response(self, experiment_or_pulses, horizons, base=0, rows=None):
         """Per-member emission metrics from this engine's stored rows — pulse.pulse_response wired to the engine's C, T,

@@ -1213,6 +1213,66 @@ int fiveeq_stream_copy_nt_f64(int64_t n, const double *src, double *dst, void *s
  * schedules (a stream that shares the caller's hardware queue costs the per-step form +12 %). */
 int fiveeq_busy(int64_t iterations, double *out, void *stream);
 
+/* new — CARBON ROWS: the airborne emissions G_a, the cumulative emissions, the cumulative uptake G_u, the airborne fraction, the
+ * iIRF100, the lifetime scaling alpha and the sink flux of a run, DIAGNOSED FROM ITS STORED ROWS, for runs of every mode, drive
+ * and precision — DESIGN.md section 3.23; host side: fiveeqscm_amd/carbon.py carbon_rows, EnsembleEngine.carbon_rows.  Additive:
+ * no symbol above changes, FIVEEQ_ABI_VERSION stays 13, fiveeq_sizeof_model() stays 448.
+ *
+ * ONE streaming pass.  The stored value of row k, gas g, member m is rows[k * c_row_stride + g * c_gas_stride + m] (the C rows
+ * [n_rows][G][ld] of a run — which hold the diagnosed EMISSIONS of a concentration-driven gas), the warming T_rows[k *
+ * t_row_stride + m].  steps dev [n_rows] int32: entry k is the model step row k holds.  drive dev [n_steps][8] as in the stepping
+ * entry points (E_g, or the target C_g of a concentration-driven gas, at [g]).  cum_end dev [n_steps][FIVEEQ_MAX_GAS]: the
+ * cumulative emissions at the END of each step — the host's fp64 cumsum(E dt), which is what column 3 + g of step t + 1 of the
+ * drive table holds, rounded to the precision of the entry point.  r dev [3 G][ld] (r0, rC, rT of gas 0, then gas 1, ...).
+ * conc_mask: bit g set = gas g was concentration-driven (MIXED DRIVE).  gas_mask: the gases to diagnose, n_sel of them; output
+ * (k, slot, m) is out[(k * n_sel + slot) * ld_out + m], slot counting the selected gases below g.
+ * DEFINITION.  For the rows in row order, t = steps[k], per selected gas and member, every operation rounded on its own in the
+ * rows' precision unless an fma is written:
+ *     emission-driven gas:        C_g = the stored row;  E = drive[t][g];  cumE = cum_end[t][g]
+ *     concentration-driven gas:   C_g = drive[t][g];  E = the stored row;  cum = fma(E, dt, cum);  cumE = cum    (the statement
+ *                                 of the stepping kernel: cum after the last row is the engine's cumE, bit for bit)
+ *     airborne = G_a = (C_g - C0) * (1 / emis2conc)
+ *     uptake   = G_u = cumE - G_a
+ *     fraction = G_a / cumE                                          IEEE division: 0/0 and x/0 as IEEE gives them
+ *     iirf     = min(fma(ra, G_a, fma(rT, T, fma(rC, G_u, r0))), iirf_max)       the statements of the stepping kernels;
+ *     alpha    = g0 exp(iirf / g1)                                   min is IEEE minNum: a NaN iIRF reads iirf_max
+ *     sink     = E - (G_a - G_a_prev) / dt                           IEEE division; G_a_prev: the row before, ga_io for the first
+ * T is the row's stored T, so iirf and alpha of the row of step t are what step t + 1 uses.  A NaN stored value makes that
+ * row's airborne, uptake, fraction and sink (and the next row's sink) NaN and its iirf / alpha those of iirf_max; cumE of an
+ * emission-driven gas is the shared table whatever the rows hold; a NaN stored E of a concentration-driven gas stays in cum.
+ * OUTPUTS, each nullable, [n_rows][n_sel][ld_out] in the rows' precision, written for columns [0, n_members) only.  CARRIED
+ * STATE, in / out and nullable: cum_io [G][ld] (cum of the concentration-driven gases before the first row; needed for their
+ * cumE, uptake, fraction, iirf, alpha) and ga_io [G][ld] (G_a before the first row; needed for sink); rows of unselected gases
+ * are neither read nor written.  Both take the rows as consecutive model steps: THE CALLER OWES that, and steps inside
+ * [0, n_steps) (carbon.carbon_rows checks; the kernel clamps a step into the tables and never reads outside them).
+ * CONSEQUENCES: rows [0, k) in one call and rows [k, n) in a second with cum_io / ga_io carried give the bits of one call; any
+ * member sub-range gives the bits of the whole; launch shape, strides and alignment cannot change a bit (rows and outputs
+ * aligned to 16 bytes with strides a multiple of 16 bytes get 16-byte accesses — an optimisation, not a contract).  Without
+ * cum_io and ga_io the rows are independent and are spread over the grid; with one of them a lane carries its members through
+ * all rows.  Nothing is allocated, nothing synchronises.  The T rows and r are read only for iirf or alpha.
+ * FIVEEQ_E_UNSUPPORTED for a pool layout outside fiveeq_layout_supported.  FIVEEQ_E_INVALID, before anything is launched and
+ * with fiveeq_last_error() naming the argument, for: an invalid model; n_rows < 0; n_members < 1 or >= 2^31; ld < n_members;
+ * ld_out < n_members with an output; c_row_stride < n_members with n_rows > 1; |c_gas_stride| < n_members with G > 1;
+ * t_row_stride < n_members with T_rows and n_rows > 1; a conc_mask or gas_mask naming a gas the model has not, an empty
+ * gas_mask; iirf or alpha without T_rows or r; sink without ga_io; cumE, uptake, fraction, iirf or alpha of a selected
+ * concentration-driven gas without cum_io, of a selected emission-driven gas without cum_end; n_steps < 1; a NULL rows, steps
+ * or drive (rows and steps may be NULL with n_rows == 0); a pointer not aligned to its element. */
+/* members per workgroup for rows of elem_bytes (8 or 4; 0 for anything else); rows in flight per lane (wide: 16-byte accesses,
+ * seq: with carried state); rows per workgroup of the row-parallel form — for tests that pick their sizes at these edges */
+int32_t fiveeq_carbon_rows_tile(int32_t elem_bytes);
+int32_t fiveeq_carbon_rows_unroll(int32_t wide, int32_t seq);
+int32_t fiveeq_carbon_rows_yrows(void);
+int fiveeq_carbon_rows_f64(const fiveeq_model *model, int32_t n_rows, int64_t n_members, int64_t ld, const double *rows,
+                           int64_t c_row_stride, int64_t c_gas_stride, const double *T_rows, int64_t t_row_stride,
+                           const int32_t *steps, const double *drive, const double *cum_end, int32_t n_steps, const double *r,
+                           int32_t conc_mask, int32_t gas_mask, double *airborne, double *cumE, double *uptake, double *fraction,
+                           double *iirf, double *alpha, double *sink, int64_t ld_out, double *cum_io, double *ga_io, void *stream);
+int fiveeq_carbon_rows_f32(const fiveeq_model *model, int32_t n_rows, int64_t n_members, int64_t ld, const float *rows,
+                           int64_t c_row_stride, int64_t c_gas_stride, const float *T_rows, int64_t t_row_stride,
+                           const int32_t *steps, const float *drive, const float *cum_end, int32_t n_steps, const float *r,
+                           int32_t conc_mask, int32_t gas_mask, float *airborne, float *cumE, float *uptake, float *fraction,
+                           float *iirf, float *alpha, float *sink, int64_t ld_out, float *cum_io, float *ga_io, void *stream);
+
 /* new — diagnostic: y[i] = f(x[i]) with one of the kernels' own fp64 math primitives, so tests can
  * pin each against a CPU libm to the ulp.  op: 0 expm1 (x <= 0), 1 exp, 2 log (x > 0, finite normal),
  * 3 sqrt (x > 0, finite normal), 4 reciprocal (x > 0, finite normal).  _f32 only: op + 8 evaluates the PACKED twin of
