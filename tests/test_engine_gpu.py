@@ -159,9 +159,11 @@ def test_hfc_conc_kernel_matches_reference_golden(gpu, golden_hfc):
         members = np.array([e0, 2.0 * e0, 0.0, -e0, 1.0])
         out = calculate_hfc_conc_ensemble(members, time).cpu().numpy()
         assert out.shape == (time.size, 5)
-        # device exp vs NumPy exp: <= 1-2 ulp on normals; absolute floor for the subnormal tail
-        np.testing.assert_allclose(out[:, 0], want, rtol=1e-15, atol=1e-300, err_msg=name)
-        np.testing.assert_allclose(out[:, 1], 2.0 * want, rtol=1e-15, atol=1e-300)
+        # device exp and NumPy's exp are each within 1 ulp of the exact value (measured 0.72 and 0.62 at worst,
+        # tests/test_first_kernels_gpu.py / _cpu.py), so they differ by at most one last place of exp(-t), 2.2e-16 relative; the
+        # two products round once each, 1.1e-16: 4.5e-16.  Below the normal range: one unit of 2^-1074 in exp(-t), times e0 exactly.
+        np.testing.assert_allclose(out[:, 0], want, rtol=4.5e-16, atol=abs(e0) * 5e-324, err_msg=name)
+        np.testing.assert_allclose(out[:, 1], 2.0 * want, rtol=4.5e-16, atol=2.0 * abs(e0) * 5e-324)
         assert np.all(out[:, 2] == 0.0)
         np.testing.assert_array_equal(out[:, 3], -out[:, 0])
     with pytest.raises(IndexError):
@@ -175,7 +177,8 @@ def test_hfc_conc_kernel_ragged_sizes(gpu):
         e0 = rng.normal(size=N) * 10
         time = rng.uniform(-2, 30, size=K)
         out = calculate_hfc_conc_ensemble(e0, time).cpu().numpy()
-        np.testing.assert_allclose(out, c_oracle.hfc_conc(e0, time), rtol=1e-15, atol=1e-300)
+        # as above, against glibc's exp; every result here is a normal number, so no absolute floor
+        np.testing.assert_allclose(out, c_oracle.hfc_conc(e0, time), rtol=4.5e-16, atol=0.0)
 
 
 def test_engine_bridge_to_reference_function(gpu, golden_hfc):

@@ -2,7 +2,8 @@
 the design of the multi-GPU runs.  CPU tests: the NumPy twin, the library's host
 entry point (same C++ functions the kernel runs), stratification, and shard invariance — a rank computes
 only its members and the union over any partition is the single-shard design bit for bit.  The kernel
-itself is compared with the NumPy twin in tests/test_engine_gpu.py."""
+itself is compared with the NumPy twin in tests/test_engine_gpu.py, and bit for bit with an independent statement of the
+design (tests/first_kernels_reference.py) at the edges of its Feistel domain in tests/test_first_kernels_gpu.py."""
 import ctypes
 
 import numpy as np
