@@ -5,7 +5,7 @@ The record is the synthetic one committed for the tests (tests/golden/obs_synthe
 tests/golden/make_obs_synthetic.py: one known member plus 0.1 K noise over 1900..2069).  Needs an MI355X.
 
     python example/constrained_ensemble.py [--members N] [--dtype f64|f32] [--forcing] [--co2-record] [--concentration-driven]
-                                           [--co2-emission-driven] [--variability SIGMA PHI]
+                                           [--co2-emission-driven] [--variability SIGMA PHI] [--minor-gases]
 
 --forcing adds forcing uncertainty (EnsembleEngine(forcing=), fiveeqscm_amd/forcing.py): an aerosol-like cooling scaled per
 member, and the accepted range of ECS with a shared and with a sampled scale.
@@ -23,6 +23,10 @@ cumulative CO2 emissions (the mean diagnosed cumE is used for CH4 and N2O only).
 --variability SIGMA PHI gives every member its own AR(1) forcing noise (standard deviation SIGMA W m-2, lag-1 autocorrelation
 PHI; forcing.ar1_noise_rows, EnsembleEngine(member_forcing=)), constrains with the in-loop misfit and prints the accepted
 fraction and the 5-95 % range of the final T with and without the variability.
+--minor-gases adds two SYNTHETIC constant-lifetime species (made-up lifetimes, efficiencies and emissions: no literature values)
+whose lifetime and radiative efficiency every member scales by its own factors, sampled on the same shard-computable design
+(minor_gases.minor_gas_rows, EnsembleEngine(member_forcing=)); with --variability their forcing is added onto the noise rows
+(into=), otherwise it runs alone.
 """
 import argparse
 import os
@@ -52,6 +56,8 @@ def main():
                     help="with --concentration-driven: keep CO2 emission-driven in the history (CH4 and N2O prescribed)")
     ap.add_argument("--variability", nargs=2, type=float, metavar=("SIGMA", "PHI"),
                     help="also give every member AR(1) forcing noise (W m-2, lag-1 autocorrelation) and constrain with it")
+    ap.add_argument("--minor-gases", action="store_true",
+                    help="also give every member two synthetic minor gases with its own lifetime and efficiency scales")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -82,8 +88,8 @@ def main():
         ap.error("--co2-emission-driven is an option of --concentration-driven")
     if a.concentration_driven:
         concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, sigma, co2_emission_driven=a.co2_emission_driven)
-    if a.variability:
-        internal_variability(p, N, n_steps, dtype, obs, run_years, *a.variability)
+    if a.variability or a.minor_gases:
+        internal_variability(p, N, n_steps, dtype, obs, run_years, *(a.variability or (None, None)), minor=a.minor_gases)
 
 
 def co2_record(p, N, n_steps, dtype, obs, run_years, years, truth=12345, sigma_ppm=1.0):
@@ -165,7 +171,25 @@ def concentration_driven_history(p, N, n_steps, dtype, run_years, years, T_obs, 
     proj.close()
 
 
-def internal_variability(p, N, n_steps, dtype, obs, run_years, sigma_f, phi):
+def synthetic_minor_gases(N, n_steps, dtype, into=None):
+    """--minor-gases: two synthetic species (lifetimes 14 and 230 yr, emissions ramping up from 1950 and levelling off; the
+    numbers are illustrations, not data) with a per-member lifetime scale in 0.8..1.2 and efficiency scale in 0.7..1.3 — two
+    more dimensions of the design, after the forcing scales' — as member_forcing rows, added onto `into` when given."""
+    from fiveeqscm_amd.minor_gases import minor_gas_rows
+    t = np.arange(n_steps, dtype=np.float64)
+    ramp = np.clip((t - 200.0) / 120.0, 0.0, 1.0)
+    E = np.stack([40.0 * ramp, 3.0 * ramp ** 2], 1)                       # kt / yr
+    scales = params.sample_forcing_scales(3, N, ranges=[(1.0, 1.0)] * 4 + [(0.8, 1.2), (0.7, 1.3)])[4:]
+    tau = np.array([14.0, 230.0])[:, None] * scales[0][None, :]
+    eff = np.array([0.16e-3, 0.57e-3])[:, None] * scales[1][None, :]      # W m-2 per ppt
+    out = minor_gas_rows(E, tau, [0.06, 0.04], eff, N, into=into, device="cuda:0", dtype=dtype)
+    print(f"minor gases: {out.species} synthetic species, lifetime x0.8..1.2 and efficiency x0.7..1.3 per member; forcing in "
+          f"{int(1750 + n_steps - 1)}: {float(out.rows[-1].min()):.3f} .. {float(out.rows[-1].max()):.3f} W m-2"
+          + (" (on top of the noise rows)" if into is not None else ""))
+    return out.rows
+
+
+def internal_variability(p, N, n_steps, dtype, obs, run_years, sigma_f, phi, minor=False):
     """--variability: the observed record contains year-to-year noise a deterministic member cannot produce, so the chi2
     charges every member for it and the posterior comes out too narrow.  With a stochastic forcing realisation per member
     (rows [n_steps, N]: n_steps N w bytes on the device, 3 GB for 1M fp32 members over 750 steps) the members carry such noise
@@ -173,8 +197,12 @@ def internal_variability(p, N, n_steps, dtype, obs, run_years, sigma_f, phi):
     from fiveeqscm_amd.forcing import ar1_noise_rows
     E = emissions.rcp_like_emissions(n_steps, 3)
     last = n_steps - 1
-    rows = ar1_noise_rows(N, n_steps, sigma_f, phi, device="cuda:0", dtype=dtype)
-    print(f"internal variability: AR(1) forcing noise, sigma {sigma_f} W m-2, phi {phi} ({rows.numel() * rows.element_size() / 1e6:.0f} MB of rows)")
+    rows = None
+    if sigma_f is not None:
+        rows = ar1_noise_rows(N, n_steps, sigma_f, phi, device="cuda:0", dtype=dtype)
+        print(f"internal variability: AR(1) forcing noise, sigma {sigma_f} W m-2, phi {phi} ({rows.numel() * rows.element_size() / 1e6:.0f} MB of rows)")
+    if minor:
+        rows = synthetic_minor_gases(N, n_steps, dtype, into=rows)
     for label, mf in (("without", None), ("with", rows)):
         eng = EnsembleEngine(p, N, E, dtype=dtype, observations=obs, member_forcing=mf, output_steps=[last],
                              store_concentrations=False, device="cuda:0")
@@ -185,7 +213,7 @@ def internal_variability(p, N, n_steps, dtype, obs, run_years, sigma_f, phi):
             q = eng.gather_summary([last], percentiles=(5.0, 95.0), accepted=keep)["percentiles"][0].tolist()
         else:
             q = [float("nan")] * 2
-        print(f"  {label:7s} variability (mode {eng.last_mode}): accepted {n_keep} of {N} ({n_keep / N:.4f}); "
+        print(f"  {label:7s} member forcing (mode {eng.last_mode}): accepted {n_keep} of {N} ({n_keep / N:.4f}); "
               f"T({int(run_years[last])}) 5-95 %: {q[0]:.3f} .. {q[1]:.3f} K")
         eng.close()
 

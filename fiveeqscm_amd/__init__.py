@@ -4,8 +4,9 @@ Hot path: Python host (torch-ROCm tensors) -> C ABI (include/fiveeq.h) -> one
 hand-written HIP kernel per timestep on gfx950.  No CPU fallback for the engine.
 """
 from .concentrations import calculate_hfc_conc  # noqa: F401  (reference-compatible, NumPy)
+from .minor_gases import minor_gas_rows, minor_gas_rows_host  # noqa: F401  (torch and the library only when the device form is called)
 
-__all__ = ["calculate_hfc_conc", "ConcentrationDrivenEngine", "MixedDriveEngine"]
+__all__ = ["calculate_hfc_conc", "ConcentrationDrivenEngine", "MixedDriveEngine", "minor_gas_rows", "minor_gas_rows_host"]
 __version__ = "0.1.0"
 
 

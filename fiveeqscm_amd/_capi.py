@@ -169,6 +169,9 @@ SIGNATURES = {
     # (seed, m0, n_members, ld, t_begin, t_end, phi, s, xi_state, rows, stream)
     "fiveeq_noise_rows_f64": (ctypes.c_int, [ctypes.c_uint64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "fiveeq_noise_rows_f32": (ctypes.c_int, [ctypes.c_uint64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
+    # (n_species, n_members, ld, n_rows, dt, c [host], emis, tau, eff, R, rows, accumulate, stream)
+    "fiveeq_minor_rows_f64": (ctypes.c_int, [_i32, _i64, _i64, _i32, ctypes.c_double, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "fiveeq_minor_rows_f32": (ctypes.c_int, [_i32, _i64, _i64, _i32, ctypes.c_double, _p, _p, _p, _p, _p, _p, _i32, _p]),
     "fiveeq_plan_launch": (ctypes.c_int, [_p, _p]),
     "fiveeq_plan_destroy": (ctypes.c_int, [_p]),
     "fiveeq_hfc_conc_f64": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, _p, _p]),
@@ -251,7 +254,7 @@ SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
     "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp", "fiveeq_noise.hpp",
-    "fiveeq_smooth.hpp", "fiveeq_carbon.hpp")) + (
+    "fiveeq_smooth.hpp", "fiveeq_carbon.hpp", "fiveeq_minor.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

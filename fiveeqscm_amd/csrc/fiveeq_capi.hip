@@ -1013,6 +1013,35 @@ int noise_rows(uint64_t seed, int64_t m0, int64_t n, int64_t ld, int32_t t_begin
     return FIVEEQ_OK;
 }
 
+// ---- per-member minor-gas forcing rows (minor_rows_kernel): every check, then one launch ----------------------------------
+template <typename T>
+int minor_rows(int32_t n_species, int64_t n, int64_t ld, int32_t n_rows, double dt, const double* c, const double* emis, const T* tau,
+               const T* eff, double* R, T* rows, int32_t accumulate, void* stream) {
+    if (n_species < 1 || n_species > FIVEEQ_MINOR_MAX)
+        return fail(FIVEEQ_E_INVALID, "n_species=%d outside 1..%d", n_species, FIVEEQ_MINOR_MAX);
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (!std::isfinite(dt) || !(dt > 0.0)) return fail(FIVEEQ_E_INVALID, "dt=%g must be finite and > 0", dt);
+    if (int rc = check_not_null({{"c", c}})) return rc;
+    MinorC cc = {};
+    for (int k = 0; k < n_species; ++k) {
+        if (!std::isfinite(c[k])) return fail(FIVEEQ_E_INVALID, "c[%d]=%g is not finite", k, c[k]);
+        cc.c[k] = c[k];
+    }
+    if (accumulate != 0 && accumulate != 1) return fail(FIVEEQ_E_INVALID, "accumulate=%d must be 0 or 1", accumulate);
+    if (int rc = check_not_null({{"emis", emis}, {"tau", tau}, {"eff", eff}, {"R", R}, {"rows", rows}})) return rc;
+    if (int rc = check_aligned({{"emis", emis, 8}, {"tau", tau, sizeof(T)}, {"eff", eff, sizeof(T)}, {"R", R, 8}, {"rows", rows, sizeof(T)}}))
+        return rc;
+    if (n_rows == 0) return FIVEEQ_OK;
+    unsigned blocks;
+    if (int rc = grid_blocks(n, FIVEEQ_BLOCK, blocks)) return rc;
+    hipLaunchKernelGGL((minor_rows_kernel<T>), dim3(blocks), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, (int)n_species, n, ld,
+                       (int)n_rows, dt, cc, emis, tau, eff, R, rows, (int)accumulate);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1419,6 +1448,16 @@ int fiveeq_plan_create_mforc_f32(const fiveeq_model* model, int64_t n_members, i
 int fiveeq_noise_rows_f32(uint64_t seed, int64_t m0, int64_t n_members, int64_t ld, int32_t t_begin, int32_t t_end, const float* phi,
                           const float* s, double* xi_state, float* rows, void* stream) {
     return noise_rows<float>(seed, m0, n_members, ld, t_begin, t_end, phi, s, xi_state, rows, stream);
+}
+int fiveeq_minor_rows_f64(int32_t n_species, int64_t n_members, int64_t ld, int32_t n_rows, double dt, const double* c,
+                          const double* emis, const double* tau, const double* eff, double* R, double* rows, int32_t accumulate,
+                          void* stream) {
+    return minor_rows<double>(n_species, n_members, ld, n_rows, dt, c, emis, tau, eff, R, rows, accumulate, stream);
+}
+int fiveeq_minor_rows_f32(int32_t n_species, int64_t n_members, int64_t ld, int32_t n_rows, double dt, const double* c,
+                          const double* emis, const float* tau, const float* eff, double* R, float* rows, int32_t accumulate,
+                          void* stream) {
+    return minor_rows<float>(n_species, n_members, ld, n_rows, dt, c, emis, tau, eff, R, rows, accumulate, stream);
 }
 int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     return fiveeq_layout_supported(n_gas, n_pools) && forcing_layout(layout_code(n_gas, n_pools)) ? 1 : 0;

@@ -197,8 +197,9 @@ class EnsembleEngine(CheckpointMixin):
         False keeps every load.  Pool layouts without the form ({4} and 4 + 1 + 1 have it) and the other families (scenario
         axis, observations=, forcing=, hist=) report the rows and run as before.
         member_forcing: a tensor [n_steps, N] on the engine's device and in its dtype — a forcing series of each member's OWN
-        that changes every step (include/fiveeq.h "MEMBER FORCING"): internal variability (forcing.ar1_noise_rows), or a
-        member's own aerosol or volcanic history.  Step t of member m opens its forcing F = F_ext[t] + member_forcing[t, m]
+        that changes every step (include/fiveeq.h "MEMBER FORCING"): internal variability (forcing.ar1_noise_rows), the
+        minor gases with each member's own lifetimes and radiative efficiencies (minor_gases.minor_gas_rows(...).rows; with
+        into= on top of noise rows), or a member's own aerosol or volcanic history.  Step t of member m opens its forcing F = F_ext[t] + member_forcing[t, m]
         (one add), then the category and gas terms of forcing= as above.  Alone (unit scales, no category) or with forcing=
         and / or observations=; modes 'per_step', 'graph', 'fused', 'ksteps' and 'auto' (never 'small'), the same bits in each;
         all-zero rows are the forcing= run bit for bit.  The rows are kept as given (not copied when contiguous), are read-only

@@ -406,6 +406,41 @@ int fiveeq_noise_rows_f64(uint64_t seed, int64_t m0, int64_t n_members, int64_t 
                           const double *phi, const double *s, double *xi_state, double *rows, void *stream);
 int fiveeq_noise_rows_f32(uint64_t seed, int64_t m0, int64_t n_members, int64_t ld, int32_t t_begin, int32_t t_end,
                           const float *phi, const float *s, double *xi_state, float *rows, void *stream);
+/* MINOR-GAS FORCING ROWS — per-member forcing of constant-lifetime species (HFCs, PFCs, SF6, ...) with each member's own
+ * lifetime and radiative efficiency (new; ADDITIVE: FIVEEQ_ABI_VERSION stays 13, sizeof(fiveeq_model) stays 448).  The second
+ * generator of member-forcing rows beside fiveeq_noise_rows_*: n_species <= 8 one-pool reservoirs without state dependence,
+ * advanced by the exact step R <- R + expm1(-dt / tau) (R - tau c E), their forcing summed into rows[t][m].
+ *   n_species                          1..8 species in this call
+ *   n_members, ld                      members of the shard, row length of tau, eff, R and rows
+ *   n_rows                             steps of the call, >= 0; 0 is a successful no-op after the checks
+ *   dt                                 step length (yr), finite and > 0
+ *   c      HOST [n_species] fp64       emis2conc (concentration units per emission unit), copied by value into the launch
+ *   emis   dev [n_rows][n_species] fp64   emissions of each step, shared by the members
+ *   tau    dev [n_species][ld]         kernel precision (widened exactly): each member's lifetime (yr), > 0
+ *   eff    dev [n_species][ld]         kernel precision (widened exactly): each member's radiative efficiency
+ *   R      dev [n_species][ld] fp64    in/out: the concentration above its baseline before the first step in, after the last out
+ *   rows   dev [n_rows][ld]            kernel precision
+ *   accumulate                         0: rows are written; 1: the forcing is added onto what the rows hold
+ * THE ARITHMETIC is fp64 whatever the kernel precision, each operation rounded on its own (no fma).  Once per call, for species
+ * k of member m:   x = -dt / tau_k (IEEE division);   em1 = expm1(x) by the library's own primitive — the value
+ * fiveeq_math_probe_f64(op = 0) returns for x;   a = tau_k * c_k.  Per step t, for k ascending:
+ *     u = a * emis[t][k];   v = R_k - u;   w = em1 * v;   R_k = R_k + w
+ * then, for k ascending from acc = accumulate ? (double)rows[t][m] : 0.0:
+ *     p = eff_k * R_k;   acc = acc + p          and   rows[t][m] = acc rounded once to the kernel precision.
+ * The bits depend on (tau, eff, c, emis, R, dt) only: not on the launch shape, ld, how the members are cut into shards or how
+ * the steps are cut into calls (R carries the state; em1 is recomputed from the same tau).  For fp64 rows, chained accumulate = 1
+ * calls over consecutive species groups equal one ordered sum over all species bit for bit; fp32 rows round once per call at
+ * the store, so a grouping is part of their definition (fiveeqscm_amd.minor_gases.minor_gas_rows: consecutive groups of 8).
+ * Columns [n_members, ld) of rows and R are not touched.  FIVEEQ_E_INVALID for n_species outside 1..8, n_members outside
+ * 1..2^31-1, n_members > ld, n_rows < 0, dt not finite or <= 0, a NULL c, a non-finite c[k], accumulate other than 0 or 1,
+ * NULL or misaligned pointers (in this order) — before anything is launched.  Host twin (bit-identical given the same em1):
+ * fiveeqscm_amd.minor_gases.minor_gas_rows_host. */
+int fiveeq_minor_rows_f64(int32_t n_species, int64_t n_members, int64_t ld, int32_t n_rows, double dt, const double *c,
+                          const double *emis, const double *tau, const double *eff, double *R, double *rows,
+                          int32_t accumulate, void *stream);
+int fiveeq_minor_rows_f32(int32_t n_species, int64_t n_members, int64_t ld, int32_t n_rows, double dt, const double *c,
+                          const double *emis, const float *tau, const float *eff, double *R, float *rows,
+                          int32_t accumulate, void *stream);
 /* FORCING SCALES UNDER THE SCENARIO AXIS (new; additive, FIVEEQ_ABI_VERSION stays 13): fiveeq_run_scen_* / fiveeq_plan_create_scen_*
  * with the forcing scales of fiveeq_run_forc_*.  The arguments of the scenario calls, then
  *   fscale dev [G + n_fext][ld]          SHARED by the scenarios, like r and q
