@@ -172,6 +172,9 @@ SIGNATURES = {
     # (n_species, n_members, ld, n_rows, dt, c [host], emis, tau, eff, R, rows, accumulate, stream)
     "fiveeq_minor_rows_f64": (ctypes.c_int, [_i32, _i64, _i64, _i32, ctypes.c_double, _p, _p, _p, _p, _p, _p, _i32, _p]),
     "fiveeq_minor_rows_f32": (ctypes.c_int, [_i32, _i64, _i64, _i32, ctypes.c_double, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    # (n_species, aci_mask, n_members, ld, n_rows, base [host], emis, ari, shape, beta, rows, accumulate, stream)
+    "fiveeq_aerosol_rows_f64": (ctypes.c_int, [_i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "fiveeq_aerosol_rows_f32": (ctypes.c_int, [_i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i32, _p]),
     "fiveeq_plan_launch": (ctypes.c_int, [_p, _p]),
     "fiveeq_plan_destroy": (ctypes.c_int, [_p]),
     "fiveeq_hfc_conc_f64": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, _p, _p]),
@@ -254,7 +257,7 @@ SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
     "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp", "fiveeq_noise.hpp",
-    "fiveeq_smooth.hpp", "fiveeq_carbon.hpp", "fiveeq_minor.hpp")) + (
+    "fiveeq_smooth.hpp", "fiveeq_carbon.hpp", "fiveeq_minor.hpp", "fiveeq_aerosol.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

@@ -1042,6 +1042,40 @@ int minor_rows(int32_t n_species, int64_t n, int64_t ld, int32_t n_rows, double 
     return FIVEEQ_OK;
 }
 
+// ---- per-member aerosol forcing rows (aerosol_rows_kernel): every check, then one launch ----------------------------------
+// shape and beta belong to the cloud term: required iff aci_mask != 0, never read without it.
+template <typename T>
+int aerosol_rows(int32_t n_species, int32_t aci_mask, int64_t n, int64_t ld, int32_t n_rows, const double* base, const double* emis,
+                 const T* ari, const T* shape, const T* beta, T* rows, int32_t accumulate, void* stream) {
+    if (n_species < 1 || n_species > FIVEEQ_AEROSOL_MAX)
+        return fail(FIVEEQ_E_INVALID, "n_species=%d outside 1..%d", n_species, FIVEEQ_AEROSOL_MAX);
+    if (aci_mask < 0 || (aci_mask >> n_species) != 0)
+        return fail(FIVEEQ_E_INVALID, "aci_mask=0x%x has a bit outside the %d species", (unsigned)aci_mask, n_species);
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (int rc = check_not_null({{"base", base}})) return rc;
+    AerosolBase bb = {};
+    for (int k = 0; k < n_species; ++k) {
+        if (!std::isfinite(base[k]) || base[k] < 0.0) return fail(FIVEEQ_E_INVALID, "base[%d]=%g must be finite and >= 0", k, base[k]);
+        bb.b[k] = base[k];
+    }
+    if (accumulate != 0 && accumulate != 1) return fail(FIVEEQ_E_INVALID, "accumulate=%d must be 0 or 1", accumulate);
+    const bool cloud = aci_mask != 0;
+    if (int rc = check_not_null({{"emis", emis}, {"ari", ari}, {"shape", shape, 1, cloud}, {"beta", beta, 1, cloud}, {"rows", rows}}))
+        return rc;
+    if (int rc = check_aligned({{"emis", emis, 8}, {"ari", ari, sizeof(T)}, {"shape", shape, sizeof(T)}, {"beta", beta, sizeof(T)},
+                                {"rows", rows, sizeof(T)}}))
+        return rc;
+    if (n_rows == 0) return FIVEEQ_OK;
+    unsigned blocks;
+    if (int rc = grid_blocks(n, FIVEEQ_BLOCK, blocks)) return rc;
+    hipLaunchKernelGGL((aerosol_rows_kernel<T>), dim3(blocks), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, (int)n_species, (int)aci_mask,
+                       n, ld, (int)n_rows, bb, emis, ari, shape, beta, rows, (int)accumulate);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1458,6 +1492,16 @@ int fiveeq_minor_rows_f32(int32_t n_species, int64_t n_members, int64_t ld, int3
                           const double* emis, const float* tau, const float* eff, double* R, float* rows, int32_t accumulate,
                           void* stream) {
     return minor_rows<float>(n_species, n_members, ld, n_rows, dt, c, emis, tau, eff, R, rows, accumulate, stream);
+}
+int fiveeq_aerosol_rows_f64(int32_t n_species, int32_t aci_mask, int64_t n_members, int64_t ld, int32_t n_rows, const double* base,
+                            const double* emis, const double* ari, const double* shape, const double* beta, double* rows,
+                            int32_t accumulate, void* stream) {
+    return aerosol_rows<double>(n_species, aci_mask, n_members, ld, n_rows, base, emis, ari, shape, beta, rows, accumulate, stream);
+}
+int fiveeq_aerosol_rows_f32(int32_t n_species, int32_t aci_mask, int64_t n_members, int64_t ld, int32_t n_rows, const double* base,
+                            const double* emis, const float* ari, const float* shape, const float* beta, float* rows,
+                            int32_t accumulate, void* stream) {
+    return aerosol_rows<float>(n_species, aci_mask, n_members, ld, n_rows, base, emis, ari, shape, beta, rows, accumulate, stream);
 }
 int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     return fiveeq_layout_supported(n_gas, n_pools) && forcing_layout(layout_code(n_gas, n_pools)) ? 1 : 0;

@@ -441,6 +441,52 @@ int fiveeq_minor_rows_f64(int32_t n_species, int64_t n_members, int64_t ld, int3
 int fiveeq_minor_rows_f32(int32_t n_species, int64_t n_members, int64_t ld, int32_t n_rows, double dt, const double *c,
                           const double *emis, const float *tau, const float *eff, double *R, float *rows,
                           int32_t accumulate, void *stream);
+/* AEROSOL FORCING ROWS — per-member aerosol forcing (ERFari + ERFaci) from a shared table of short-lived-forcer emissions (SO2,
+ * BC, OC, NH3, ...) with each member's own coefficients (new; ADDITIVE: FIVEEQ_ABI_VERSION stays 13, sizeof(fiveeq_model) stays
+ * 448).  The third generator of member-forcing rows beside fiveeq_noise_rows_* and fiveeq_minor_rows_*: a linear
+ * aerosol-radiation mix of n_species <= 8 species and one saturating aerosol-cloud term over the species of aci_mask,
+ *     rows[t][m] = sum_k ari_k (emis[t][k] - base_k) - beta (ln(1 + sum_mask emis[t][k] / s_k) - ln(1 + sum_mask base_k / s_k)).
+ *   n_species                          1..8 species in this call (the cloud term's sum cannot be split across calls)
+ *   aci_mask                           bit k set: species k enters the cloud term; no bit at or above n_species; 0: no cloud term
+ *   n_members, ld                      members of the shard, row length of ari, shape, beta and rows
+ *   n_rows                             steps of the call, >= 0; 0 is a successful no-op after the checks
+ *   base   HOST [n_species] fp64       reference (pre-industrial) emissions, finite and >= 0, copied by value into the launch
+ *   emis   dev [n_rows][n_species] fp64   emissions of each step, shared by the members, >= 0
+ *   ari    dev [n_species][ld]         kernel precision (widened exactly): each member's W m-2 per emission unit
+ *   shape  dev [n_species][ld]         kernel precision (widened exactly): each member's s_k in emission units, > 0 with a
+ *                                      finite reciprocal; read for the species of aci_mask only
+ *   beta   dev [ld]                    kernel precision (widened exactly): each member's cloud-term scale, W m-2
+ *   rows   dev [n_rows][ld]            kernel precision
+ *   accumulate                         0: rows are written; 1: the forcing is added onto what the rows hold
+ * With aci_mask == 0 shape and beta are not read and may be NULL.
+ * THE ARITHMETIC is fp64 whatever the kernel precision, each operation rounded on its own (no fma outside the logarithm).  Once
+ * per call, for member m:
+ *     for k ascending, bit k of aci_mask set:   g_k = 1.0 / s_k          (IEEE division)
+ *     x = 0.0;  for k ascending in the mask:    p = g_k * base_k;  x = x + p
+ *     y0 = 1.0 + x;   L0 = ln(y0) by the library's own primitive — the value fiveeq_math_probe_f64(op = 2) returns for y0.
+ * Per step t:
+ *     acc = accumulate ? (double)rows[t][m] : 0.0
+ *     for k ascending, k < n_species:           e = emis[t][k] - base_k;  p = ari_k * e;  acc = acc + p
+ *     if aci_mask != 0:
+ *         x = 0.0;  for k ascending in the mask: p = g_k * emis[t][k];  x = x + p
+ *         y = 1.0 + x;  L = ln(y) (the same primitive);  v = L - L0;  w = beta * v;  acc = acc - w
+ *     rows[t][m] = acc rounded once to the kernel precision.
+ * The bits depend on (emis, base, ari, shape, beta, aci_mask) only: not on the launch shape, ld, how the members are cut into
+ * shards or how the steps are cut into calls (there is no state to carry).  A step whose emissions equal base forms L by the
+ * operations that formed L0 and contributes exactly +0: a table equal to base at every step gives all-zero rows — by the
+ * contract of MEMBER FORCING the run without them, bit for bit.  Domain: emis >= 0, base >= 0, s > 0 with 1 / s finite, so that
+ * y >= 1 is finite and normal; the Python wrapper enforces it for emis and the device rows, the kernel does not guard it.
+ * Columns [n_members, ld) of rows are not touched.  FIVEEQ_E_INVALID for n_species outside 1..8, an aci_mask that is negative
+ * or has a bit at or above n_species, n_members outside 1..2^31-1, n_members > ld, n_rows < 0, a NULL base, a base[k] that is
+ * not finite or negative, accumulate other than 0 or 1, NULL or misaligned pointers (shape and beta required iff
+ * aci_mask != 0) — in this order, before anything is launched.  Host twin (bit-identical given the same logarithm):
+ * fiveeqscm_amd.aerosols.aerosol_rows_host. */
+int fiveeq_aerosol_rows_f64(int32_t n_species, int32_t aci_mask, int64_t n_members, int64_t ld, int32_t n_rows,
+                            const double *base, const double *emis, const double *ari, const double *shape,
+                            const double *beta, double *rows, int32_t accumulate, void *stream);
+int fiveeq_aerosol_rows_f32(int32_t n_species, int32_t aci_mask, int64_t n_members, int64_t ld, int32_t n_rows,
+                            const double *base, const double *emis, const float *ari, const float *shape,
+                            const float *beta, float *rows, int32_t accumulate, void *stream);
 /* FORCING SCALES UNDER THE SCENARIO AXIS (new; additive, FIVEEQ_ABI_VERSION stays 13): fiveeq_run_scen_* / fiveeq_plan_create_scen_*
  * with the forcing scales of fiveeq_run_forc_*.  The arguments of the scenario calls, then
  *   fscale dev [G + n_fext][ld]          SHARED by the scenarios, like r and q
