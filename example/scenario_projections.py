@@ -37,8 +37,13 @@ members carry internal variability.
 --carbon prints, per scenario at the last stored step, the percentiles of the CO2 airborne fraction and of the CH4 lifetime
 scaling alpha (EnsembleEngine.carbon_rows on one-row blocks of the stored rows; weighted where weights are in use).
 
+--sea-level prints, per scenario, the percentiles of the global-mean sea-level rise since the branch year at the last step and
+of the first year it reaches 0.5 m (EnsembleEngine.sea_level_rows into trajectory_metrics with a level in metres).  Sea-level
+rise integrates every year, so a second projection stores consecutive steps.  Its four components' priors are ILLUSTRATIVE,
+NOT A CALIBRATION.
+
     python example/scenario_projections.py [--members N] [--out FILE] [--forcing] [--weights] [--resample M] [--drivers]
-                                           [--metrics LEVELS [--smooth W]] [--carbon]
+                                           [--metrics LEVELS [--smooth W]] [--carbon] [--sea-level]
 """
 import argparse
 import os
@@ -74,6 +79,8 @@ def main():
                     "of the CH4 lifetime scaling alpha at the last summary year (diagnosed from the stored rows: the projection then "
                     "stores C too)")
     ap.add_argument("--drivers", action="store_true", help="rank the parameters by the share of the spread of T they explain")
+    ap.add_argument("--sea-level", action="store_true", help="also print, per scenario, the percentiles of the sea-level rise at the last "
+                    "step and of the year it first reaches 0.5 m (component priors illustrative, not a calibration)")
     a = ap.parse_args()
     n_steps, N = 750, a.members
     run_years = 1750.0 + np.arange(n_steps)
@@ -189,6 +196,45 @@ def main():
                 for k, what in enumerate((f"T({int(run_years[-1])})", "peak")):
                     top = torch.argsort(d.eta2[:, k].nan_to_num(-1.0), descending=True)[:5].tolist()
                     print(f"        {what:8s} " + ", ".join(f"{names[i]} {float(d.eta2[i, k]):.3f} (r {float(d.moments.corr[i, k]):+.2f})" for i in top))
+    if a.sea_level:
+        from fiveeqscm_amd import metrics
+        from fiveeqscm_amd.distributed import gather_summary, gather_weighted_summary
+        from fiveeqscm_amd.sea_level import SeaLevelComponents
+        # Sea-level rise integrates every year's warming, so it needs the stored rows of CONSECUTIVE steps: a second projection
+        # from the same branch state stores every step (the summary engine above stores every tenth).
+        # The component priors below are ILLUSTRATIVE, NOT A CALIBRATION: round numbers of the right order of magnitude, drawn
+        # independently per member, so that the example has a spread to print.  The levels are rises since the branch year.
+        sea = EnsembleEngine(p_proj, n_proj, E_s, R0=R0, S0=S0, output_steps=list(range(t_branch, n_steps)), store_concentrations=False,
+                             scenario_names=list(SCENARIOS), forcing=sf, device="cuda:0")
+        sea.run(t_branch, n_steps, mode="auto")
+        rng = np.random.default_rng(2016)
+        u = lambda lo, hi: rng.uniform(lo, hi, n_proj)                                   # noqa: E731
+        comp = SeaLevelComponents(
+            ("expansion", "glaciers", "greenland", "antarctica"), ("relax", "relax", "rate", "rate"),
+            tau=np.stack([u(150.0, 500.0), u(100.0, 300.0), np.ones(n_proj), np.ones(n_proj)]),              # years
+            a=np.stack([u(0.2, 0.6), u(0.15, 0.35), u(0.0004, 0.0016), u(0.0002, 0.0020)]),                  # m / K; m / yr / K
+            b=np.stack([np.zeros(n_proj), np.zeros(n_proj), u(0.0, 0.0004), u(0.0, 0.0006)]),
+            T0=np.stack([u(0.6, 1.0), u(0.4, 0.9), u(0.5, 1.0), u(0.7, 1.2)]),                               # K: in balance near today
+            cap=np.stack([np.full(n_proj, np.inf), u(0.30, 0.41), np.full(n_proj, np.inf), np.full(n_proj, np.inf)]))
+        sl = sea.sea_level_rows(comp)                              # all scenarios in one launch: total [S, n_rows, N] fp64
+        m = metrics.trajectory_metrics(sl.total, sl.steps, levels=(0.5,))
+        w = how.get("weights")
+        print(f"  sea-level rise since {int(run_years[t_branch])} (illustrative component priors, not a calibration):")
+        for s, name in enumerate(sea.scenario_names):
+            row = sl.total[s, -1:].contiguous()
+            if w is not None:
+                q = gather_weighted_summary(row, w, pct)["percentiles"][0].tolist()
+            else:
+                q = gather_summary(row[:, how["accepted"]].contiguous() if "accepted" in how else row, pct)["percentiles"][0].tolist()
+            print(f"  {name:5s} rise({int(run_years[-1])}) 5/50/95 %: {q[0]:.3f} / {q[1]:.3f} / {q[2]:.3f} m")
+            first = m.first[s] if "accepted" not in how else m.first[s][:, how["accepted"]]
+            (crossed, total), = metrics.exceedance(first, weights=w)
+            line = f"        P(rise >= 0.5 m) = {crossed / total:.4f}"
+            if crossed:
+                c = metrics.crossing_summary(first[0], run_years, pct, weights=w)["percentiles"][0].tolist()
+                line += f"; first year at or above, among those that cross, 5/50/95 %: {c[0]:.0f} / {c[1]:.0f} / {c[2]:.0f}"
+            print(line)
+        sea.close()
     hist.close()
     proj.close()
 

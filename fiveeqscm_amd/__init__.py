@@ -6,9 +6,11 @@ hand-written HIP kernel per timestep on gfx950.  No CPU fallback for the engine.
 from .concentrations import calculate_hfc_conc  # noqa: F401  (reference-compatible, NumPy)
 from .minor_gases import minor_gas_rows, minor_gas_rows_host  # noqa: F401  (torch and the library only when the device form is called)
 from .aerosols import aerosol_rows, aerosol_rows_host, aci_scale_for_target, aci_scale_for_target_host  # noqa: F401  (likewise)
+from .sea_level import SeaLevelComponents, SeaLevelRows, sea_level_rows, sea_level_rows_host  # noqa: F401  (likewise)
 
 __all__ = ["calculate_hfc_conc", "ConcentrationDrivenEngine", "MixedDriveEngine", "minor_gas_rows", "minor_gas_rows_host",
-           "aerosol_rows", "aerosol_rows_host", "aci_scale_for_target", "aci_scale_for_target_host"]
+           "aerosol_rows", "aerosol_rows_host", "aci_scale_for_target", "aci_scale_for_target_host",
+           "SeaLevelComponents", "SeaLevelRows", "sea_level_rows", "sea_level_rows_host"]
 __version__ = "0.1.0"
 
 

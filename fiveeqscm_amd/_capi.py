@@ -175,6 +175,10 @@ SIGNATURES = {
     # (n_species, aci_mask, n_members, ld, n_rows, base [host], emis, ari, shape, beta, rows, accumulate, stream)
     "fiveeq_aerosol_rows_f64": (ctypes.c_int, [_i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i32, _p]),
     "fiveeq_aerosol_rows_f32": (ctypes.c_int, [_i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    # (n_scen, n_comp, rate_mask, n_members, ld, n_rows, dt, T_rows, t_row_stride, t_scen_stride, par, heat, h_row_stride,
+    # h_scen_stride, eta, S_io, total, comps, ld_out, stream)
+    **{f"fiveeq_sea_level_rows_{sfx}": (ctypes.c_int, [_i32, _i32, _i32, _i64, _i64, _i32, ctypes.c_double, _p, _i64, _i64, _p, _p, _i64,
+                                                       _i64, _p, _p, _p, _p, _i64, _p]) for sfx in ("f64", "f32")},
     "fiveeq_plan_launch": (ctypes.c_int, [_p, _p]),
     "fiveeq_plan_destroy": (ctypes.c_int, [_p]),
     "fiveeq_hfc_conc_f64": (ctypes.c_int, [_i64, _i64, _i32, _p, _p, _p, _p]),
@@ -257,7 +261,7 @@ SOURCES = tuple(os.path.join(_HERE, "csrc", name) for name in (
     "fiveeq_capi.hip", "fiveeq_device.hpp", "fiveeq_math.hpp", "fiveeq_stats.hpp", "fiveeq_member.hpp", "fiveeq_step.hpp",
     "fiveeq_fused.hpp", "fiveeq_small.hpp", "fiveeq_summary.hpp", "fiveeq_wsummary.hpp", "fiveeq_resample.hpp",
     "fiveeq_metrics.hpp", "fiveeq_joint.hpp", "fiveeq_diag.hpp", "fiveeq_score.hpp", "fiveeq_forcrows.hpp", "fiveeq_pulse.hpp", "fiveeq_noise.hpp",
-    "fiveeq_smooth.hpp", "fiveeq_carbon.hpp", "fiveeq_minor.hpp", "fiveeq_aerosol.hpp")) + (
+    "fiveeq_smooth.hpp", "fiveeq_carbon.hpp", "fiveeq_minor.hpp", "fiveeq_aerosol.hpp", "fiveeq_sea.hpp")) + (
     os.path.join(os.path.dirname(_HERE), "include", "fiveeq.h"),)
 
 

@@ -1076,6 +1076,45 @@ int aerosol_rows(int32_t n_species, int32_t aci_mask, int64_t n, int64_t ld, int
     return FIVEEQ_OK;
 }
 
+// ---- per-member sea-level rows (sea_level_rows_kernel): every check, then one launch over (members, scenarios) ------------
+// heat and eta belong to the thermosteric term: eta is required iff heat is given, never read without it.
+template <typename T>
+int sea_level_rows(int32_t n_scen, int32_t n_comp, int32_t rate_mask, int64_t n, int64_t ld, int32_t n_rows, double dt, const T* T_rows,
+                   int64_t t_row, int64_t t_scen, const double* par, const double* heat, int64_t h_row, int64_t h_scen,
+                   const double* eta, double* S_io, double* total, double* comps, int64_t ld_out, void* stream) {
+    if (int rc = check_scen(n_scen)) return rc;
+    if (n_comp < 1 || n_comp > FIVEEQ_SEA_MAX) return fail(FIVEEQ_E_INVALID, "n_comp=%d outside 1..%d", n_comp, FIVEEQ_SEA_MAX);
+    if (rate_mask < 0 || (rate_mask >> n_comp) != 0)
+        return fail(FIVEEQ_E_INVALID, "rate_mask=0x%x has a bit outside the %d components", (unsigned)rate_mask, n_comp);
+    if (int rc = check_members(n)) return rc;
+    if (int rc = check_ld("ld", ld, n)) return rc;
+    if (int rc = check_n_rows(n_rows)) return rc;
+    if (!std::isfinite(dt) || !(dt > 0.0)) return fail(FIVEEQ_E_INVALID, "dt=%g must be finite and > 0", dt);
+    const auto spans = [&](const char* name, int64_t stride) {       // a stride, or the outputs' row length, spans a row of ld
+        return stride < ld ? fail(FIVEEQ_E_INVALID, "%s=%lld < ld=%lld", name, (long long)stride, (long long)ld) : FIVEEQ_OK;
+    };
+    if (int rc = spans("t_row_stride", t_row)) return rc;
+    if (int rc = spans("t_scen_stride", t_scen)) return rc;
+    if (heat) {
+        if (int rc = spans("h_row_stride", h_row)) return rc;
+        if (int rc = spans("h_scen_stride", h_scen)) return rc;
+        if (!eta) return fail(FIVEEQ_E_INVALID, "heat without eta: eta is NULL");
+    }
+    if (int rc = check_ld("ld_out", ld_out, n)) return rc;
+    if (int rc = check_not_null({{"T_rows", T_rows}, {"par", par}, {"S_io", S_io}, {"total", total}})) return rc;
+    if (int rc = check_aligned({{"T_rows", T_rows, sizeof(T)}, {"par", par, 8}, {"heat", heat, 8}, {"eta", eta, 8}, {"S_io", S_io, 8},
+                                {"total", total, 8}, {"comps", comps, 8}}))
+        return rc;
+    if (n_rows == 0) return FIVEEQ_OK;
+    unsigned blocks;
+    if (int rc = grid_blocks(n, FIVEEQ_BLOCK, blocks)) return rc;
+    hipLaunchKernelGGL((sea_level_rows_kernel<T>), dim3(blocks, (unsigned)n_scen), dim3(FIVEEQ_BLOCK), 0, (hipStream_t)stream, (int)n_comp,
+                       (int)rate_mask, n, ld, (int)n_rows, dt, T_rows, t_row, t_scen, par, heat, h_row, h_scen, heat ? eta : nullptr, S_io,
+                       total, comps, ld_out);
+    HIP_TRY(hipGetLastError());
+    return FIVEEQ_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1502,6 +1541,20 @@ int fiveeq_aerosol_rows_f32(int32_t n_species, int32_t aci_mask, int64_t n_membe
                             const double* emis, const float* ari, const float* shape, const float* beta, float* rows,
                             int32_t accumulate, void* stream) {
     return aerosol_rows<float>(n_species, aci_mask, n_members, ld, n_rows, base, emis, ari, shape, beta, rows, accumulate, stream);
+}
+int fiveeq_sea_level_rows_f64(int32_t n_scen, int32_t n_comp, int32_t rate_mask, int64_t n_members, int64_t ld, int32_t n_rows, double dt,
+                              const double* T_rows, int64_t t_row_stride, int64_t t_scen_stride, const double* par, const double* heat,
+                              int64_t h_row_stride, int64_t h_scen_stride, const double* eta, double* S_io, double* total, double* comps,
+                              int64_t ld_out, void* stream) {
+    return sea_level_rows<double>(n_scen, n_comp, rate_mask, n_members, ld, n_rows, dt, T_rows, t_row_stride, t_scen_stride, par, heat,
+                                  h_row_stride, h_scen_stride, eta, S_io, total, comps, ld_out, stream);
+}
+int fiveeq_sea_level_rows_f32(int32_t n_scen, int32_t n_comp, int32_t rate_mask, int64_t n_members, int64_t ld, int32_t n_rows, double dt,
+                              const float* T_rows, int64_t t_row_stride, int64_t t_scen_stride, const double* par, const double* heat,
+                              int64_t h_row_stride, int64_t h_scen_stride, const double* eta, double* S_io, double* total, double* comps,
+                              int64_t ld_out, void* stream) {
+    return sea_level_rows<float>(n_scen, n_comp, rate_mask, n_members, ld, n_rows, dt, T_rows, t_row_stride, t_scen_stride, par, heat,
+                                 h_row_stride, h_scen_stride, eta, S_io, total, comps, ld_out, stream);
 }
 int fiveeq_forcing_layout_supported(int32_t n_gas, const int32_t* n_pools) {
     return fiveeq_layout_supported(n_gas, n_pools) && forcing_layout(layout_code(n_gas, n_pools)) ? 1 : 0;

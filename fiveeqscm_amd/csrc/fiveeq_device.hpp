@@ -33,6 +33,7 @@
 //   fiveeq_carbon.hpp   16 carbon_rows_kernel   airborne emissions, cumulative emissions and uptake, airborne fraction, iIRF, alpha and sink from stored rows
 //   fiveeq_minor.hpp    17 minor_rows_kernel    per-member forcing rows of constant-lifetime minor gases, each member's own lifetime and efficiency
 //   fiveeq_aerosol.hpp  18 aerosol_rows_kernel  per-member aerosol forcing rows (ERFari + ERFaci) from shared emissions, each member's own coefficients
+//   fiveeq_sea.hpp      19 sea_level_rows_kernel per-member sea-level rise rows from stored T rows (and heat-uptake rows), each member's own components
 // and what they share: fiveeq_math.hpp (the model struct, lane types, fe_* math), fiveeq_stats.hpp (per-wave statistics, the bin
 // rule), fiveeq_member.hpp (member_step(), gas_forcing(), the misfit update, the lane's member span and row access).
 // All model arithmetic is member_step(): every kernel that steps the model gives the same bits.
@@ -89,3 +90,4 @@ constexpr int DRIVE_STRIDE = 8;
 #include "fiveeq_carbon.hpp"
 #include "fiveeq_minor.hpp"
 #include "fiveeq_aerosol.hpp"
+#include "fiveeq_sea.hpp"

@@ -1241,6 +1241,33 @@ class EnsembleEngine(CheckpointMixin):
         return ForcingRows(stack("F"), stack("F_gas"), stack("N"), stack("H"), stack("S_end"),
                            [p.replay_mismatches for p in parts] if replay else None)
 
+    def sea_level_rows(self, components, expansion=None, want=("total",), rows=None, scenario=None, state=None):
+        """Each member's global-mean sea-level rise after every stored row — sea_level.sea_level_rows wired to this engine's
+        stored T rows, out_steps (consecutive steps, ValueError otherwise) and dt, for this shard's members: `components`
+        (a sea_level.SeaLevelComponents) gives its per-member rows over these n_members columns.  One streaming HIP pass, fp64.
+        expansion: each member's eta (a value or [N]): the thermosteric term eta H is added, H taken from
+        self.forcing_rows(want=("H",)) over the stored rows from the first one (so that a rows= slice sees the H of the whole
+        run) — that method's refusals stand: no stored concentrations, a concentration-driven or compensated run, and
+        member_forcing=, whose forcing is not recomputed; model the expansion of such runs as a relax component instead.
+        want: any of "total", "components".  rows: a slice of the stored rows (default: all).  With the scenario axis,
+        scenario=None covers all scenarios in one launch and the results carry a leading [S] axis; an index covers that
+        scenario.  state: the result of an earlier call over the rows directly before these, or S0 [.., J, N].
+        Reads the engine; writes nothing into it.  Returns sea_level.SeaLevelRows: `.total, .steps` go where stored rows go."""
+        from .sea_level import sea_level_rows
+        if self.T is None or self.n_rows == 0:
+            raise RuntimeError("no stored T rows: sea_level_rows needs output_steps")
+        sel = _stored_rows_slice(rows)
+        sc = self._scen(scenario) if self.scenario_axis and scenario is not None else None
+        heat = None
+        if expansion is not None:
+            start, stop, _ = sel.indices(self.n_rows)
+            heat = self.forcing_rows(want=("H",), rows=slice(0, stop), scenario=sc).H[..., start:, :]
+        _joined(self)
+        T = self.T if sc is None else self.T[sc]
+        with torch.cuda.device(self.device):
+            return sea_level_rows(T[..., sel, :], self.out_steps[sel], components, dt=self.dt, heat=heat, expansion=expansion,
+                                  state=state, want=want)
+
     def carbon_rows(self, want=("fraction",), gases=None, rows=None, scenario=None):
         """The carbon-cycle quantities of the STORED rows — carbon.carbon_rows wired to this engine's stored rows, T, out_steps,
         r rows, the scenario's drive table and its cumulative emissions, the drive mask, dt and the initial pools

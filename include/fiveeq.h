@@ -487,6 +487,55 @@ int fiveeq_aerosol_rows_f64(int32_t n_species, int32_t aci_mask, int64_t n_membe
 int fiveeq_aerosol_rows_f32(int32_t n_species, int32_t aci_mask, int64_t n_members, int64_t ld, int32_t n_rows,
                             const double *base, const double *emis, const float *ari, const float *shape,
                             const float *beta, float *rows, int32_t accumulate, void *stream);
+/* SEA-LEVEL ROWS — per-member global-mean sea-level rise from the STORED warming rows (and, optionally, the heat-uptake rows H of
+ * fiveeq_forcing_rows_*), each member with its own components (new; ADDITIVE: FIVEEQ_ABI_VERSION stays 13, sizeof(fiveeq_model)
+ * stays 448).  A member has n_comp <= 6 components (thermal expansion, glaciers, ice-sheet surface balance and discharge, land
+ * water, ...), each of one of two kinds:
+ *     relax   dS/dt = (Seq(T) - S) / tau   (Mengel et al. 2016), advanced exactly over one step with the row's T held
+ *     rate    dS/dt = Seq(T)               (the semi-empirical form of Rahmstorf 2007)
+ * with Seq(T) = (a + b x) x, x = T - T0, capped from above at cap (finite ice; +inf: no cap).  The pass is unit-agnostic.
+ *   n_scen                              1..64 scenarios, all in one launch; the parameters and eta are shared by them
+ *   n_comp                              1..6 components
+ *   rate_mask                           bit j set: component j is of kind rate; no bit at or above n_comp
+ *   n_members, ld                       members of the shard; row length of par, eta and S_io
+ *   n_rows                              rows of the call, each ONE model step after the one before, >= 0; 0 is a successful
+ *                                       no-op after the checks
+ *   dt                                  the model step, finite and > 0
+ *   T_rows dev                          the stored warming in the kernel precision (widened exactly): element (s, t, m) at
+ *                                       T_rows[s t_scen_stride + t t_row_stride + m]; both strides >= ld
+ *   par    dev [5][n_comp][ld] fp64     tau, a, b, T0, cap in this order; tau is read for the relax components only (> 0)
+ *   heat   dev fp64, may be NULL        H: element (s, t, m) at heat[s h_scen_stride + t h_row_stride + m], strides >= ld
+ *   eta    dev [ld] fp64                each member's expansion efficiency; required iff heat is given, not read without it
+ *   S_io   dev [n_scen][n_comp][ld] fp64   every component's state before the first row in, after the last row out
+ *   total  dev [n_scen][n_rows][ld_out] fp64
+ *   comps  dev [n_scen][n_rows][n_comp][ld_out] fp64, may be NULL: the component rows
+ *   ld_out                              row length of total and comps, >= n_members
+ * THE ARITHMETIC is fp64 whatever the kernel precision, each operation rounded on its own (no fma).  Once per call, for each
+ * relax component j of member m:   x = -dt / tau_j (IEEE division);   em1_j = expm1(x) by the library's own primitive — the
+ * value fiveeq_math_probe_f64(op = 0) returns for x.  Per scenario s and row t, with Tt = (double)T[s][t][m], for j ascending:
+ *     x = Tt - T0_j;  p = b_j * x;  c = a_j + p;  e = c * x;  if (e > cap_j) e = cap_j;        (a NaN e stays NaN)
+ *     relax:  v = S_j - e;  w = em1_j * v;  S_j = S_j + w
+ *     rate:   w = dt * e;   S_j = S_j + w
+ * then   acc = heat ? eta * H[s][t][m] : 0.0;   for j ascending: acc = acc + S_j;   total[s][t][m] = acc;
+ * comps[s][t][j][m] = S_j.  After the last row S_io holds S.  Components at or above n_comp do not exist: they are skipped,
+ * not computed with neutral values.
+ * The bits depend on (T, H, eta, par, S, dt) only: not on the launch shape, ld, how the members are cut into shards or how the
+ * rows are cut into calls (S_io carries the state, em1 is recomputed from the same tau).  A NaN in a member's T row makes that
+ * member's state NaN from that row on and touches no other member.  Columns [n_members, ld) of S_io and [n_members, ld_out) of
+ * total and comps are not touched.  FIVEEQ_E_INVALID for n_scen outside 1..64, n_comp outside 1..6, a rate_mask that is negative
+ * or has a bit at or above n_comp, n_members outside 1..2^31-1, ld < n_members, n_rows < 0, a dt that is not finite and > 0,
+ * t_row_stride or t_scen_stride < ld, with heat: h_row_stride or h_scen_stride < ld, then a NULL eta; ld_out < n_members; NULL
+ * T_rows, par, S_io or total; misaligned pointers (the kernel precision's size for T_rows, 8 bytes for the others) — in this
+ * order, before anything is launched.  Host twin (bit-identical given the same expm1):
+ * fiveeqscm_amd.sea_level.sea_level_rows_host. */
+int fiveeq_sea_level_rows_f64(int32_t n_scen, int32_t n_comp, int32_t rate_mask, int64_t n_members, int64_t ld, int32_t n_rows,
+                              double dt, const double *T_rows, int64_t t_row_stride, int64_t t_scen_stride, const double *par,
+                              const double *heat, int64_t h_row_stride, int64_t h_scen_stride, const double *eta, double *S_io,
+                              double *total, double *comps, int64_t ld_out, void *stream);
+int fiveeq_sea_level_rows_f32(int32_t n_scen, int32_t n_comp, int32_t rate_mask, int64_t n_members, int64_t ld, int32_t n_rows,
+                              double dt, const float *T_rows, int64_t t_row_stride, int64_t t_scen_stride, const double *par,
+                              const double *heat, int64_t h_row_stride, int64_t h_scen_stride, const double *eta, double *S_io,
+                              double *total, double *comps, int64_t ld_out, void *stream);
 /* FORCING SCALES UNDER THE SCENARIO AXIS (new; additive, FIVEEQ_ABI_VERSION stays 13): fiveeq_run_scen_* / fiveeq_plan_create_scen_*
  * with the forcing scales of fiveeq_run_forc_*.  The arguments of the scenario calls, then
  *   fscale dev [G + n_fext][ld]          SHARED by the scenarios, like r and q
